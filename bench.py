@@ -5,6 +5,13 @@ A "step" is one pass of the hot path (rmp2_step: FK -> J, Jdot qd -> leaves -> p
 sum -> resolve) over this rank's robot batch, inputs and outputs resident in HBM.
 
     python bench.py [--gpus N --steps K --warmup W --workload auto|config2|config3|config4|config5 --robots R]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps, writes its outputs (--dump-outputs) and prints the line; everything
+else this file measures or checks -- the result check against the CPU oracle, the roofline object, the nested `secondary`
+and `solve_auto` legs, the world-1 leg of an N > 1 config-4 job, the CPU baseline -- runs with `--full` only.
+`--dump-outputs DIR` writes the qdd the timed path left in its output buffers after its last step as DIR/<name>.npy
+(float32, at most 64 MB in all; the inputs are seeded, so two builds can be compared file for file).
 
 Workloads (BASELINE.json configs[1..4]; weak scaling: the per-GPU fleet is fixed):
   config3  (default at N = 1) Franka Panda cluttered set, 8 control points x 32 shared spheres, 65536 robots per
@@ -23,10 +30,10 @@ anything in this process touches a GPU) and fails loudly when the node has fewer
 `--solve pinv` (the default: the reference's only resolve, rmp.py:148-152, as one certifying launch) gives the line's `value`;
 the same workload under `--solve auto` (elimination without the certificate) rides along as the nested `solve_auto` object.
 
-Rank 0 prints ONE JSON line (contract in the task description): whole-job steps/s, the roofline fractions of the
-control-step kernel from the ALGORITHMIC bytes / flops of BASELINE.md section 3 (and, beside them, from the flops this run
-EXECUTED: `roofline.executed_frac`), and (N = 1) a CPU baseline timed on this box's host cores on a bounded sample.  N > 1
-lines carry `world1_same_workload_ms`: the same workload on every rank's own shard with a one-rank communicator, MAX over ranks
+Rank 0 prints ONE JSON line (contract in the task description): whole-job steps/s and, with `--full`, the roofline fractions
+of the control-step kernel from the ALGORITHMIC bytes / flops of BASELINE.md section 3 (and, beside them, from the flops this
+run EXECUTED: `roofline.executed_frac`), and (N = 1) a CPU baseline timed on this box's host cores on a bounded sample.  N > 1
+`--full` lines carry `world1_same_workload_ms`: the same workload on every rank's own shard with a one-rank communicator, MAX over ranks
 -- the like-for-like base of a weak-scaling efficiency.  No child process is started once HIP has been touched (host facts come
 from /proc, the libraries are built in `preflight()` before the first device call).
 """
@@ -342,6 +349,28 @@ class Timed:
         kern_ms = raw_ms / grp if grp > 1 else max(raw_ms - floor_ms, 1e-6)
         return dict(dt=dt, kernel_ms=kern_ms, grp=grp, raw_ms=raw_ms, floor_ms=floor_ms, settle=self.settle_launches,
                     host_issue_ms_per_step=t_host / steps * 1e3)
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: the output buffers the timed path left after its last step, one <path>/<name>.npy each (".rank<r>"
+    appended when world > 1), float32 / float64 as computed.  Over this rank's share of DUMP_BYTES every array keeps the same
+    fixed, seeded sample of its rows, in order -- the same rows for the same arguments, whatever the build."""
+    import numpy as np
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    budget = DUMP_BYTES // world - 4096 * len(host)          # (room for the .npy headers)
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if total > budget and len(a) > 1:
+            rows = np.random.default_rng(0).choice(len(a), max(1, len(a) * budget // total), replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(path, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
+    print(f"bench.py: rank {rank} wrote {', '.join(host)} to {path}", file=sys.stderr)
 
 
 def roofline_obj(kernel, kern, per_launch_bytes, per_launch_flops, bytes_rs, flops_rs, workload, R, bound="valu", exe=None):
@@ -672,7 +701,7 @@ def emulate_world(args, workload, dev, local_rank, use_dist):
     wl = WORKLOADS[workload]
     R = args.robots or wl["robots"]
     steps, warmup = min(args.steps, 500), min(args.warmup, 50)
-    rows, extra = [], {}
+    rows, extra, outputs = [], {}, {}
     if workload == "config5":
         curves = MixedFleetShard.calibrate_curves(local_rank) if args.calibrate else MixedFleetShard.DEFAULT_CURVES
         extra["cost_model"] = {"kind": "kernel time curves per robot type (us per step at a ladder of fleet sizes)",
@@ -688,6 +717,8 @@ def emulate_world(args, workload, dev, local_rank, use_dist):
                 if args.graph:
                     shard.capture()
                 k = Timed(dev, False).run(shard.step, steps, warmup)
+                if args.dump_outputs and pname == "calibrated":
+                    outputs.update({f"qdd_{key}.rank{r}": p["out"].cpu() for key, p in shard.parts.items()})
                 prow.append({"rank": r, "two_joint": shard.n_two_joint, "panda": shard.n_panda,
                              "us_per_step": k["dt"] / steps * 1e6, "est_us": shard.work / 1e3 if pname == "calibrated" else None,
                              "kernels": {key: p["engine"].last_kernel() for key, p in shard.parts.items()}})
@@ -711,12 +742,16 @@ def emulate_world(args, workload, dev, local_rank, use_dist):
             one_step, eng, desc, table, s, spheres_np, keep = build_config34(
                 workload, args, dev, local_rank, 0, 1, R, seed_rank=r, exch=exch)
             k = Timed(dev, use_dist).run(one_step, steps, warmup)
+            if args.dump_outputs:
+                outputs[f"qdd.rank{r}"] = keep[3].cpu()
             chk = check_against_oracle(desc, s, spheres_np, keep[3], what=f"{workload} rank {r}")
             rows.append({"rank": r, "robots": R, "us_per_step": k["dt"] / steps * 1e6, "kernel_us": k["kernel_ms"] * 1e3,
                          "kernel": eng.last_kernel(), "result_check": chk})
             del one_step, eng, keep
             gc.collect()
             torch.cuda.synchronize(dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     t = np.array([x["us_per_step"] for x in rows])
     total = R * W
     line = {
@@ -833,9 +868,12 @@ def worker(args) -> int:
     if workload in ("config2", "config3", "config3b", "config3c", "config3l", "config4"):
         one_step, eng, desc, table, s, spheres_np, keep = build_config34(workload, args, dev, local_rank, rank, world, R)
         kern = timer.run(one_step, args.steps, args.warmup)
-        # result check, outside the timed region: the buffers the timed steps wrote, against the oracle
-        line_extra["result_check"] = check_against_oracle(desc, s, spheres_np, keep[3], what=workload,
-                                                          pairs=(keep[4], keep[5]) if workload in ("config3b", "config3l") else None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"qdd": keep[3]}, rank, world)
+        if args.full:
+            # result check, outside the timed region: the buffers the timed steps wrote, against the oracle
+            line_extra["result_check"] = check_against_oracle(desc, s, spheres_np, keep[3], what=workload,
+                                                              pairs=(keep[4], keep[5]) if workload in ("config3b", "config3l") else None)
         if workload == "config4":
             ex = next(k for k in keep if hasattr(k, "start") and hasattr(k, "world"))
             line_extra["exchange"] = args.exchange
@@ -846,12 +884,12 @@ def worker(args) -> int:
             line_extra["rccl_nranks"] = int(ex.nranks) if args.exchange == "native" else (
                 None if args.rehearse_one_gpu else int(dist.get_world_size()))     # (a rehearsal's process group is gloo's)
             line_extra["exchange_depth"] = int(args.exchange_depth) if args.exchange == "native" else 1
-        if workload == "config4" and world > 1:
+        if workload == "config4" and world > 1 and args.full:
             line_extra["world1_same_workload_ms"], line_extra["world1_same_workload"] = world1_leg(
                 args, dev, local_rank, rank, world, R, timer)
         bytes_rs, flops_rs = wl["bytes"], wl["flops"]
         per_launch_bytes, per_launch_flops = bytes_rs * R, flops_rs * R
-        exe = executed_flops(eng, desc, keep[0], spheres_np, workload)
+        exe = executed_flops(eng, desc, keep[0], spheres_np, workload) if args.full else None
         kernel_name = eng.last_kernel() + " (chosen by fleet size, rmp2_hip.hip dispatch_solve)"
         total_robots = R * world
         bound = wl.get("bound", "valu")
@@ -882,27 +920,30 @@ def worker(args) -> int:
         one_step = shard.step
         exe = None
         kern = timer.run(one_step, args.steps, args.warmup)
-        # the dominant kernel (the Panda engine's) timed on its own right after the timed region, same buffers
-        kk = Timed(dev, False).run(shard.step_dominant, min(args.steps, 200), 10)
-        kern.update(kernel_ms=kk["kernel_ms"], grp=kk["grp"], raw_ms=kk["raw_ms"], floor_ms=kk["floor_ms"])
-        # result check of BOTH robot types of this rank's shard (outside the timed region), ragged lists and all
-        chk = {}
-        for key, part in shard.parts.items():
-            pq, pqd, pgoal, _ = part["keep"]
-            m = min(256, part["n"])
-            off = part["host"]["csr_offset"][: m + 1]
-            host = {"q": pq[:m].cpu().numpy(), "qd": pqd[:m].cpu().numpy(), "goal": pgoal[:m].cpu().numpy()}
-            if args.link_geometry:   # the oracle reads explicit pairs: one per list entry (fp64 closed form), far fillers beyond
-                pl_, po_ = link_pairs_for_lists(part["desc"], part["host"]["link_capsules"], part["host"]["spheres"], host["q"],
-                                                off, part["host"]["csr_index"])
-                chk[key] = check_against_oracle(part["desc"], host, None, part["out"], n=m, what=f"config5 {key} (link geometry)",
-                                                extra_kw=dict(p_link=pl_, p_obs=po_))
-            else:
-                chk[key] = check_against_oracle(part["desc"], host, part["host"]["spheres"], part["out"], n=m, what=f"config5 {key}",
-                                                extra_kw=dict(csr_offset=off, csr_index=part["host"]["csr_index"][: off[-1]]))
-            chk[key].pop("tolerance")
-        chk["tolerance"] = TOLERANCE_RULE
-        line_extra["result_check"] = chk
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {f"qdd_{key}": part["out"] for key, part in shard.parts.items()}, rank, world)
+        if args.full:
+            # the dominant kernel (the Panda engine's) timed on its own right after the timed region, same buffers
+            kk = Timed(dev, False).run(shard.step_dominant, min(args.steps, 200), 10)
+            kern.update(kernel_ms=kk["kernel_ms"], grp=kk["grp"], raw_ms=kk["raw_ms"], floor_ms=kk["floor_ms"])
+            # result check of BOTH robot types of this rank's shard (outside the timed region), ragged lists and all
+            chk = {}
+            for key, part in shard.parts.items():
+                pq, pqd, pgoal, _ = part["keep"]
+                m = min(256, part["n"])
+                off = part["host"]["csr_offset"][: m + 1]
+                host = {"q": pq[:m].cpu().numpy(), "qd": pqd[:m].cpu().numpy(), "goal": pgoal[:m].cpu().numpy()}
+                if args.link_geometry:   # the oracle reads explicit pairs: one per list entry (fp64 closed form), far fillers beyond
+                    pl_, po_ = link_pairs_for_lists(part["desc"], part["host"]["link_capsules"], part["host"]["spheres"], host["q"],
+                                                    off, part["host"]["csr_index"])
+                    chk[key] = check_against_oracle(part["desc"], host, None, part["out"], n=m, what=f"config5 {key} (link geometry)",
+                                                    extra_kw=dict(p_link=pl_, p_obs=po_))
+                else:
+                    chk[key] = check_against_oracle(part["desc"], host, part["host"]["spheres"], part["out"], n=m, what=f"config5 {key}",
+                                                    extra_kw=dict(csr_offset=off, csr_index=part["host"]["csr_index"][: off[-1]]))
+                chk[key].pop("tolerance")
+            chk["tolerance"] = TOLERANCE_RULE
+            line_extra["result_check"] = chk
         per_launch_bytes, per_launch_flops = shard.dominant_bytes, shard.dominant_flops
         bytes_rs = per_launch_bytes / max(shard.dominant_robots, 1)
         flops_rs = per_launch_flops / max(shard.dominant_robots, 1)
@@ -937,9 +978,10 @@ def worker(args) -> int:
             "data": "synthetic",
             "config": {"workload": wl["name"], "workload_key": workload, "robots_per_gpu": R, "solve": args.solve,
                        "parallelism": parallelism},
-            "roofline": roofline_obj(kernel_name, kern, per_launch_bytes, per_launch_flops, bytes_rs, flops_rs,
-                                     "config3" if workload == "config4" else workload, R, bound, exe),
         }
+        if args.full:
+            line["roofline"] = roofline_obj(kernel_name, kern, per_launch_bytes, per_launch_flops, bytes_rs, flops_rs,
+                                            "config3" if workload == "config4" else workload, R, bound, exe)
         line.update(line_extra)
         if args.rehearse_one_gpu:
             line["rehearsal"] = {
@@ -947,7 +989,7 @@ def worker(args) -> int:
                 "note": f"{world} rank processes time-sharing ONE GPU: executes the launcher, the rank agreement, the exchange's "
                         "all-rank fall-back and the barrier / MAX-over-ranks timing of the N > 1 path on a one-GPU box.  NOT a "
                         "scaling measurement: `value` is the ranks' robots over the time they took sharing the device"}
-        if workload in ("config3", "config4") and not args.no_secondary:
+        if workload in ("config3", "config4") and args.full and not args.no_secondary:
             # BASELINE configs[1] in the same process: the latency-bound fleet (4096 robots: one wave per SIMD)
             t2, d2 = Cf.config2(args.solve)
             eng2 = Engine(d2, local_rank)
@@ -963,7 +1005,7 @@ def worker(args) -> int:
                 "roofline": roofline_obj(eng2.last_kernel(), k2, w2["bytes"] * 4096, w2["flops"] * 4096, w2["bytes"], w2["flops"],
                                          "config2", 4096, "valu"),
                 "note": "latency regime: 1024 waves on 1024 SIMDs, ~3 us of the launch is dispatch floor (DESIGN.md section 5)"}
-        if workload == "config3" and not args.no_secondary:
+        if workload == "config3" and args.full and not args.no_secondary:
             # the same workload under the OTHER resolve, same process, same inputs.  The line's `value` is on solve = "pinv", the
             # reference's only resolve (rmp.py:153-154: one certifying launch); "auto" (plain elimination,
             # pseudo-inverse for flagged robots only) rides along so that what reference semantics cost stays visible
@@ -982,7 +1024,7 @@ def worker(args) -> int:
                 "max_abs_diff_to_" + args.solve: float((op - keep[3]).abs().nan_to_num(0.0).max().item()),
                 "note": ("plain elimination; the pseudo-inverse only for robots the elimination flags" if other == "auto" else
                          "full rank certified per robot inside the elimination (pinv = inv there), Jacobi pseudo-inverse for the rest")}
-        if not args.no_cpu_baseline and world == 1 and desc is not None:
+        if args.full and not args.no_cpu_baseline and world == 1 and desc is not None:
             line["cpu_baseline"] = cpu_baseline(workload, desc, table, s, spheres_np)
         emit(line)
     if use_dist:
@@ -1006,19 +1048,21 @@ def emit(line) -> None:
         os.write(REAL_STDOUT, text.encode())
 
 
-def preflight():
+def preflight(args):
     """Everything that may start a child process or read the host, done BEFORE this process can hold a HIP context (a process
     with one must not fork + exec on this pool): the host summary, the library build (hipcc, only when the sources changed;
-    rank 0 of a launcher, or the lone process) and the checker's library (oracle/: `make`, only when stale -- loading the
-    checker here is not using it; it is called after the timed region, in check_against_oracle / cpu_baseline)."""
+    rank 0 of a launcher, or the lone process) and, when a check will run (--full, --emulate-world), the checker's library
+    (oracle/: `make`, only when stale -- loading the checker here is not using it; it is called after the timed region, in
+    check_against_oracle / cpu_baseline)."""
     global HOST_SUMMARY
     HOST_SUMMARY = lscpu_summary()
     if os.environ.get("RANK", "0") == "0":
         import __graft_entry__ as ge
         ge.build_hip()
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import oracle as O
-        O.lib()
+        if args.full or args.emulate_world:
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import oracle as O
+            O.lib()
 
 
 def main():
@@ -1054,18 +1098,27 @@ def main():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="--gpus N on a node with ONE GPU: every rank on device 0, torch's gloo backend instead of RCCL (which "
                          "refuses two ranks on one device).  Executes the N > 1 control flow; the line is labelled a rehearsal")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the result check against the CPU oracle, the roofline object, the nested "
+                         "`secondary` (config 2) and `solve_auto` legs, the world-1 leg of an N > 1 config-4 job and the CPU "
+                         "baseline (--no-cpu-baseline / --no-secondary leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the qdd of the last step (every robot; a fixed, seeded sample of the "
+                         "rows beyond 64 MB in all) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args))
     global REAL_STDOUT
     sys.stdout.flush()
     REAL_STDOUT = os.dup(1)
     os.dup2(2, 1)
-    preflight()
+    preflight(args)
     sys.exit(worker(args))
 
 

@@ -100,7 +100,7 @@ def test_stub_collective_library_exports_what_the_exchange_binds():
 
 
 def test_committed_bench_line_keeps_the_contract():
-    """The line `python bench.py` printed on the GPU box this round (profiles/r05_bench_default.json): every field the driver's
+    """The line `python bench.py` printed on an MI355X in round 5, now `--full` (profiles/r05_bench_default.json): every field the driver's
     contract names, the roofline and cpu_baseline objects, the tolerance rule + robots admitted per clause in result_check, and the
     round-5 additions: `value` on solve = "pinv" with the auto leg nested, the executed-flop fraction beside the algorithmic one."""
     import json
@@ -126,6 +126,26 @@ def test_committed_bench_line_keeps_the_contract():
     assert line["value"] >= 1.43e9                                            # (the round-4 review's bar for the pinv headline)
     assert 0 < roof["executed_frac"] < roof["frac"] and roof["executed_flops_per_robot_step"] < 66.0e3
     assert len(open(os.path.join(ROOT, "profiles", "r05_bench_default.json")).read().strip().splitlines()) == 1   # ONE line on stdout
+
+
+def test_dump_outputs_writes_every_row_or_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the arrays as computed (float32 stays float32) under the byte budget; over it, the same seeded
+    rows of every array, in order, on every call -- two builds dump comparable files -- and within the budget."""
+    import numpy as np
+    import bench
+    a = torch.randn(1000, 9)
+    bench.dump_outputs(str(tmp_path / "all"), {"qdd": a})
+    got = np.load(tmp_path / "all" / "qdd.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 4096 + 300 * 9 * 4)
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), {"qdd_a": a, "qdd_b": a[:500].double()}, rank=1, world=1)
+    x, y = (np.load(tmp_path / d / "qdd_a.npy") for d in ("x", "y"))
+    b = np.load(tmp_path / "x" / "qdd_b.npy")
+    assert np.array_equal(x, y) and 0 < len(x) < 1000 and b.dtype == np.float64
+    assert x.nbytes + b.nbytes <= 300 * 9 * 4
+    rows = [int(np.flatnonzero((a.numpy() == r).all(axis=1))[0]) for r in x]
+    assert rows == sorted(rows)
 
 
 def test_spawned_ranks_share_device_0_in_a_rehearsal(monkeypatch):

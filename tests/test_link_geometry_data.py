@@ -1,7 +1,7 @@
 """Link / obstacle geometry the GPU closest-point code works on, checked on the CPU:
  * robots/panda_link_capsules.json (capsules fitted to the Panda's collision meshes; generator
-   tests/golden/make_panda_link_capsules.py): sane, picked up by urdf.link_capsules, and -- where the reference's meshes are at
-   hand (this container) -- containing every mesh vertex;
+   tests/golden/make_panda_link_capsules.py): sane, picked up by urdf.link_capsules, and containing every vertex of the
+   reference's collision meshes (stored in tests/golden/panda_collision_meshes.npz);
  * the reference's cylinder obstacles (simulation.py:245-261: flat caps) as capsules: the error of that approximation is
    confined to the cap region and bounded by (sqrt(2) - 1) r, attained at the rim."""
 import json
@@ -30,33 +30,23 @@ def test_fitted_panda_capsules_are_used_and_sane():
     assert np.allclose(stand_in[:, 3], 0.06)          # the default-radius stand-in is still what `fitted=None` gives
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/urdf/franka_panda/panda.urdf"), reason="the reference's meshes are not at hand")
-def test_fitted_panda_capsules_contain_the_collision_meshes():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("mk", os.path.join(ROOT, "tests", "golden", "make_panda_link_capsules.py"))
-    mk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mk)
-    from xml.etree import ElementTree
-    from riemannian_motion_policies_amd.urdf import rotation_from_rpy_reference_order, _floats
+def test_fitted_panda_capsules_contain_the_collision_meshes(golden_dir):
+    from riemannian_motion_policies_amd.urdf import rotation_from_rpy_reference_order
     data = json.load(open(os.path.join(ROOT, "riemannian_motion_policies_amd", "robots", "panda_link_capsules.json")))["links"]
-    root = ElementTree.parse(mk.REF_URDF).getroot()
+    # the reference's collision meshes (vertex sets) and their URDF origins: generator tests/golden/make_panda_collision_meshes.py
+    meshes = np.load(os.path.join(golden_dir, "panda_collision_meshes.npz"))
     seen = 0
-    for link in root.findall("link"):
-        col = link.find("collision")
-        mesh = col.find("geometry").find("mesh") if col is not None else None
-        if mesh is None:
-            continue
-        V = mk.read_obj_vertices(os.path.join(os.path.dirname(mk.REF_URDF), mesh.attrib["filename"].replace("package://", "")))
-        origin = col.find("origin")
-        xyz = np.asarray(_floats(origin.attrib.get("xyz") if origin is not None else None), dtype=np.float64)
-        Rc = rotation_from_rpy_reference_order(_floats(origin.attrib.get("rpy") if origin is not None else None)).astype(np.float64)
+    for name in meshes["links"]:
+        name = str(name)
+        V, xyz = meshes[f"{name}.vertices"], meshes[f"{name}.xyz"]
+        Rc = rotation_from_rpy_reference_order(meshes[f"{name}.rpy"]).astype(np.float64)
         P = V @ Rc.T + xyz
-        c = data[link.attrib["name"]]
+        c = data[name]
         a, b = np.asarray(c["a"]), np.asarray(c["b"])
         ab = b - a
         t = np.clip(((P - a) @ ab) / max(float(ab @ ab), 1e-30), 0.0, 1.0)
         dist = np.linalg.norm(P - (a + np.outer(t, ab)), axis=1)
-        assert dist.max() <= c["r"] + 1e-6, (link.attrib["name"], dist.max(), c["r"])     # contains every vertex (hence the hull)
+        assert dist.max() <= c["r"] + 1e-6, (name, dist.max(), c["r"])     # contains every vertex (hence the hull)
         assert dist.max() >= c["r"] - 1e-3, "the capsule is tight: some vertex touches its surface"
         seen += 1
     assert seen == 11

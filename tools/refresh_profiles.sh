@@ -8,17 +8,17 @@
 set -x
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r01c; mkdir -p $O
-python bench.py > $O/bench_config2.json 2> $O/bench_config2.err
-python bench.py --workload config3 > $O/bench_config3.json 2> $O/bench_config3.err
-python bench.py --robots 65536 --no-cpu-baseline > $O/bench_config2_64k.json 2>/dev/null
-python bench.py --workload config3 --robots 4096 --no-cpu-baseline > $O/bench_config3_4k.json 2>/dev/null
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --no-cpu-baseline > $O/bench_config2_torchrun1.json 2>$O/torchrun.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -- python3 bench.py --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt3 -- python3 bench.py --workload config3 --steps 100 --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/f2 -- python3 bench.py --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/w2 -- python3 bench.py --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/f3 -- python3 bench.py --workload config3 --steps 100 --no-cpu-baseline > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/w3 -- python3 bench.py --workload config3 --steps 100 --no-cpu-baseline > /dev/null 2>&1
+python bench.py --full > $O/bench_config2.json 2> $O/bench_config2.err
+python bench.py --full --workload config3 > $O/bench_config3.json 2> $O/bench_config3.err
+python bench.py --full --robots 65536 --no-cpu-baseline > $O/bench_config2_64k.json 2>/dev/null
+python bench.py --full --workload config3 --robots 4096 --no-cpu-baseline > $O/bench_config3_4k.json 2>/dev/null
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --no-cpu-baseline > $O/bench_config2_torchrun1.json 2>$O/torchrun.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -- python3 bench.py --full --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt3 -- python3 bench.py --full --workload config3 --steps 100 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/f2 -- python3 bench.py --full --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/w2 -- python3 bench.py --full --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/f3 -- python3 bench.py --full --workload config3 --steps 100 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/w3 -- python3 bench.py --full --workload config3 --steps 100 --no-cpu-baseline > /dev/null 2>&1
 python tools/pmc_traffic.py $O/f2 $O/w2 config2 4096 $O/traffic_config2.json
 python tools/pmc_traffic.py $O/f3 $O/w3 config3 65536 $O/traffic_config3.json
 for R in 4096 65536; do rocprofv3 --kernel-trace --output-format csv -d $O/abl_$R -- python3 tools/phase_timing.py $R > /dev/null 2>&1; python tools/trace_summary.py $O/abl_$R > $O/ablation_R$R.txt; done
