@@ -35,12 +35,14 @@
 extern "C" {
 #endif
 
-#define RMP2_ABI_VERSION 4 /* 4: rmp2_reserve, rmp2_exchange_nranks, RMP2_STATUS_JACOBI; attached-point leaves take a table + link_capsules */
+#define RMP2_ABI_VERSION 5 /* 5: self collision (rmp2_set_self_collision, rmp2_self_pairs); 4: rmp2_reserve, rmp2_exchange_nranks,
+                              RMP2_STATUS_JACOBI; attached-point leaves take a table + link_capsules */
 
 #define RMP2_MAX_FRAMES 32  /* frames (= URDF joints) per robot type                    */
 #define RMP2_MAX_DOF 16     /* actuated joints per robot type                            */
 #define RMP2_MAX_LEAVES 48  /* leaf RMPs per set                                          */
 #define RMP2_MAX_PARAMS 12  /* scalar parameters per leaf                                 */
+#define RMP2_MAX_SELF_PAIRS 256 /* self-collision pairs per robot (rmp2_set_self_collision) */
 
 /* ---- error codes --------------------------------------------------------------------- */
 #define RMP2_OK 0
@@ -416,6 +418,43 @@ int rmp2_closest_points(rmp2_handle *h, const float *q, const rmp2_obstacles *ta
  * surfaces (capsule-vs-sphere, capsule-vs-capsule).  link_capsules == NULL: rmp2_closest_points. */
 int rmp2_closest_points_links(rmp2_handle *h, const float *q, const rmp2_obstacles *table, const float *link_capsules,
                               float *p_link, float *p_obs, int32_t R, void *stream);
+
+/* ---- self collision: link-vs-link pairs formed on the device ---------------------------------------------------------
+ * The reference's self-avoidance data path (simulation.py:411-441 with helper/pybullet_helper.py:46-68; switched off there at
+ * simulation.py:406): every link A that carries a distance or attached-point leaf is paired with every other link B that has a
+ * collision shape -- the fixed base included -- unless one is within 3 parent hops of the other (urdf.self_collision_pairs).
+ * "linkB is interpreted as obstacle": a self pair is one more entry in A's leaf's pair range, with the values and the derivative
+ * rule of an obstacle pair of that leaf (FK_DISTANCE: d = |p_link - p_obs|, derivative through the frame origin, quirk Q5;
+ * FK_POINT: the attached point with its lever arm).  No derivative flows through B; there is no two-body Jacobian.
+ *
+ * rmp2_set_self_collision: copy the pair list into the handle.  pairs (host) [n_pairs][2] = (descriptor leaf index of an
+ * FK_DISTANCE or FK_POINT leaf, frame B or -1 = the base link); capsules (host) [n_frames + 1][8] = (a.xyz, radius, b.xyz, -)
+ * per frame in FRAME coordinates, the last row the base link in base coordinates (urdf.self_collision_capsules).  A leaf's pairs
+ * keep the order given; leaves in descriptor order.  n_pairs == 0 or pairs == NULL turns the feature off: the handle then steps
+ * exactly as one on which this was never called.  At most RMP2_MAX_SELF_PAIRS pairs; B must differ from the leaf's own frame.
+ * Synchronous (one small host-to-device copy).
+ *
+ * rmp2_self_pairs: the stand-alone stage.  Per robot, leaf ordinal i's pairs (i-th pair-consuming leaf in descriptor order)
+ * at [S_0 + ... + S_{i-1}, + S_i), S_l = pairs of leaf l:
+ *   FK_DISTANCE leaf: p_link, p_obs = the nearest points of the two capsule SURFACES in the base frame;
+ *   FK_POINT leaf:    p_link = relative_position (the point on A's surface in A's joint frame), p_obs = unit normal (base frame),
+ *                     dist = distance (data_management.py:33-53), as rmp2_device.h link_pair_fields forms them for a table.
+ * p_link, p_obs device [R][S][3]; dist device [R][S] (required when an attached-point leaf has self pairs, else may be NULL).
+ * Intersecting capsule axes take the fixed normal +z (finite).  Feeding the arrays to an EXPLICIT_PAIRS step reproduces what
+ * rmp2_step does with self collision on and no obstacle table.
+ *
+ * rmp2_step on a handle with self collision: the stage, then the explicit-pair step (two launches).  Obstacle input NONE, or
+ * SHARED_SPHERES with sphere or capsule records (with or without link_capsules) on sets without attached-point leaves: leaf l's
+ * range is then [K obstacle pairs | S_l self pairs], the obstacle half bit-identical to rmp2_closest_points_links on the same
+ * inputs (its default wave form).  Memory: a buffer of the handle of 24 P (+ 4 P with attached-point leaves) bytes per robot,
+ * P = sum over the pair leaves of (K + S_l) -- config 3 with 32 spheres and 44 self pairs: 7 200 B per robot, 472 MB at 65 536
+ * robots.  Grown on demand (refused with the byte count when it exceeds the free device memory, and inside a stream capture:
+ * step once outside it first).  RMP2_ERR_UNSUPPORTED, with a message naming the combination: RAGGED_SPHERES lists, CYLINDER
+ * tables, caller-supplied EXPLICIT_PAIRS, a table with attached-point leaves, rmp2_rollout, rmp2_step_pair and
+ * rmp2_exchange_step.  Out of scope: those forms, a symmetric (two-body) self-pair Jacobian, mesh-exact distances (capsules
+ * stand in, as for obstacles). */
+int rmp2_set_self_collision(rmp2_handle *h, int32_t n_pairs, const int32_t *pairs, const float *capsules);
+int rmp2_self_pairs(rmp2_handle *h, const float *q, float *p_link, float *p_obs, float *dist, int32_t R, void *stream);
 
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,

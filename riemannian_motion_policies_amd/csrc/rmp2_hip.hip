@@ -909,6 +909,235 @@ rmp2_closest_wave_kernel(const DevProgram* __restrict__ prog, const float* __res
   }
 }
 
+// ---- self collision (include/rmp2.h rmp2_set_self_collision) ---------------------------------------------------------------
+// The pair list of a handle, compiled by rmp2_set_self_collision.  "Pair leaves" are the leaves that take per-pair obstacle data
+// (FK_DISTANCE and FK_POINT), numbered in descriptor order (the ordinal); B slots are the distinct links that appear as B.
+struct SelfProg {
+  int32_t n_leaves;                          // pair leaves L
+  int32_t n_b;                               // B slots
+  int32_t n_pairs;                           // S = self pairs per robot
+  int32_t base_slot;                         // B slot of the base link, -1: none
+  int32_t n_dist;                            // FK_DISTANCE leaves (rows of the obstacle stage's link segments)
+  int32_t pad_[3];
+  int32_t ord_of_leaf[RMP2_MAX_LEAVES];      // descriptor leaf -> pair-leaf ordinal, -1: not a pair leaf
+  int32_t dord[RMP2_MAX_LEAVES];             // ordinal -> FK_DISTANCE ordinal (obstacle rows), -1: attached-point leaf
+  int32_t self_begin[RMP2_MAX_LEAVES + 1];   // ordinal -> first self pair (prefix sums of S_l)
+  int32_t b_slot_of_frame[RMP2_MAX_FRAMES];  // frame -> B slot, -1: the frame is no B link (the marker of the B walk)
+  int32_t pair_b[RMP2_MAX_SELF_PAIRS];       // self pair -> B slot
+  float leaf_cap[RMP2_MAX_LEAVES][8];        // ordinal -> capsule of the leaf's link in its frame coordinates
+  float b_cap[RMP2_MAX_FRAMES + 1][8];       // B slot -> capsule in its frame coordinates (the base: base coordinates)
+};
+
+// Float4 records per robot in the stage's LDS: obstacle segments (2 per FK_DISTANCE leaf, only with a table), self segments
+// (2 per pair leaf), the frame of each pair leaf (3: rows of R with the origin in .w), B segments (2 per B slot).
+__host__ __device__ inline int self_lds_records(int n_dist_obs, int n_leaves, int n_b) { return 2 * n_dist_obs + 5 * n_leaves + 2 * n_b; }
+
+// The self-pair stage (with the obstacle pairs of a shared table when OBS): one wave per nr = kClosestRobots robots, as
+// rmp2_closest_wave_kernel.  Phase 1, a lane per robot: a walk of the step's program (`prog`: the pair leaves' frames, exactly the
+// FK the obstacle stage computes) puts each pair leaf's link segment, its frame, and -- OBS -- the obstacle stage's segment of each
+// distance leaf into LDS; a second walk, of the unpruned program (`prog_full`: leaf-less frames are not in the step's), puts the
+// segment of every frame the B marker names.  Phase 2, a lane per pair: leaf l's range is [K obstacle pairs | S_l self pairs]
+// (K = 0 without a table and for attached-point leaves); a chunk of 64 lanes writes 64 consecutive pairs of one robot per store.
+// Obstacle pairs: the closed forms of rmp2_closest_wave_kernel, operation for operation (bit-identical outputs).  Self pairs:
+// rmp2_device.h link_pair_fields (the crossing guard keeps intersecting axes finite).
+template <int SLOTS, bool OBS, bool LINK, bool CAPS>
+__global__ void __launch_bounds__(kWave)
+rmp2_self_stage_kernel(const DevProgram* __restrict__ prog, const DevProgram* __restrict__ prog_full, const SelfProg* __restrict__ sp,
+                       const float* __restrict__ q, const ObsArgs obs, const float* __restrict__ link_caps, float* __restrict__ p_link,
+                       float* __restrict__ p_obs, float* __restrict__ dist, int P, int R, int nr) {
+  extern __shared__ float4 lds[];
+  const int L = sp->n_leaves, NB = sp->n_b, ND = OBS ? sp->n_dist : 0, K = OBS ? obs.n_spheres : 0;
+  const int W = self_lds_records(ND, L, NB);
+  const int o_self = 2 * ND, o_rot = o_self + 2 * L, o_b = o_rot + 3 * L;   // record offsets inside a robot's W records
+  const int lane = threadIdx.x;
+  const int r0 = blockIdx.x * nr;
+  const int robot = r0 + lane;
+  if (lane < nr && robot < R) {
+    float4* my = lds + (size_t)lane * W;
+    const float* my_q = q + (size_t)robot * prog->n_dof;
+    FrameState cur;
+    FrameState slot[SLOTS > 0 ? SLOTS : 1];
+    for (int k = 0; k < prog->n_ops; ++k) {
+      const DevOp& op = prog->ops[k];
+      if (SLOTS > 0 && op.restore >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+          if (op.restore == s) cur = slot[s];
+      }
+      float z[3];
+      visit_frame<false>(cur, op, op.qidx >= 0 ? my_q[op.qidx] : 0.f, 0.f, op.restore == -2, z);
+      if (SLOTS > 0 && op.save >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+          if (op.save == s) slot[s] = cur;
+      }
+      for (int li = 0; li < op.leaf_count; ++li) {
+        const DevLeaf& lf = prog->leaves[prog->fk_leaves[op.leaf_begin + li]];
+        const int o = sp->ord_of_leaf[lf.index];
+        if (o < 0) continue;
+        if (OBS && lf.taskmap == RMP2_TASKMAP_FK_DISTANCE) {   // (rmp2_closest_wave_kernel's segment of the leaf)
+          const int ord = sp->dord[o];
+          float4 a = make_float4(cur.p[0], cur.p[1], cur.p[2], 0.f), b = a;
+          if (LINK) {
+            const float* lc = link_caps + 8 * ord;
+            float A[3], B[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+              A[i] = cur.p[i] + cur.R[3 * i] * lc[0] + cur.R[3 * i + 1] * lc[1] + cur.R[3 * i + 2] * lc[2];
+              B[i] = cur.p[i] + cur.R[3 * i] * lc[4] + cur.R[3 * i + 1] * lc[5] + cur.R[3 * i + 2] * lc[6];
+            }
+            a = make_float4(A[0], A[1], A[2], lc[3]);
+            b = make_float4(B[0], B[1], B[2], 0.f);
+          }
+          my[2 * ord] = a;
+          my[2 * ord + 1] = b;
+        }
+        const float* lc = sp->leaf_cap[o];
+        float A[3], B[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          A[i] = cur.p[i] + cur.R[3 * i] * lc[0] + cur.R[3 * i + 1] * lc[1] + cur.R[3 * i + 2] * lc[2];
+          B[i] = cur.p[i] + cur.R[3 * i] * lc[4] + cur.R[3 * i + 1] * lc[5] + cur.R[3 * i + 2] * lc[6];
+        }
+        my[o_self + 2 * o] = make_float4(A[0], A[1], A[2], lc[3]);
+        my[o_self + 2 * o + 1] = make_float4(B[0], B[1], B[2], 0.f);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) my[o_rot + 3 * o + i] = make_float4(cur.R[3 * i], cur.R[3 * i + 1], cur.R[3 * i + 2], cur.p[i]);
+      }
+    }
+    // the B links: the unpruned walk, a segment for every marked frame
+    for (int k = 0; k < prog_full->n_ops; ++k) {
+      const DevOp& op = prog_full->ops[k];
+      if (SLOTS > 0 && op.restore >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+          if (op.restore == s) cur = slot[s];
+      }
+      float z[3];
+      visit_frame<false>(cur, op, op.qidx >= 0 ? my_q[op.qidx] : 0.f, 0.f, op.restore == -2, z);
+      if (SLOTS > 0 && op.save >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+          if (op.save == s) slot[s] = cur;
+      }
+      const int b = sp->b_slot_of_frame[op.frame];
+      if (b < 0) continue;
+      const float* bc = sp->b_cap[b];
+      float A[3], B[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        A[i] = cur.p[i] + cur.R[3 * i] * bc[0] + cur.R[3 * i + 1] * bc[1] + cur.R[3 * i + 2] * bc[2];
+        B[i] = cur.p[i] + cur.R[3 * i] * bc[4] + cur.R[3 * i + 1] * bc[5] + cur.R[3 * i + 2] * bc[6];
+      }
+      my[o_b + 2 * b] = make_float4(A[0], A[1], A[2], bc[3]);
+      my[o_b + 2 * b + 1] = make_float4(B[0], B[1], B[2], 0.f);
+    }
+    if (sp->base_slot >= 0) {   // the fixed base: its capsule is in base coordinates already
+      const float* bc = sp->b_cap[sp->base_slot];
+      my[o_b + 2 * sp->base_slot] = make_float4(bc[0], bc[1], bc[2], bc[3]);
+      my[o_b + 2 * sp->base_slot + 1] = make_float4(bc[4], bc[5], bc[6], 0.f);
+    }
+  }
+  __syncthreads();
+  const int n_live = min(nr, R - r0);
+  for (int p0 = 0; p0 < P; p0 += kWave) {
+    const int p = p0 + lane;
+    const bool ok = p < P;
+    // which leaf range the pair falls in, and which half of it
+    int o = 0, begin = 0, kl = 0;
+    for (int t = 0; t < L; ++t) {
+      const int kt = (OBS && sp->dord[t] >= 0) ? K : 0;
+      const int len = kt + sp->self_begin[t + 1] - sp->self_begin[t];
+      if (p >= begin + len) {
+        begin += len;
+        continue;
+      }
+      o = t, kl = kt;
+      break;
+    }
+    const int i = (ok ? p : begin) - begin;
+    const bool is_obs = OBS && i < kl;
+    const int bi = is_obs ? i : 0;
+    const int j = is_obs ? 0 : min(sp->self_begin[o] + (i - kl), RMP2_MAX_SELF_PAIRS - 1);
+    const int bslot = ok ? sp->pair_b[j] : 0;
+    const bool point = sp->dord[o] < 0;
+    const int leaf = OBS ? max(sp->dord[o], 0) : 0;
+    float4 ca, cb;
+    if (OBS && CAPS) {
+      ca = reinterpret_cast<const float4*>(obs.spheres)[2 * bi];
+      cb = reinterpret_cast<const float4*>(obs.spheres)[2 * bi + 1];
+    } else if (OBS) {
+      ca = cb = reinterpret_cast<const float4*>(obs.spheres)[bi];
+    } else {
+      ca = cb = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float r_obs = ca.w;
+    size_t off = ((size_t)r0 * P + p) * 3;
+    for (int r = 0; r < n_live; ++r, off += (size_t)P * 3) {
+      const float4* rec = lds + (size_t)r * W;
+      if (is_obs) {
+        const float4 sa = rec[2 * leaf];
+        float X[3] = {sa.x, sa.y, sa.z}, Y[3] = {ca.x, ca.y, ca.z};  // nearest points of the two axes
+        if (LINK) {
+          const float4 sb = rec[2 * leaf + 1];
+          const float A[3] = {sa.x, sa.y, sa.z}, B[3] = {sb.x, sb.y, sb.z};
+          const float C[3] = {ca.x, ca.y, ca.z}, D[3] = {cb.x, cb.y, cb.z};
+          float sl, to = 0.f;
+          if (CAPS) {
+            segment_segment(A, B, C, D, sl, to);
+          } else {  // (segment_segment with a point as the second segment)
+            const float d1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+            const float rr[3] = {A[0] - C[0], A[1] - C[1], A[2] - C[2]};
+            const float aa = d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2];
+            const float cc = d1[0] * rr[0] + d1[1] * rr[1] + d1[2] * rr[2];
+            sl = aa > 0.f ? fminf(fmaxf(-cc / aa, 0.f), 1.f) : 0.f;
+          }
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            X[c] = A[c] + sl * (B[c] - A[c]);
+            if (CAPS) Y[c] = C[c] + to * (D[c] - C[c]);
+          }
+        } else if (CAPS) {
+          capsule_centre(ca, cb, X, Y);
+        }
+        const float n[3] = {X[0] - Y[0], X[1] - Y[1], X[2] - Y[2]};
+        const float inv = 1.0f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        if (ok) {
+          const float wl = LINK ? sa.w * inv : 0.f, wo = r_obs * inv;
+          __builtin_nontemporal_store(f32x3{X[0] - wl * n[0], X[1] - wl * n[1], X[2] - wl * n[2]}, reinterpret_cast<f32x3*>(p_link + off));
+          __builtin_nontemporal_store(f32x3{Y[0] + wo * n[0], Y[1] + wo * n[1], Y[2] + wo * n[2]}, reinterpret_cast<f32x3*>(p_obs + off));
+        }
+        continue;
+      }
+      // self pair: leaf o's link against B (an obstacle for the step)
+      const float4 la = rec[o_self + 2 * o], lb = rec[o_self + 2 * o + 1];
+      const float4 ba = rec[o_b + 2 * bslot], bb = rec[o_b + 2 * bslot + 1];
+      const float LA[3] = {la.x, la.y, la.z}, LD[3] = {lb.x - la.x, lb.y - la.y, lb.z - la.z};
+      const float laa = dot3(LD, LD);
+      const float inv_laa = laa > 0.f ? 1.0f / laa : 0.f;
+      float P3[3] = {0.f, 0.f, 0.f};
+      float4 rw[3];
+      if (point) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rw[c] = rec[o_rot + 3 * o + c], P3[c] = rw[c].w;
+      }
+      float rr[3], nv[3], dd;
+      link_pair_fields(LA, LD, laa, inv_laa, la.w, ba, bb, P3, rr, nv, dd);
+      if (!ok) continue;
+      if (point) {   // relative_position in the joint frame R^T r, normal_vec, distance (data_management.py:33-53)
+        const float rel[3] = {rw[0].x * rr[0] + rw[1].x * rr[1] + rw[2].x * rr[2], rw[0].y * rr[0] + rw[1].y * rr[1] + rw[2].y * rr[2],
+                              rw[0].z * rr[0] + rw[1].z * rr[1] + rw[2].z * rr[2]};
+        __builtin_nontemporal_store(f32x3{rel[0], rel[1], rel[2]}, reinterpret_cast<f32x3*>(p_link + off));
+        __builtin_nontemporal_store(f32x3{nv[0], nv[1], nv[2]}, reinterpret_cast<f32x3*>(p_obs + off));
+      } else {       // the two surface points: p_link - p_obs = dd nv
+        __builtin_nontemporal_store(f32x3{rr[0], rr[1], rr[2]}, reinterpret_cast<f32x3*>(p_link + off));
+        __builtin_nontemporal_store(f32x3{rr[0] - dd * nv[0], rr[1] - dd * nv[1], rr[2] - dd * nv[2]}, reinterpret_cast<f32x3*>(p_obs + off));
+      }
+      if (dist) __builtin_nontemporal_store(dd, dist + off / 3);
+    }
+  }
+}
+
 // x = vec(T_frame), xd = J qd, J = d vec(T)/dq, c = Jdot qd   (kinematics.py:250-270)
 template <int SLOTS>
 __global__ void __launch_bounds__(kWave)
@@ -1897,6 +2126,12 @@ int rmp2_create(const rmp2_desc* desc, int device, rmp2_handle** out) {
     h->cull_c0 = std::max(h->cull_c0, desc->leaves[l].params[7] + desc->leaves[l].params[0]);
   for (int l = 0; l < desc->n_leaves; ++l)
     if (desc->leaves[l].taskmap == RMP2_TASKMAP_FK_POINT) h->has_point = true;
+  for (int l = 0; l < desc->n_leaves; ++l)
+    if (desc->leaves[l].taskmap == RMP2_TASKMAP_FK_DISTANCE || desc->leaves[l].taskmap == RMP2_TASKMAP_FK_POINT) {
+      h->pair_leaves.push_back(l);
+      h->pair_leaf_frame.push_back(desc->leaves[l].frame);
+      h->pair_leaf_point.push_back(desc->leaves[l].taskmap == RMP2_TASKMAP_FK_POINT ? 1 : 0);
+    }
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipMalloc(&h->d_prog, sizeof(DevProgram));
   if (e == hipSuccess) e = hipMemcpy(h->d_prog, &P, sizeof(DevProgram), hipMemcpyHostToDevice);
@@ -1957,6 +2192,8 @@ int rmp2_destroy(rmp2_handle* h) {
   if (h->d_scratch) (void)hipFree(h->d_scratch);
   if (h->d_system) (void)hipFree(h->d_system);
   if (h->d_pairs) (void)hipFree(h->d_pairs);
+  if (h->d_self) (void)hipFree(h->d_self);
+  if (h->d_self_buf) (void)hipFree(h->d_self_buf);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
   return RMP2_OK;
@@ -2100,6 +2337,113 @@ int rmp2_reserve(rmp2_handle* h, int32_t R) {
   return RMP2_OK;
 }
 
+// Launch of rmp2_self_stage_kernel: `table` = a SHARED_SPHERES table whose pairs come first in each distance leaf's range, or
+// NULL (self pairs only).  P = pairs per robot of the layout.
+static int launch_self_stage(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
+                             int P, int32_t R, hipStream_t s) {
+  ObsArgs o;
+  std::memset(&o, 0, sizeof(o));
+  const int n_dist = (int)h->distance_leaves.size();
+  const bool with_table = table != nullptr;
+  if (with_table) {
+    o.mode = table->mode;
+    o.n_spheres = table->n_spheres;
+    o.capsule = table->primitive != RMP2_PRIM_SPHERE ? 1 : 0;
+    o.spheres = table->spheres;
+  }
+  const int W = self_lds_records(with_table ? n_dist : 0, (int)h->pair_leaves.size(), h->self_n_b);
+  // robots per wave: kClosestRobots (64 per wave measured slower for config 3 at 65 536 robots: 105 against 72 us for the self
+  // stage alone -- a quarter of the waves, each walking phase 2 for four times the robots)
+  const int nr = kClosestRobots;
+  const size_t lds_bytes = sizeof(float4) * (size_t)W * nr;
+  const int blocks = (R + nr - 1) / nr;
+  const SelfProg* sp = static_cast<const SelfProg*>(h->d_self);
+  const float* lc = with_table ? table->link_capsules : nullptr;
+#define RMP2_SELF_STAGE_(OBS_, LINK_, CAPS_)                                                                                   \
+  hipLaunchKernelGGL((rmp2_self_stage_kernel<2, OBS_, LINK_, CAPS_>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog,      \
+                     h->d_prog_full, sp, q, o, lc, p_link, p_obs, dist, P, (int)R, nr)
+  if (!with_table) RMP2_SELF_STAGE_(false, false, false);
+  else if (lc && o.capsule) RMP2_SELF_STAGE_(true, true, true);
+  else if (lc) RMP2_SELF_STAGE_(true, true, false);
+  else if (o.capsule) RMP2_SELF_STAGE_(true, false, true);
+  else RMP2_SELF_STAGE_(true, false, false);
+#undef RMP2_SELF_STAGE_
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
+// The staged step of a handle with self collision (include/rmp2.h): validates the obstacle input, forms every pair leaf's range
+// [K obstacle pairs | S_l self pairs] in the handle's buffer and describes it as EXPLICIT_PAIRS in `staged`.
+static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs, const RolloutArgs& ro, int32_t R, void* stream,
+                      rmp2_obstacles& staged) {
+  if (ro.n_iters != 1 || ro.substeps != 0)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
+  const int mode = obs ? obs->mode : RMP2_OBS_NONE;
+  if (mode == RMP2_OBS_EXPLICIT_PAIRS)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision with caller-supplied EXPLICIT_PAIRS: the self pairs would have to be merged "
+                                         "into the caller's ranges -- append rmp2_self_pairs' output to them and step a handle without "
+                                         "self collision");
+  if (mode == RMP2_OBS_RAGGED_SPHERES)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision over RAGGED_SPHERES lists: not supported (shared tables only)");
+  if (mode != RMP2_OBS_NONE && mode != RMP2_OBS_SHARED_SPHERES) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "unknown obstacle mode");
+  if (!q) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "q, qd and out->qdd are required");
+  const bool with_table = mode == RMP2_OBS_SHARED_SPHERES && obs->n_spheres != 0;
+  if (with_table) {
+    if (obs->n_spheres < 0 || !obs->spheres) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "sphere table missing");
+    if (obs->primitive == RMP2_PRIM_CYLINDER)
+      return fail(h, RMP2_ERR_UNSUPPORTED, "self collision with a CYLINDER table: not supported (sphere or capsule records)");
+    if (obs->primitive != RMP2_PRIM_SPHERE && obs->primitive != RMP2_PRIM_CAPSULE)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "unknown obstacle primitive");
+    if (h->has_point)
+      return fail(h, RMP2_ERR_UNSUPPORTED, "self collision with an obstacle table on a set with attached-point leaves: not supported "
+                                           "(obstacle input NONE, or a set of distance leaves)");
+  }
+  const size_t K = with_table ? (size_t)obs->n_spheres : 0;
+  const size_t L = h->pair_leaves.size();
+  size_t P = 0;
+  int32_t pb[RMP2_MAX_LEAVES + 1];
+  for (int l = 0, o = 0; l <= RMP2_MAX_LEAVES; ++l) {
+    pb[l] = (int32_t)P;
+    if (o < (int)L && h->pair_leaves[o] == l) {
+      P += (h->pair_leaf_point[o] ? 0 : K) + (size_t)h->self_counts[o];
+      ++o;
+    }
+  }
+  if (P > (size_t)INT32_MAX / 4) return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: too many pairs per robot");
+  // buffer: p_link | p_obs [R][P][3] (+ dist [R][P] with attached-point leaves) -- 24 P (+ 4 P) bytes per robot (include/rmp2.h)
+  const size_t arr = (size_t)R * P * 3;
+  const size_t need = 2 * arr + (h->has_point ? (size_t)R * P : 0);
+  hipStream_t s = (hipStream_t)stream;
+  if (need > h->self_buf_floats) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+      return fail(h, RMP2_ERR_UNSUPPORTED, "self collision as stage + explicit-pair step: the handle's pair buffer must grow -- step once "
+                                           "outside the capture first");
+    if (int rc = use_device(h)) return rc;
+    if (h->d_self_buf) HIP_TRY(h, hipFree(h->d_self_buf));   // (synchronises the device: no launch still reads the old buffer)
+    h->d_self_buf = nullptr, h->self_buf_floats = 0;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    if (sizeof(float) * need > free_b)
+      return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: the stage's pair buffer needs " + std::to_string(sizeof(float) * need) +
+                                               " bytes (" + std::to_string(sizeof(float) * need / (size_t)R) + " per robot), " +
+                                               std::to_string(free_b) + " bytes of device memory are free -- step a smaller fleet");
+    HIP_TRY(h, hipMalloc(&h->d_self_buf, sizeof(float) * need));
+    h->self_buf_floats = need;
+  }
+  if (int rc = use_device(h)) return rc;
+  float* const pl = h->d_self_buf;
+  float* const po = pl + arr;
+  float* const dd = h->has_point ? po + arr : nullptr;
+  if (int rc = launch_self_stage(h, q, with_table ? obs : nullptr, pl, po, dd, (int)P, R, s)) return rc;
+  std::memset(&staged, 0, sizeof(staged));
+  staged.mode = RMP2_OBS_EXPLICIT_PAIRS;
+  staged.n_pairs = (int32_t)P;
+  for (int l = 0; l <= RMP2_MAX_LEAVES; ++l) staged.pair_begin[l] = pb[l];
+  staged.p_link = pl, staged.p_obs = po, staged.dist = dd;
+  return RMP2_OK;
+}
+
 static int step_impl(rmp2_handle* h, const float* q, const float* qd, const float* goal, int32_t goal_stride,
                      const rmp2_obstacles* obs, const rmp2_outputs* out, const RolloutArgs& ro, int32_t R, void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
@@ -2114,6 +2458,10 @@ static int step_impl(rmp2_handle* h, const float* q, const float* qd, const floa
   // rmp2_gather_list_pairs_kernel lays out one pair per list entry at L = the fleet's longest list slots per leaf -- L is read back
   // from csr_offset, so this form synchronises the stream and is refused inside a stream capture.
   rmp2_obstacles staged;
+  if (h->self_n_pairs > 0) {   // self collision: the self stage (+ the table's pairs), then the explicit-pair step on its arrays
+    if (int rc = stage_self(h, q, obs, ro, R, stream, staged)) return rc;
+    obs = &staged;
+  }
   const bool ragged_lists = obs && obs->mode == RMP2_OBS_RAGGED_SPHERES;
   if (obs && obs->link_capsules && (obs->mode == RMP2_OBS_SHARED_SPHERES || ragged_lists) && !h->has_point && ro.n_iters == 1 &&
       ro.substeps == 0 && obs->n_spheres > 0 && obs->spheres && !h->distance_leaves.empty() &&
@@ -2405,6 +2753,10 @@ int rmp2_exchange_step(rmp2_exchange* x, rmp2_handle* h, const float* q, const f
                        int32_t goal_stride, const float* next_local, int32_t next_local_is_ready, const rmp2_outputs* out,
                        int32_t R, void* stream, const float** table_out) {
   if (!x || !h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (h->self_n_pairs > 0) {
+    x->error = "self collision: not in rmp2_exchange_step (the exchange's step is one launch on the gathered table)";
+    return fail(h, RMP2_ERR_UNSUPPORTED, x->error);
+  }
   if (x->n_pending < 1) return x->error = "no gathered table outstanding: rmp2_exchange_start first", RMP2_ERR_INVALID_ARGUMENT;
   const int b = x->pending[0];
   for (int i = 1; i < x->n_pending; ++i) x->pending[i - 1] = x->pending[i];
@@ -2465,6 +2817,9 @@ int rmp2_step_pair(rmp2_handle* ha, const float* qa, const float* qda, const flo
                    const float* qdb, const float* goalb, int32_t gsb, const rmp2_obstacles* obsb, const rmp2_outputs* outb,
                    int32_t Rb, void* stream) {
   if (!ha || !hb) return RMP2_ERR_INVALID_ARGUMENT;
+  for (rmp2_handle* hx : {ha, hb})
+    if (hx->self_n_pairs > 0)
+      return fail(hx, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_step_pair (step the two handles with rmp2_step)");
   const RolloutArgs ro{1, 0, 0.f, nullptr, nullptr, 0};
   if (Ra > 0 && Rb > 0 && ha->device == hb->device && !ha->step_fence && !hb->step_fence) {
     ObsArgs oa_, ob_;
@@ -2484,6 +2839,8 @@ int rmp2_rollout(rmp2_handle* h, float* q, float* qd, const float* goal, int32_t
                  const rmp2_obstacles* obs, const rmp2_rollout_cfg* cfg, const rmp2_outputs* out, int32_t R,
                  void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (h->self_n_pairs > 0)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
   if (!cfg || cfg->n_control_steps < 1 || cfg->substeps < 0 || !(cfg->dt >= 0.f))
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, "rollout: need n_control_steps >= 1, substeps >= 0, dt >= 0");
   if (obs && obs->mode == RMP2_OBS_EXPLICIT_PAIRS)
@@ -2585,6 +2942,91 @@ int rmp2_closest_points_links(rmp2_handle* h, const float* q, const rmp2_obstacl
   }
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
+}
+
+int rmp2_set_self_collision(rmp2_handle* h, int32_t n_pairs, const int32_t* pairs, const float* capsules) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (n_pairs < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "n_pairs < 0");
+  if (n_pairs == 0 || !pairs) {   // off: the handle steps as one on which this was never called
+    h->self_n_pairs = 0;
+    h->self_counts.clear();
+    return RMP2_OK;
+  }
+  if (n_pairs > RMP2_MAX_SELF_PAIRS)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self collision: at most " + std::to_string(RMP2_MAX_SELF_PAIRS) + " pairs, got " +
+                                                  std::to_string(n_pairs));
+  if (!capsules) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self collision: capsules [n_frames + 1][8] are required");
+  const int F = h->n_frames, L = (int)h->pair_leaves.size();
+  SelfProg sp;
+  std::memset(&sp, 0, sizeof(sp));
+  for (int l = 0; l < RMP2_MAX_LEAVES; ++l) sp.ord_of_leaf[l] = sp.dord[l] = -1;
+  for (int f = 0; f < RMP2_MAX_FRAMES; ++f) sp.b_slot_of_frame[f] = -1;
+  sp.base_slot = -1;
+  sp.n_leaves = L;
+  sp.n_dist = (int)h->distance_leaves.size();
+  for (int o = 0, nd = 0; o < L; ++o) {
+    sp.ord_of_leaf[h->pair_leaves[o]] = o;
+    sp.dord[o] = h->pair_leaf_point[o] ? -1 : nd++;
+  }
+  std::vector<std::vector<int>> by_leaf(L);   // B frames per ordinal, in the order given
+  for (int k = 0; k < n_pairs; ++k) {
+    const int leaf = pairs[2 * k], b = pairs[2 * k + 1];
+    const int o = (leaf >= 0 && leaf < h->n_leaves) ? sp.ord_of_leaf[leaf] : -1;
+    if (o < 0)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": leaf " + std::to_string(leaf) +
+                                                    " is not a distance or attached-point leaf");
+    if (b < -1 || b >= F)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B " + std::to_string(b) + " out of range");
+    if (b == h->pair_leaf_frame[o])
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B is the leaf's own frame");
+    by_leaf[o].push_back(b);
+  }
+  for (int f = 0; f <= F; ++f)
+    for (int c = 0; c < 8; ++c)
+      if (!std::isfinite(capsules[8 * f + c]) || (c == 3 && capsules[8 * f + c] < 0.f))
+        return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self collision: capsule " + std::to_string(f) + " is not finite or has a negative radius");
+  std::vector<int> counts(L);
+  int j = 0;
+  for (int o = 0; o < L; ++o) {
+    sp.self_begin[o] = j;
+    counts[o] = (int)by_leaf[o].size();
+    const float* lc = capsules + 8 * h->pair_leaf_frame[o];
+    for (int c = 0; c < 8; ++c) sp.leaf_cap[o][c] = lc[c];
+    for (int b : by_leaf[o]) {
+      int& slot = b < 0 ? sp.base_slot : sp.b_slot_of_frame[b];
+      if (slot < 0) {
+        slot = sp.n_b++;
+        const float* bc = capsules + 8 * (b < 0 ? F : b);
+        for (int c = 0; c < 8; ++c) sp.b_cap[slot][c] = bc[c];
+      }
+      sp.pair_b[j++] = slot;
+    }
+  }
+  sp.self_begin[L] = j;
+  sp.n_pairs = j;
+  // the stage's LDS: kClosestRobots robots' records, obstacle segments included
+  const size_t lds = sizeof(float4) * kClosestRobots * (size_t)self_lds_records(sp.n_dist, L, sp.n_b);
+  if (lds > 64 * 1024)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: the stage's records need " + std::to_string(lds) + " bytes of LDS (> 64 KiB)");
+  if (int rc = use_device(h)) return rc;
+  if (!h->d_self) HIP_TRY(h, hipMalloc(&h->d_self, sizeof(SelfProg)));
+  HIP_TRY(h, hipMemcpy(h->d_self, &sp, sizeof(SelfProg), hipMemcpyHostToDevice));   // (synchronous: no launch still reads the old list)
+  h->self_n_b = sp.n_b;
+  h->self_counts = counts;
+  h->self_n_pairs = n_pairs;
+  return RMP2_OK;
+}
+
+int rmp2_self_pairs(rmp2_handle* h, const float* q, float* p_link, float* p_obs, float* dist, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (h->self_n_pairs == 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self collision is off: rmp2_set_self_collision first");
+  if (!q || !p_link || !p_obs || R < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "bad argument");
+  bool point_pairs = false;
+  for (size_t o = 0; o < h->pair_leaves.size(); ++o) point_pairs = point_pairs || (h->pair_leaf_point[o] && h->self_counts[o] > 0);
+  if (point_pairs && !dist) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "attached-point leaves have self pairs: dist is required");
+  if (R == 0) return RMP2_OK;
+  if (int rc = use_device(h)) return rc;
+  return launch_self_stage(h, q, nullptr, p_link, p_obs, dist, h->self_n_pairs, R, (hipStream_t)stream);
 }
 
 static int differentiate_impl(rmp2_handle* h, const float* q, const float* qd, int32_t frame, float* x, float* xd, float* J,

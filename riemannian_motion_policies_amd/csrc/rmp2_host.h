@@ -63,6 +63,16 @@ struct rmp2_handle {
   size_t pairs_floats = 0;     // (floats per array)
   double* d_system = nullptr;  // [robots][n_dof * (n_dof + 1)] combined metric and force between the quad step and rmp2_pinv_kernel
   size_t system_robots = 0;
+  // self collision (rmp2_set_self_collision): off while self_n_pairs == 0
+  int self_n_pairs = 0;
+  int self_n_b = 0;                     // B slots of the list
+  std::vector<int> pair_leaves;         // descriptor indices of the FK_DISTANCE / FK_POINT leaves, descriptor order (the ordinals)
+  std::vector<int> pair_leaf_frame;     // their frames
+  std::vector<char> pair_leaf_point;    // 1: FK_POINT
+  std::vector<int> self_counts;         // S_l per ordinal
+  void* d_self = nullptr;               // SelfProg (rmp2_hip.hip)
+  float* d_self_buf = nullptr;          // p_link | p_obs | dist of the stage when a step runs as self stage + explicit-pair step
+  size_t self_buf_floats = 0;
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
   mutable const char* last_kernel = "none";  // mapping the last control step / rollout was launched with (rmp2_last_kernel)
   std::string error;

@@ -122,16 +122,18 @@ class Datamanager:
             T = T_all[self.fkine.table.frame_index(frame)]
             st["relative_position"].assign((p_link - T[:3, 3][None, :]) @ T[:3, :3])
 
-    def update_device(self, core, q, primitives, link_capsules=None, primitive=None):
+    def update_device(self, core, q, primitives, link_capsules=None, primitive=None, self_collision=False):
         """The same five fields, filled on the device for a whole fleet without PyBullet and without a host hop: `core` is the
         RmpCore whose distance leaves read this manager's holders; its closest-point stage (rmp2_closest_points_links) writes
         pos_on_link / pos_on_obstacle for every (robot, leaf, primitive) pair, and distance, normal_vec and relative_position
         follow from them (simulation.py:462-484 reports the same tuple; data_management.py:33-53 the relative position).
         q: [R, n] tensor on the core's device; primitives: [K,4] spheres, [K,8] capsules or -- primitive="cylinder" -- [K,8] finite
         cylinders (centre, radius, unit axis, half height: the reference's own obstacles, simulation.py:245-261); link_capsules:
-        urdf.link_capsules(...) rows in the order of the core's distance leaves, or None for the frame origins as control points."""
+        urdf.link_capsules(...) rows in the order of the core's distance leaves, or None for the frame origins as control points.
+        self_collision=True: each frame's fields hold its K obstacle pairs followed by its self pairs (RmpCore.update_distances)."""
         import torch
-        pairs = core.update_distances(q, primitives, link_capsules=link_capsules, primitive=primitive)   # (lazy: nothing has run yet)
+        pairs = core.update_distances(q, primitives, link_capsules=link_capsules, primitive=primitive,
+                                      self_collision=self_collision)   # (lazy: nothing has run yet)
         src = pairs.source
         eng, single = src.eng, src.single
         frames = pairs.frames
@@ -151,14 +153,20 @@ class Datamanager:
                 memo["nvec"] = diff / dist.clamp_min(1e-12).unsqueeze(-1)
                 idx = torch.as_tensor([table.frame_index(f) for f in frames], device=eng.device)
                 Tf = T.index_select(1, idx)                                        # [R, L, 4, 4]
-                memo["rel"] = torch.einsum("rlbk,rlkj->rlbj", pl_all.view(-1, L, K, 3) - Tf[:, :, None, :3, 3], Tf[:, :, :3, :3])
+                if src.self_counts is None:
+                    rel = torch.einsum("rlbk,rlkj->rlbj", pl_all.view(-1, L, K, 3) - Tf[:, :, None, :3, 3], Tf[:, :, :3, :3])
+                    memo["rel"] = [rel[:, i] for i in range(L)]
+                else:   # (per-frame pair counts differ: K obstacle pairs plus the frame's self pairs)
+                    memo["rel"] = [torch.einsum("rbk,rkj->rbj", pl_all[:, off[i]:off[i + 1]] - Tf[:, i, None, :3, 3], Tf[:, i, :3, :3])
+                                   for i in range(L)]
             return memo
+        off = src.offsets
         for i, frame in enumerate(frames):
             st = self.state[frame]
             # (the same holders, already marked, when the core's leaves were built on this manager's state)
             st["pos_on_link_in_base_frame"].assign_lazy(lambda i=i: src.view(i, 0), owner=src)
             st["pos_on_obstacle_in_base_frame"].assign_lazy(lambda i=i: src.view(i, 1), owner=src)
-            sl = slice(i * K, (i + 1) * K)
+            sl = slice(off[i], off[i + 1])
             st["distance"].assign_lazy(lambda sl=sl: derived()["dist"][0, sl] if single else derived()["dist"][:, sl])
             st["normal_vec"].assign_lazy(lambda sl=sl: derived()["nvec"][0, sl] if single else derived()["nvec"][:, sl])
-            st["relative_position"].assign_lazy(lambda i=i: derived()["rel"][0, i] if single else derived()["rel"][:, i])
+            st["relative_position"].assign_lazy(lambda i=i: derived()["rel"][i][0] if single else derived()["rel"][i])

@@ -49,6 +49,7 @@ class Engine:
         self._fence_attached = False  # a bound launch attached a completion fence to the handle (bind(done_fence=))
         _native.check(self._lib.rmp2_create(C.byref(desc), self.device.index or 0, C.byref(self._h)))
         self._dist_leaves = D.distance_leaf_indices(desc)
+        self._self_counts = None   # self pairs per pair leaf (set_self_collision), None = off
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -174,7 +175,7 @@ class Engine:
             else:
                 raise ValueError(f"goal must be [{self.desc.goal_floats}] or [R, {self.desc.goal_floats}]")
             goal_ptr = goal.data_ptr()
-        if self._dist_leaves and (obstacles is None or obstacles.mode == D.OBS_NONE):
+        if self._dist_leaves and (obstacles is None or obstacles.mode == D.OBS_NONE) and self._self_counts is None:
             raise ValueError("this RMP set has distance leaves: pass obstacles=engine.obstacles(...)")
         if out is None:
             out = torch.empty((R, self.n_dof), dtype=torch.float32, device=self.device)
@@ -343,6 +344,55 @@ class Engine:
         _native.check(self._lib.rmp2_closest_points_links(self._h, q.data_ptr(), C.byref(table), lc_ptr, p_link.data_ptr(),
                                                           p_obs.data_ptr(), R, s), self._h)
         return p_link, p_obs
+
+    def set_self_collision(self, pairs, capsules) -> None:
+        """Self collision (include/rmp2.h rmp2_set_self_collision): `pairs` = [(leaf ordinal, frame B or -1)] as
+        urdf.self_collision_pairs returns them (ordinal i = the i-th distance / attached-point leaf in leaf order), `capsules`
+        [n_frames + 1, 8] = urdf.self_collision_capsules.  Every later step forms the self pairs on the device and appends them
+        to each leaf's obstacle pairs (obstacle input NONE or a shared sphere / capsule table).  Empty `pairs` turns it off."""
+        pairs = [(int(a), int(b)) for a, b in (pairs or [])]
+        if not pairs:
+            if self._self_counts is not None:
+                _native.check(self._lib.rmp2_set_self_collision(self._h, 0, None, None), self._h)
+            self._self_counts, self._self_key = None, None
+            return
+        dl = self._dist_leaves
+        if any(not 0 <= a < len(dl) for a, _ in pairs):
+            raise ValueError(f"leaf ordinals must lie in [0, {len(dl)})")
+        caps = np.ascontiguousarray(capsules, dtype=np.float32)
+        if caps.shape != (self.n_frames + 1, 8):
+            raise ValueError(f"capsules must be [{self.n_frames + 1}, 8] (one per frame, then the base link)")
+        key = (tuple(pairs), caps.tobytes())
+        if self._self_counts is not None and getattr(self, "_self_key", None) == key:
+            return   # (the same list: nothing to upload)
+        arr = np.ascontiguousarray([(dl[a], b) for a, b in pairs], dtype=np.int32)
+        _native.check(self._lib.rmp2_set_self_collision(self._h, len(pairs), arr.ctypes.data, caps.ctypes.data), self._h)
+        counts = [0] * len(dl)
+        for a, _ in pairs:
+            counts[a] += 1
+        # (the library keeps each leaf's pairs in the order given, leaves in leaf order)
+        self._self_counts, self._self_key = counts, key
+
+    @property
+    def self_counts(self):
+        """Self pairs per distance / attached-point leaf (leaf order), or None when self collision is off."""
+        return None if self._self_counts is None else list(self._self_counts)
+
+    def self_pairs(self, q: torch.Tensor):
+        """The self-pair stage on its own (rmp2_self_pairs): (p_link, p_obs, dist) [R, S, 3], [R, S, 3], [R, S]; leaf ordinal
+        i's pairs at [S_0 + ... + S_{i-1}, + S_i).  Distance leaves: the nearest points of the two capsule surfaces (dist =
+        their distance); attached-point leaves: relative_position in the joint frame, normal_vec and distance."""
+        if self._self_counts is None:
+            raise ValueError("self collision is off: set_self_collision first")
+        q = _f32(q, self.device)
+        R, S = q.shape[0], sum(self._self_counts)
+        p_link = torch.empty((R, S, 3), dtype=torch.float32, device=self.device)
+        p_obs = torch.empty_like(p_link)
+        dist = torch.empty((R, S), dtype=torch.float32, device=self.device)
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        _native.check(self._lib.rmp2_self_pairs(self._h, q.data_ptr(), p_link.data_ptr(), p_obs.data_ptr(), dist.data_ptr(), R, s),
+                      self._h)
+        return p_link, p_obs, dist
 
     def differentiate(self, q: torch.Tensor, qd: torch.Tensor, frame: int):
         q, qd = _f32(q, self.device), _f32(qd, self.device)

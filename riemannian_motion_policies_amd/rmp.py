@@ -55,8 +55,9 @@ class _StageSource:
     """One call of RmpCore.update_distances: the inputs of the closest-point stage (snapshots: the caller may advance q or move
     the obstacles in place afterwards) and, once somebody asks for them, its output arrays."""
 
-    def __init__(self, core, eng, q, single, prim, lc, n_leaves, primitive=None):
+    def __init__(self, core, eng, q, single, prim, lc, n_leaves, primitive=None, self_counts=None):
         self.core, self.eng, self.single, self.n_leaves = core, eng, single, n_leaves
+        self.self_counts = self_counts    # self pairs per leaf (update_distances(self_collision=True)), None = off
         self.primitive = primitive    # None (by record size) | "cylinder"
         # "the q the stage was given, unmodified": the tensor OBJECT (holding it pins its storage: the allocator cannot hand the
         # address to a fresh tensor that would then pass for it) and its version counter (inference-mode tensors have none:
@@ -70,6 +71,9 @@ class _StageSource:
         self.prim = prim.clone()
         self.lc = None if lc is None else lc.clone()
         self.K = int(prim.shape[0])
+        counts = [self.K + (0 if self_counts is None else c) for c in (self_counts or [0] * n_leaves)]
+        self.counts = counts                                   # pairs per leaf: K obstacle pairs, then its self pairs
+        self.offsets = [sum(counts[:i]) for i in range(n_leaves + 1)]
         self._arrays = None
         self._zeros = None
         self.fusable = True    # (cleared when the engine refuses the fused form: its limits are the library's to state)
@@ -93,12 +97,18 @@ class _StageSource:
         if self._arrays is None:
             table = self.eng.obstacles(spheres=self.prim, primitive=self.primitive)
             pl, po = self.eng.closest_points(self.q, table, link_capsules=self.lc)
+            if self.self_counts is not None:   # each leaf's range: its K obstacle pairs, then its self pairs (rmp2_step's layout)
+                self.eng.set_self_collision(*self.core._self_collision_list(self.eng))
+                spl, spo, _ = self.eng.self_pairs(self.q)
+                K, so = self.K, [sum(self.self_counts[:i]) for i in range(self.n_leaves + 1)]
+                pl = torch.cat([t for i in range(self.n_leaves) for t in (pl[:, i * K:(i + 1) * K], spl[:, so[i]:so[i + 1]])], 1)
+                po = torch.cat([t for i in range(self.n_leaves) for t in (po[:, i * K:(i + 1) * K], spo[:, so[i]:so[i + 1]])], 1)
             self._arrays = (pl, po)
-            self.core._pairs_cache = (pl, po, [self.K] * self.n_leaves)
+            self.core._pairs_cache = (pl, po, list(self.counts))
         return self._arrays
 
     def view(self, i, which):
-        a = self.arrays()[which][:, i * self.K:(i + 1) * self.K]
+        a = self.arrays()[which][:, self.offsets[i]:self.offsets[i + 1]]
         return a[0] if self.single else a
 
 
@@ -191,6 +201,7 @@ class RmpCore:
         if table.n_dof != n_dof:
             raise ValueError(f"q has {n_dof} entries, the robot has {table.n_dof} dof")
         self._table = table
+        self._fkine = fks[0] if fks else None
         specs = [rmp.leaf_spec(lambda fk: table.frame_index(fk.frame)) for rmp in self.rmps.values()]
         sig = (id(table), self.solve, tuple(s.signature() for s in specs))
         if sig != self._signature:
@@ -213,7 +224,19 @@ class RmpCore:
         _compile: every entry point compiles first)."""
         return self._pairs
 
-    def update_distances(self, q, primitives, link_capsules=None, primitive=None):
+    def _self_collision_list(self, eng):
+        """(pairs, capsules) of the reference's self-avoidance rule (urdf.self_collision_pairs) over this core's pair leaves."""
+        from . import urdf as U
+        if self._fkine is None:
+            raise ValueError("self collision needs FK task maps (a URDF robot)")
+        frames = [eng.desc.leaves[i].frame for i in eng._dist_leaves]
+        key = (id(self._table), tuple(frames))
+        if getattr(self, "_self_key", None) != key:
+            self._self_list = (U.self_collision_pairs(self._table, frames), U.self_collision_capsules(self._fkine.filepath, self._table))
+            self._self_key = key
+        return self._self_list
+
+    def update_distances(self, q, primitives, link_capsules=None, primitive=None, self_collision=False):
         """The closest-point preprocessing stage on the device (simulation.py:462-484 calculate_distances followed by
         data_management.py:16-31 update): for every TaskmapJointFrame4x4ToDistance leaf and every obstacle primitive
         ([K,4] spheres or [K,8] capsules) the nearest points of the link (its capsule from `link_capsules`, rows in leaf order;
@@ -224,7 +247,11 @@ class RmpCore:
         Returns a mapping {frame name: (p_link, p_obs)} (reading an entry runs the stage); .frames lists the names.
         ("Unmodified" is torch's version counter of q: in-place torch operations and Engine.rollout bump it; a write through
         the raw pointer by foreign code does not -- call update_distances again after one, as the reference's loop does every
-        step.)"""
+        step.)
+        self_collision=True: the reference's self-avoidance pairs as well (simulation.py:411-441; urdf.self_collision_pairs over
+        the core's distance leaves, the base link included): each leaf's holders then hold its K obstacle pairs followed by its
+        self pairs, the other links being obstacles of the step (include/rmp2.h rmp2_set_self_collision).  `primitives` may
+        have zero rows."""
         single = q.dim() == 1 if isinstance(q, torch.Tensor) else np.ndim(q) == 1
         eng = self.engine_for(q)
         qt = as_tensor(q, eng.device)
@@ -239,7 +266,10 @@ class RmpCore:
             raise NotImplementedError("update_distances: attached-point leaves (TaskmapRelative4x4) carry their own pair data")
         prim = as_tensor(primitives, eng.device)
         lc = None if link_capsules is None else as_tensor(link_capsules, eng.device)
-        src = _StageSource(self, eng, qt, single, prim, lc, len(leaves), primitive=primitive)
+        if self_collision:
+            eng.set_self_collision(*self._self_collision_list(eng))
+        src = _StageSource(self, eng, qt, single, prim, lc, len(leaves), primitive=primitive,
+                           self_counts=eng.self_counts if self_collision else None)
         self._stage = src
         names = self._table.frame_names
         frames = []
@@ -266,6 +296,12 @@ class RmpCore:
                 h = getattr(last, attr, None)
                 if not (isinstance(h, ArrayVar) and h.owner is src):
                     return None
+        if src.self_counts is not None:   # the step forms the self pairs itself: the engine carries the list
+            eng.set_self_collision(*self._self_collision_list(eng))
+            if src.K == 0:
+                return eng.obstacles()
+        else:
+            eng.set_self_collision([], None)
         return eng.obstacles(spheres=src.prim, link_capsules=src.link_capsules_or_origins(), primitive=src.primitive)
 
     def _evaluate_device(self, q, qd, spheres, link_capsules=None):
@@ -285,6 +321,7 @@ class RmpCore:
         pair_rmps = self._pair_leaves()
         if pair_rmps:
             if all(isinstance(last, TaskmapSphereDistance) for _, _, last in pair_rmps):
+                eng.set_self_collision([], None)
                 sp = spheres if spheres is not None else self.spheres
                 if sp is None:
                     raise ValueError("TaskmapSphereDistance leaves need evaluate(..., spheres=[K,4])")
@@ -323,6 +360,7 @@ class RmpCore:
                 p_link, p_obs = whole if whole is not None else (torch.cat(pl, dim=1), torch.cat(po, dim=1))
                 obstacles = eng.obstacles(p_link=p_link, p_obs=p_obs, dist=torch.cat(dd, dim=1) if has_point else None,
                                           pair_counts=counts)
+                eng.set_self_collision([], None)   # (explicit arrays: the self pairs, if any, are in them already)
             else:
                 raise NotImplementedError("mixing explicit-pair and sphere distance task maps in one core")
         out = eng.step(q2, qd2, goal=goal, obstacles=obstacles)
@@ -370,6 +408,7 @@ class RmpCore:
         pair_rmps = self._pair_leaves()
         if pair_rmps:
             if all(isinstance(last, TaskmapSphereDistance) for _, _, last in pair_rmps):
+                eng.set_self_collision([], None)
                 sp = spheres if spheres is not None else self.spheres
                 if sp is None:
                     raise ValueError("TaskmapSphereDistance leaves need evaluate(..., spheres=[K,4])")
@@ -402,6 +441,7 @@ class RmpCore:
                     goal, k = dev_parts[2], 3
                 obstacles = eng.obstacles(p_link=dev_parts[k], p_obs=dev_parts[k + 1], dist=dev_parts[k + 2] if has_point else None,
                                           pair_counts=[a.shape[1] for a in pl])
+                eng.set_self_collision([], None)   # (explicit arrays: the self pairs, if any, are in them already)
             else:
                 raise NotImplementedError("mixing explicit-pair and sphere distance task maps in one core")
         out = eng.step(q2, qd2, goal=goal, obstacles=obstacles)

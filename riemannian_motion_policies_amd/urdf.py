@@ -314,40 +314,112 @@ def link_capsules(urdf_filepath: str, table: KinematicTable, frames: Sequence[st
     out = np.zeros((len(frames), 8), dtype=np.float32)
     for i, fr in enumerate(frames):
         f = table.frame_index(fr)
-        link = link_by_name.get(table.link_names[f])
-        col = link.find("collision") if link is not None else None
-        geom = col.find("geometry") if col is not None else None
-        origin = col.find("origin") if col is not None else None
-        xyz = np.asarray(_floats(origin.attrib.get("xyz") if origin is not None else None), dtype=np.float64)
-        Rc = rotation_from_rpy_reference_order(_floats(origin.attrib.get("rpy") if origin is not None else None)).astype(np.float64)
-        prim = None
-        if geom is not None:
-            for tag in ("cylinder", "box", "sphere"):
-                if geom.find(tag) is not None:
-                    prim = (tag, geom.find(tag))
-        if prim is not None and prim[0] == "cylinder":
-            r, L = float(prim[1].attrib["radius"]), float(prim[1].attrib["length"])
-            half = max(L / 2.0 - r, 0.0)
-            axis = Rc @ np.array([0.0, 0.0, 1.0])
-        elif prim is not None and prim[0] == "box":
-            size = np.asarray(_floats(prim[1].attrib["size"]), dtype=np.float64)
-            k = int(np.argmax(size))
-            r = float(np.max(np.delete(size, k))) / 2.0
-            half = max(size[k] / 2.0 - r, 0.0)
-            axis = Rc @ np.eye(3)[k]
-        elif prim is not None and prim[0] == "sphere":
-            r, half, axis = float(prim[1].attrib["radius"]), 0.0, np.array([0.0, 0.0, 1.0])
-        else:
-            cap = fitted.get(table.link_names[f])
-            if cap is not None:   # a capsule fitted to the link's collision mesh (robots/*_link_capsules.json)
-                out[i] = [cap["a"][0], cap["a"][1], cap["a"][2], cap["r"], cap["b"][0], cap["b"][1], cap["b"][2], 0.0]
-                continue
-            kids = [c for c in range(table.n_frames) if table.parent[c] == f]
-            b = table.T_const[kids[0], :3, 3].astype(np.float64) if kids else np.zeros(3)
-            out[i] = [0.0, 0.0, 0.0, default_radius, b[0], b[1], b[2], 0.0]
+        kids = [c for c in range(table.n_frames) if table.parent[c] == f]
+        b = table.T_const[kids[0], :3, 3].astype(np.float64) if kids else np.zeros(3)
+        out[i] = _link_capsule(link_by_name.get(table.link_names[f]), fitted.get(table.link_names[f]), b, default_radius)
+    return out
+
+
+def _link_capsule(link, cap, fallback_b, default_radius: float) -> np.ndarray:
+    """One row of link_capsules: the capsule of `link` (an URDF <link> element or None) in its own coordinates; `cap` is its
+    fitted capsule or None, `fallback_b` the end of the fallback segment from the origin."""
+    col = link.find("collision") if link is not None else None
+    geom = col.find("geometry") if col is not None else None
+    origin = col.find("origin") if col is not None else None
+    xyz = np.asarray(_floats(origin.attrib.get("xyz") if origin is not None else None), dtype=np.float64)
+    Rc = rotation_from_rpy_reference_order(_floats(origin.attrib.get("rpy") if origin is not None else None)).astype(np.float64)
+    prim = None
+    if geom is not None:
+        for tag in ("cylinder", "box", "sphere"):
+            if geom.find(tag) is not None:
+                prim = (tag, geom.find(tag))
+    if prim is not None and prim[0] == "cylinder":
+        r, L = float(prim[1].attrib["radius"]), float(prim[1].attrib["length"])
+        half = max(L / 2.0 - r, 0.0)
+        axis = Rc @ np.array([0.0, 0.0, 1.0])
+    elif prim is not None and prim[0] == "box":
+        size = np.asarray(_floats(prim[1].attrib["size"]), dtype=np.float64)
+        k = int(np.argmax(size))
+        r = float(np.max(np.delete(size, k))) / 2.0
+        half = max(size[k] / 2.0 - r, 0.0)
+        axis = Rc @ np.eye(3)[k]
+    elif prim is not None and prim[0] == "sphere":
+        r, half, axis = float(prim[1].attrib["radius"]), 0.0, np.array([0.0, 0.0, 1.0])
+    else:
+        if cap is not None:   # a capsule fitted to the link's collision mesh (robots/*_link_capsules.json)
+            return np.asarray([cap["a"][0], cap["a"][1], cap["a"][2], cap["r"], cap["b"][0], cap["b"][1], cap["b"][2], 0.0],
+                              dtype=np.float32)
+        b = fallback_b
+        return np.asarray([0.0, 0.0, 0.0, default_radius, b[0], b[1], b[2], 0.0], dtype=np.float32)
+    a, b = xyz - half * axis, xyz + half * axis
+    return np.asarray([a[0], a[1], a[2], r, b[0], b[1], b[2], 0.0], dtype=np.float32)
+
+
+# ---- self collision: link-vs-link pairs (simulation.py:411-441, helper/pybullet_helper.py:46-68) ----------------------------
+
+def _within_neighborhood(table: KinematicTable, link_a: int, link_b: int, n_neighbors: int) -> bool:
+    """check_link_neighborhood: a == b, or one of the two is among the first `n_neighbors` parents of the other (-1 = the base
+    link, which has no parent)."""
+    if link_a == link_b:
+        return True
+    for link, other in ((link_a, link_b), (link_b, link_a)):
+        elem = link
+        for _ in range(n_neighbors):
+            if elem == -1:
+                break
+            parent = int(table.parent[elem])
+            if parent == other:
+                return True
+            elem = parent
+    return False
+
+
+def self_collision_pairs(table: KinematicTable, leaf_frames: Sequence[int], n_neighbors: int = 3,
+                         base_has_collision: bool = True):
+    """The self pairs of a policy set: [(leaf ordinal, frame B or -1)].  `leaf_frames` are the frames of the leaves that take
+    per-pair obstacle data (distance and attached-point maps), in leaf order; ordinal i is leaf_frames[i].  Link A = the leaf's
+    link, link B = any other link with a collision shape, the fixed base (-1) included; a pair is dropped when either link is
+    within `n_neighbors` parent hops of the other (the reference's rule, both directions as its double loop gives them).  B is
+    an obstacle for the step: no derivative flows through it.  Grouped by leaf ordinal, B ascending from -1."""
+    out = []
+    for i, a in enumerate(leaf_frames):
+        a = int(a)
+        if not table.has_collision[a]:
             continue
-        a, b = xyz - half * axis, xyz + half * axis
-        out[i] = [a[0], a[1], a[2], r, b[0], b[1], b[2], 0.0]
+        for b in range(-1, table.n_frames):
+            has_b = base_has_collision if b < 0 else bool(table.has_collision[b])
+            if not has_b or _within_neighborhood(table, a, b, n_neighbors):
+                continue
+            out.append((i, b))
+    return out
+
+
+def base_link_name(urdf_filepath: str, table: KinematicTable) -> str:
+    """Name of the fixed base link: the parent link of the joints attached to the base (parent[f] == -1)."""
+    root = ElementTree.parse(urdf_filepath).getroot()
+    roots = [table.frame_names[f] for f in range(table.n_frames) if table.parent[f] < 0]
+    for j in root.findall("joint"):
+        if j.attrib.get("name") in roots:
+            return j.find("parent").attrib["link"]
+    raise ValueError("no joint attached to the base link")
+
+
+def self_collision_capsules(urdf_filepath: str, table: KinematicTable, default_radius: float = 0.06, fitted="auto") -> np.ndarray:
+    """Capsules [n_frames + 1, 8] = (a, radius, b, 0) for rmp2_set_self_collision: row f is frame f's link in frame coordinates,
+    as link_capsules builds it; the last row is the base link in base coordinates.  Frames without a collision shape get a zero
+    row (self_collision_pairs never pairs them)."""
+    F = table.n_frames
+    out = np.zeros((F + 1, 8), dtype=np.float32)
+    frames = [table.frame_names[f] for f in range(F) if table.has_collision[f]]
+    if frames:
+        rows = link_capsules(urdf_filepath, table, frames, default_radius=default_radius, fitted=fitted)
+        for fr, row in zip(frames, rows):
+            out[table.frame_index(fr)] = row
+    root = ElementTree.parse(urdf_filepath).getroot()
+    link_by_name = {l.attrib["name"]: l for l in root.findall("link")}
+    base = base_link_name(urdf_filepath, table)
+    fitted = fitted_link_capsules(urdf_filepath) if fitted == "auto" else (fitted or {})
+    out[F] = _link_capsule(link_by_name.get(base), fitted.get(base), np.zeros(3), default_radius)
     return out
 
 
