@@ -43,6 +43,8 @@ extern "C" {
 #define RMP2_MAX_LEAVES 48  /* leaf RMPs per set                                          */
 #define RMP2_MAX_PARAMS 12  /* scalar parameters per leaf                                 */
 #define RMP2_MAX_SELF_PAIRS 256 /* self-collision pairs per robot (rmp2_set_self_collision) */
+#define RMP2_MAX_HULL_VERTICES 512 /* vertices per link hull (rmp2_set_link_hulls)          */
+#define RMP2_MAX_HULL_FACES 1024   /* face planes per link hull (rmp2_set_link_hulls)       */
 
 /* ---- error codes --------------------------------------------------------------------- */
 #define RMP2_OK 0
@@ -455,6 +457,49 @@ int rmp2_closest_points_links(rmp2_handle *h, const float *q, const rmp2_obstacl
  * stand in, as for obstacles). */
 int rmp2_set_self_collision(rmp2_handle *h, int32_t n_pairs, const int32_t *pairs, const float *capsules);
 int rmp2_self_pairs(rmp2_handle *h, const float *q, float *p_link, float *p_obs, float *dist, int32_t R, void *stream);
+
+/* ---- convex-hull link geometry: closest points on the collision meshes ----------------------------------------------
+ * The reference's closest points are PyBullet's, between the link's collision MESH -- loaded as its convex hull -- and the
+ * obstacle (simulation.py:462-484 -> data_management.py:22-53).  Capsules contain their mesh, so rmp2_closest_points_links
+ * under-estimates every distance; a handle with link hulls uses the hulls themselves (urdf.link_hulls).
+ *
+ * rmp2_set_link_hulls: copy one convex hull per pair leaf (the FK_DISTANCE and FK_POINT leaves, descriptor order) into the
+ * handle.  Host arrays: hull i has the vertices verts[vert_offset[i] .. vert_offset[i+1])[3] and the face planes
+ * planes[face_offset[i] .. face_offset[i+1])[4] = (n, d), n a unit outward normal, n . x <= d inside, all in the leaf's FRAME
+ * coordinates (vert_offset[0] = face_offset[0] = 0).  At most RMP2_MAX_HULL_VERTICES vertices and RMP2_MAX_HULL_FACES planes per
+ * hull (RMP2_ERR_INVALID_ARGUMENT beyond).  Synchronous.  n_hulls == 0 turns the feature off: the handle then steps bit for bit
+ * as one on which this was never called.
+ *
+ * rmp2_closest_points_hulls: the stand-alone stage for a SHARED_SPHERES table of K sphere or capsule records.  Pair leaf i
+ * owns pairs [i*K, (i+1)*K) (for sets without attached-point leaves the layout of rmp2_closest_points_links).  Per pair, with
+ * c the obstacle's axis point -- the sphere centre, or the point of the capsule's segment the GJK iteration picks -- and r its
+ * radius, in the leaf's frame (the obstacle is brought there as R^T (x - t), so the hull is one constant for the fleet):
+ *   axis outside the hull: h = the hull point nearest the axis, n = (c - h) / |c - h|; p_link = h, p_obs = c - r n (also a sphere
+ *     that overlaps the hull while its centre stays outside);
+ *   axis meets the hull (the centre inside, the segment piercing it, or within 1e-7 m of its surface): the separating face of
+ *     least translation over the hull's planes, t_f = d_f - min over the segment's endpoints of n_f . x, f* = argmin t_f, x* the
+ *     endpoint attaining that min; p_link = x* + t_f* n_f*, p_obs = x* - r n_f*.  Conservative against PyBullet's EPA, which
+ *     also weighs edge-edge directions.
+ *   FK_DISTANCE leaf: p_link, p_obs in the base frame (explicit-pair semantics: d = |p_link - p_obs|, the derivative follows
+ *     the frame origin, quirk Q5).
+ *   FK_POINT leaf: the fields rmp2_device.h link_pair_fields forms from the same two points: p_link = relative_position (the
+ *     hull point in the joint frame), p_obs = normal_vec = sign(g) u (base frame) and dist = |g|, where u is the unit direction
+ *     from c to the hull point (-n_f* when the axis meets the hull) and g the signed gap (|h - c| - r outside, -(t_f* + r) when
+ *     the axis meets the hull).
+ * p_link, p_obs device [R][L*K][3]; dist device [R][L*K] (|g| for every pair; required when the set has attached-point leaves,
+ * else it may be NULL).  The device iteration is bounded: at most 32 GJK steps per pair (fp64), one pass over the planes.
+ *
+ * rmp2_step on a handle with hulls and a SHARED_SPHERES sphere / capsule table: this stage into a buffer of the handle, then the
+ * explicit-pair step (two launches; the same numbers as calling the two).  Memory: 24 P (+ 4 P with attached-point leaves)
+ * bytes per robot, P = L*K; grown on demand, refused with the byte count beyond the free device memory and inside a stream
+ * capture (step once outside it first).  Obstacle input NONE, or an empty table, steps as without hulls.
+ * RMP2_ERR_UNSUPPORTED, with a message naming the combination: rmp2_rollout, rmp2_step_pair, rmp2_exchange_step, RAGGED_SPHERES
+ * lists, CYLINDER tables, caller-supplied EXPLICIT_PAIRS, link_capsules given together with hulls, hulls together with self
+ * collision.  Out of scope: hull-versus-hull self pairs, cylinder obstacles. */
+int rmp2_set_link_hulls(rmp2_handle *h, int32_t n_hulls, const int32_t *vert_offset, const float *verts, const int32_t *face_offset,
+                        const float *planes);
+int rmp2_closest_points_hulls(rmp2_handle *h, const float *q, const rmp2_obstacles *table, float *p_link, float *p_obs, float *dist,
+                              int32_t R, void *stream);
 
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,

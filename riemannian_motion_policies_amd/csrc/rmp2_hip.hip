@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "rmp2_host.h"
+#include "rmp2_hull.h"
 
 using namespace rmp2;
 
@@ -1138,6 +1139,114 @@ rmp2_self_stage_kernel(const DevProgram* __restrict__ prog, const DevProgram* __
   }
 }
 
+// ---- convex-hull link geometry (include/rmp2.h rmp2_set_link_hulls) ---------------------------------------------------------
+// The hulls of a handle, compiled by rmp2_set_link_hulls: pair leaf o (ordinal, descriptor order) owns the vertices
+// [vert_off[o], vert_off[o + 1]) and the planes [face_off[o], face_off[o + 1]) of the handle's two arrays.
+struct HullProg {
+  int32_t n_leaves;                           // pair leaves L
+  int32_t pad_[3];
+  int32_t ord_of_leaf[RMP2_MAX_LEAVES];       // descriptor leaf -> pair-leaf ordinal, -1: not a pair leaf
+  int32_t is_point[RMP2_MAX_LEAVES];          // ordinal -> 1: FK_POINT
+  int32_t vert_off[RMP2_MAX_LEAVES + 1];
+  int32_t face_off[RMP2_MAX_LEAVES + 1];
+};
+
+constexpr int kHullRobots = 16;   // robots per wave (as kClosestRobots)
+
+// The hull stage: one wave per kHullRobots robots, as rmp2_closest_wave_kernel.  Phase 1, a lane per robot: a walk of the step's
+// program puts each pair leaf's frame (rows of R with the origin in .w) into LDS.  Phase 2, a lane per (robot, record) pair of
+// ONE leaf at a time -- the leaf, and with it the hull, is wave-uniform, so its vertices and planes are read through the scalar
+// and vector caches at uniform addresses --: the obstacle's axis is brought into the leaf frame (R^T (x - t)), rmp2_hull.h
+// hull_closest finds the pair (fp64 GJK, at most kHullGjkIters steps; the face rule where the axis meets the hull), and the
+// points go back to the base frame.  Consecutive lanes write consecutive pairs of one robot.
+template <int SLOTS, bool CAPS>
+__global__ void __launch_bounds__(kWave)
+rmp2_hull_stage_kernel(const DevProgram* __restrict__ prog, const HullProg* __restrict__ hp, const float4* __restrict__ hverts,
+                       const float4* __restrict__ hplanes, const float* __restrict__ q, const float4* __restrict__ table, int K,
+                       float* __restrict__ p_link, float* __restrict__ p_obs, float* __restrict__ dist, int R) {
+  extern __shared__ float4 frm[];   // [kHullRobots][L][3]
+  const int L = hp->n_leaves;
+  const int lane = threadIdx.x;
+  const int r0 = blockIdx.x * kHullRobots;
+  const int robot = r0 + lane;
+  if (lane < kHullRobots && robot < R) {
+    const float* my_q = q + (size_t)robot * prog->n_dof;
+    FrameState cur;
+    FrameState slot[SLOTS > 0 ? SLOTS : 1];
+    for (int k = 0; k < prog->n_ops; ++k) {
+      const DevOp& op = prog->ops[k];
+      if (SLOTS > 0 && op.restore >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+          if (op.restore == s) cur = slot[s];
+      }
+      float z[3];
+      visit_frame<false>(cur, op, op.qidx >= 0 ? my_q[op.qidx] : 0.f, 0.f, op.restore == -2, z);
+      if (SLOTS > 0 && op.save >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+          if (op.save == s) slot[s] = cur;
+      }
+      for (int li = 0; li < op.leaf_count; ++li) {
+        const DevLeaf& lf = prog->leaves[prog->fk_leaves[op.leaf_begin + li]];
+        const int o = hp->ord_of_leaf[lf.index];
+        if (o < 0) continue;
+        float4* rec = frm + ((size_t)lane * L + o) * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rec[i] = make_float4(cur.R[3 * i], cur.R[3 * i + 1], cur.R[3 * i + 2], cur.p[i]);
+      }
+    }
+  }
+  __syncthreads();
+  const int n_live = min(kHullRobots, R - r0);
+  const int P = L * K;
+  for (int o = 0; o < L; ++o) {
+    const int v0 = hp->vert_off[o], nv = hp->vert_off[o + 1] - v0;
+    const int f0 = hp->face_off[o], nf = hp->face_off[o + 1] - f0;
+    const bool point = hp->is_point[o] != 0;
+    for (int it = lane; it < n_live * K; it += kWave) {
+      const int r = it / K, k = it - r * K;
+      const float4 ca = CAPS ? table[2 * k] : table[k];
+      const float4 cb = CAPS ? table[2 * k + 1] : ca;
+      const float4* rw = frm + ((size_t)r * L + o) * 3;
+      const float4 w0 = rw[0], w1 = rw[1], w2 = rw[2];
+      const double Rm[9] = {w0.x, w0.y, w0.z, w1.x, w1.y, w1.z, w2.x, w2.y, w2.z};
+      const double t[3] = {w0.w, w1.w, w2.w};
+      const double A[3] = {ca.x - t[0], ca.y - t[1], ca.z - t[2]}, B[3] = {cb.x - t[0], cb.y - t[1], cb.z - t[2]};
+      double a[3], b[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        a[i] = Rm[i] * A[0] + Rm[3 + i] * A[1] + Rm[6 + i] * A[2];
+        b[i] = Rm[i] * B[0] + Rm[3 + i] * B[1] + Rm[6 + i] * B[2];
+      }
+      const double rad = ca.w;
+      const HullHit hh = hull_closest(hverts + v0, nv, hplanes + f0, nf, a, b, rad);
+      const size_t pair = (size_t)(r0 + r) * P + (size_t)o * K + k;
+      if (point) {   // relative_position (frame), normal_vec = sign(g) u (base), distance |g|  (link_pair_fields' conventions)
+        const double sg = hh.gap >= 0.0 ? 1.0 : -1.0;
+        f32x3 nvb;
+        nvb.x = (float)(sg * (Rm[0] * hh.u[0] + Rm[1] * hh.u[1] + Rm[2] * hh.u[2]));
+        nvb.y = (float)(sg * (Rm[3] * hh.u[0] + Rm[4] * hh.u[1] + Rm[5] * hh.u[2]));
+        nvb.z = (float)(sg * (Rm[6] * hh.u[0] + Rm[7] * hh.u[1] + Rm[8] * hh.u[2]));
+        __builtin_nontemporal_store(f32x3{(float)hh.hp[0], (float)hh.hp[1], (float)hh.hp[2]}, reinterpret_cast<f32x3*>(p_link + 3 * pair));
+        __builtin_nontemporal_store(nvb, reinterpret_cast<f32x3*>(p_obs + 3 * pair));
+      } else {       // the two points in the base frame: p_link = h, p_obs = c + r u
+        const double po[3] = {hh.xp[0] + rad * hh.u[0], hh.xp[1] + rad * hh.u[1], hh.xp[2] + rad * hh.u[2]};
+        f32x3 L3, O3;
+        L3.x = (float)(Rm[0] * hh.hp[0] + Rm[1] * hh.hp[1] + Rm[2] * hh.hp[2] + t[0]);
+        L3.y = (float)(Rm[3] * hh.hp[0] + Rm[4] * hh.hp[1] + Rm[5] * hh.hp[2] + t[1]);
+        L3.z = (float)(Rm[6] * hh.hp[0] + Rm[7] * hh.hp[1] + Rm[8] * hh.hp[2] + t[2]);
+        O3.x = (float)(Rm[0] * po[0] + Rm[1] * po[1] + Rm[2] * po[2] + t[0]);
+        O3.y = (float)(Rm[3] * po[0] + Rm[4] * po[1] + Rm[5] * po[2] + t[1]);
+        O3.z = (float)(Rm[6] * po[0] + Rm[7] * po[1] + Rm[8] * po[2] + t[2]);
+        __builtin_nontemporal_store(L3, reinterpret_cast<f32x3*>(p_link + 3 * pair));
+        __builtin_nontemporal_store(O3, reinterpret_cast<f32x3*>(p_obs + 3 * pair));
+      }
+      if (dist) __builtin_nontemporal_store((float)fabs(hh.gap), dist + pair);
+    }
+  }
+}
+
 // x = vec(T_frame), xd = J qd, J = d vec(T)/dq, c = Jdot qd   (kinematics.py:250-270)
 template <int SLOTS>
 __global__ void __launch_bounds__(kWave)
@@ -2194,6 +2303,10 @@ int rmp2_destroy(rmp2_handle* h) {
   if (h->d_pairs) (void)hipFree(h->d_pairs);
   if (h->d_self) (void)hipFree(h->d_self);
   if (h->d_self_buf) (void)hipFree(h->d_self_buf);
+  if (h->d_hull) (void)hipFree(h->d_hull);
+  if (h->d_hull_verts) (void)hipFree(h->d_hull_verts);
+  if (h->d_hull_planes) (void)hipFree(h->d_hull_planes);
+  if (h->d_hull_buf) (void)hipFree(h->d_hull_buf);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
   return RMP2_OK;
@@ -2444,6 +2557,100 @@ static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs,
   return RMP2_OK;
 }
 
+// Launch of rmp2_hull_stage_kernel over a SHARED_SPHERES sphere / capsule table (K > 0): pair leaf o owns pairs [o K, (o + 1) K).
+static int launch_hull_stage(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
+                             int32_t R, hipStream_t s) {
+  const int L = h->hull_n, K = table->n_spheres;
+  const size_t lds_bytes = sizeof(float4) * 3 * (size_t)L * kHullRobots;
+  const int blocks = (R + kHullRobots - 1) / kHullRobots;
+  const HullProg* hp = static_cast<const HullProg*>(h->d_hull);
+  const float4* tab = reinterpret_cast<const float4*>(table->spheres);
+#define RMP2_HULL_STAGE_(SLOTS_, CAPS_)                                                                                      \
+  hipLaunchKernelGGL((rmp2_hull_stage_kernel<SLOTS_, CAPS_>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog, hp,      \
+                     h->d_hull_verts, h->d_hull_planes, q, tab, K, p_link, p_obs, dist, (int)R)
+  const bool caps = table->primitive == RMP2_PRIM_CAPSULE;
+  switch (h->n_slots) {
+    case 0: if (caps) RMP2_HULL_STAGE_(0, true); else RMP2_HULL_STAGE_(0, false); break;
+    case 1: if (caps) RMP2_HULL_STAGE_(1, true); else RMP2_HULL_STAGE_(1, false); break;
+    default: if (caps) RMP2_HULL_STAGE_(2, true); else RMP2_HULL_STAGE_(2, false); break;
+  }
+#undef RMP2_HULL_STAGE_
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
+// The obstacle table of a hull stage (rmp2_closest_points_hulls and the staged step): a SHARED_SPHERES table of sphere or capsule
+// records without link_capsules.
+static int check_hull_table(rmp2_handle* h, const rmp2_obstacles* t) {
+  if (t->mode == RMP2_OBS_EXPLICIT_PAIRS)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls with caller-supplied EXPLICIT_PAIRS: the hulls form the pairs from a table -- "
+                                         "step a handle without hulls on the arrays of rmp2_closest_points_hulls");
+  if (t->mode == RMP2_OBS_RAGGED_SPHERES)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls over RAGGED_SPHERES lists: not supported (shared tables only)");
+  if (t->mode != RMP2_OBS_SHARED_SPHERES) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls need a SHARED_SPHERES table");
+  if (t->n_spheres < 0 || (t->n_spheres > 0 && !t->spheres)) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "sphere table missing");
+  if (t->primitive == RMP2_PRIM_CYLINDER)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls with a CYLINDER table: not supported (sphere or capsule records)");
+  if (t->primitive != RMP2_PRIM_SPHERE && t->primitive != RMP2_PRIM_CAPSULE)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "unknown obstacle primitive");
+  if (t->link_capsules)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link_capsules given together with link hulls: one link geometry per handle (turn the hulls "
+                                         "off with rmp2_set_link_hulls(h, 0, ...) to step on capsules)");
+  return RMP2_OK;
+}
+
+// The staged step of a handle with link hulls (include/rmp2.h): the hull stage into the handle's buffer, described as
+// EXPLICIT_PAIRS in `staged` (*used = true); obstacle input NONE or an empty table: nothing to stage (*used = false).
+static int stage_hulls(rmp2_handle* h, const float* q, const rmp2_obstacles* obs, const RolloutArgs& ro, int32_t R, void* stream,
+                       rmp2_obstacles& staged, bool* used) {
+  *used = false;
+  if (ro.n_iters != 1 || ro.substeps != 0)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
+  if (!obs || obs->mode == RMP2_OBS_NONE) return RMP2_OK;
+  if (int rc = check_hull_table(h, obs)) return rc;
+  if (obs->n_spheres == 0) return RMP2_OK;
+  if (!q) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "q, qd and out->qdd are required");
+  const size_t K = (size_t)obs->n_spheres, L = (size_t)h->hull_n;
+  const size_t P = L * K;
+  if (P > (size_t)INT32_MAX / 4) return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: too many pairs per robot");
+  // buffer: p_link | p_obs [R][P][3] (+ dist [R][P] with attached-point leaves) -- 24 P (+ 4 P) bytes per robot (include/rmp2.h)
+  const size_t arr = (size_t)R * P * 3;
+  const size_t need = 2 * arr + (h->has_point ? (size_t)R * P : 0);
+  hipStream_t s = (hipStream_t)stream;
+  if (need > h->hull_buf_floats) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+      return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls as stage + explicit-pair step: the handle's pair buffer must grow -- step once "
+                                           "outside the capture first");
+    if (int rc = use_device(h)) return rc;
+    if (h->d_hull_buf) HIP_TRY(h, hipFree(h->d_hull_buf));   // (synchronises the device: no launch still reads the old buffer)
+    h->d_hull_buf = nullptr, h->hull_buf_floats = 0;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    if (sizeof(float) * need > free_b)
+      return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: the stage's pair buffer needs " + std::to_string(sizeof(float) * need) +
+                                               " bytes (" + std::to_string(sizeof(float) * need / (size_t)R) + " per robot), " +
+                                               std::to_string(free_b) + " bytes of device memory are free -- step a smaller fleet");
+    HIP_TRY(h, hipMalloc(&h->d_hull_buf, sizeof(float) * need));
+    h->hull_buf_floats = need;
+  }
+  if (int rc = use_device(h)) return rc;
+  float* const pl = h->d_hull_buf;
+  float* const po = pl + arr;
+  float* const dd = h->has_point ? po + arr : nullptr;
+  if (int rc = launch_hull_stage(h, q, obs, pl, po, dd, R, s)) return rc;
+  std::memset(&staged, 0, sizeof(staged));
+  staged.mode = RMP2_OBS_EXPLICIT_PAIRS;
+  staged.n_pairs = (int32_t)P;
+  for (int l = 0, o = 0, acc = 0; l <= RMP2_MAX_LEAVES; ++l) {
+    staged.pair_begin[l] = acc;
+    if (o < (int)h->pair_leaves.size() && h->pair_leaves[o] == l) acc += (int)K, ++o;
+  }
+  staged.p_link = pl, staged.p_obs = po, staged.dist = dd;
+  *used = true;
+  return RMP2_OK;
+}
+
 static int step_impl(rmp2_handle* h, const float* q, const float* qd, const float* goal, int32_t goal_stride,
                      const rmp2_obstacles* obs, const rmp2_outputs* out, const RolloutArgs& ro, int32_t R, void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
@@ -2458,6 +2665,12 @@ static int step_impl(rmp2_handle* h, const float* q, const float* qd, const floa
   // rmp2_gather_list_pairs_kernel lays out one pair per list entry at L = the fleet's longest list slots per leaf -- L is read back
   // from csr_offset, so this form synchronises the stream and is refused inside a stream capture.
   rmp2_obstacles staged;
+  if (h->hull_n > 0) {   // link hulls: the hull stage, then the explicit-pair step on its arrays
+    if (h->self_n_pairs > 0) return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls together with self collision: not supported");
+    bool used = false;
+    if (int rc = stage_hulls(h, q, obs, ro, R, stream, staged, &used)) return rc;
+    if (used) obs = &staged;
+  }
   if (h->self_n_pairs > 0) {   // self collision: the self stage (+ the table's pairs), then the explicit-pair step on its arrays
     if (int rc = stage_self(h, q, obs, ro, R, stream, staged)) return rc;
     obs = &staged;
@@ -2757,6 +2970,10 @@ int rmp2_exchange_step(rmp2_exchange* x, rmp2_handle* h, const float* q, const f
     x->error = "self collision: not in rmp2_exchange_step (the exchange's step is one launch on the gathered table)";
     return fail(h, RMP2_ERR_UNSUPPORTED, x->error);
   }
+  if (h->hull_n > 0) {
+    x->error = "link hulls: not in rmp2_exchange_step (the exchange's step is one launch on the gathered table)";
+    return fail(h, RMP2_ERR_UNSUPPORTED, x->error);
+  }
   if (x->n_pending < 1) return x->error = "no gathered table outstanding: rmp2_exchange_start first", RMP2_ERR_INVALID_ARGUMENT;
   const int b = x->pending[0];
   for (int i = 1; i < x->n_pending; ++i) x->pending[i - 1] = x->pending[i];
@@ -2820,6 +3037,9 @@ int rmp2_step_pair(rmp2_handle* ha, const float* qa, const float* qda, const flo
   for (rmp2_handle* hx : {ha, hb})
     if (hx->self_n_pairs > 0)
       return fail(hx, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_step_pair (step the two handles with rmp2_step)");
+  for (rmp2_handle* hx : {ha, hb})
+    if (hx->hull_n > 0)
+      return fail(hx, RMP2_ERR_UNSUPPORTED, "link hulls: not in rmp2_step_pair (step the two handles with rmp2_step)");
   const RolloutArgs ro{1, 0, 0.f, nullptr, nullptr, 0};
   if (Ra > 0 && Rb > 0 && ha->device == hb->device && !ha->step_fence && !hb->step_fence) {
     ObsArgs oa_, ob_;
@@ -2841,6 +3061,8 @@ int rmp2_rollout(rmp2_handle* h, float* q, float* qd, const float* goal, int32_t
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   if (h->self_n_pairs > 0)
     return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
+  if (h->hull_n > 0)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
   if (!cfg || cfg->n_control_steps < 1 || cfg->substeps < 0 || !(cfg->dt >= 0.f))
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, "rollout: need n_control_steps >= 1, substeps >= 0, dt >= 0");
   if (obs && obs->mode == RMP2_OBS_EXPLICIT_PAIRS)
@@ -2952,6 +3174,8 @@ int rmp2_set_self_collision(rmp2_handle* h, int32_t n_pairs, const int32_t* pair
     h->self_counts.clear();
     return RMP2_OK;
   }
+  if (h->hull_n > 0)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision together with link hulls: not supported (turn the hulls off first)");
   if (n_pairs > RMP2_MAX_SELF_PAIRS)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self collision: at most " + std::to_string(RMP2_MAX_SELF_PAIRS) + " pairs, got " +
                                                   std::to_string(n_pairs));
@@ -3027,6 +3251,87 @@ int rmp2_self_pairs(rmp2_handle* h, const float* q, float* p_link, float* p_obs,
   if (R == 0) return RMP2_OK;
   if (int rc = use_device(h)) return rc;
   return launch_self_stage(h, q, nullptr, p_link, p_obs, dist, h->self_n_pairs, R, (hipStream_t)stream);
+}
+
+int rmp2_set_link_hulls(rmp2_handle* h, int32_t n_hulls, const int32_t* vert_offset, const float* verts, const int32_t* face_offset,
+                        const float* planes) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (n_hulls < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "n_hulls < 0");
+  if (n_hulls == 0) {   // off: the handle steps as one on which this was never called
+    h->hull_n = 0;
+    return RMP2_OK;
+  }
+  if (h->self_n_pairs > 0)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls together with self collision: not supported (turn self collision off first)");
+  const int L = (int)h->pair_leaves.size();
+  if (n_hulls != L)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: one hull per distance / attached-point leaf (" + std::to_string(L) + "), got " +
+                                                  std::to_string(n_hulls));
+  if (!vert_offset || !verts || !face_offset || !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: null array");
+  if (vert_offset[0] != 0 || face_offset[0] != 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: offsets must start at 0");
+  HullProg hp;
+  std::memset(&hp, 0, sizeof(hp));
+  hp.n_leaves = L;
+  for (int l = 0; l < RMP2_MAX_LEAVES; ++l) hp.ord_of_leaf[l] = -1;
+  for (int o = 0; o < L; ++o) {
+    const int nv = vert_offset[o + 1] - vert_offset[o], nf = face_offset[o + 1] - face_offset[o];
+    if (nv < 1 || nf < 1)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hull " + std::to_string(o) + ": needs at least one vertex and one face plane");
+    if (nv > RMP2_MAX_HULL_VERTICES || nf > RMP2_MAX_HULL_FACES)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hull " + std::to_string(o) + ": " + std::to_string(nv) + " vertices / " +
+                                                    std::to_string(nf) + " faces, at most RMP2_MAX_HULL_VERTICES = " +
+                                                    std::to_string(RMP2_MAX_HULL_VERTICES) + " / RMP2_MAX_HULL_FACES = " +
+                                                    std::to_string(RMP2_MAX_HULL_FACES));
+    hp.ord_of_leaf[h->pair_leaves[o]] = o;
+    hp.is_point[o] = h->pair_leaf_point[o];
+    hp.vert_off[o] = vert_offset[o], hp.face_off[o] = face_offset[o];
+  }
+  hp.vert_off[L] = vert_offset[L], hp.face_off[L] = face_offset[L];
+  const size_t NV = (size_t)vert_offset[L], NF = (size_t)face_offset[L];
+  std::vector<float4> hv(NV), hpl(NF);
+  for (size_t i = 0; i < NV; ++i) {
+    hv[i] = make_float4(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2], 0.f);
+    if (!std::isfinite(hv[i].x) || !std::isfinite(hv[i].y) || !std::isfinite(hv[i].z))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: vertex " + std::to_string(i) + " is not finite");
+  }
+  for (size_t i = 0; i < NF; ++i) {
+    hpl[i] = make_float4(planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]);
+    const double n2 = (double)hpl[i].x * hpl[i].x + (double)hpl[i].y * hpl[i].y + (double)hpl[i].z * hpl[i].z;
+    if (!std::isfinite(hpl[i].w) || !(std::fabs(n2 - 1.0) <= 1e-4))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: plane " + std::to_string(i) + " needs a unit normal and a finite offset");
+  }
+  if (int rc = use_device(h)) return rc;
+  if (NV > h->hull_verts_cap) {
+    if (h->d_hull_verts) HIP_TRY(h, hipFree(h->d_hull_verts));
+    h->d_hull_verts = nullptr, h->hull_verts_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->d_hull_verts, sizeof(float4) * NV));
+    h->hull_verts_cap = NV;
+  }
+  if (NF > h->hull_planes_cap) {
+    if (h->d_hull_planes) HIP_TRY(h, hipFree(h->d_hull_planes));
+    h->d_hull_planes = nullptr, h->hull_planes_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->d_hull_planes, sizeof(float4) * NF));
+    h->hull_planes_cap = NF;
+  }
+  if (!h->d_hull) HIP_TRY(h, hipMalloc(&h->d_hull, sizeof(HullProg)));
+  // (synchronous copies: no launch still reads the old hulls)
+  HIP_TRY(h, hipMemcpy(h->d_hull_verts, hv.data(), sizeof(float4) * NV, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->d_hull_planes, hpl.data(), sizeof(float4) * NF, hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->d_hull, &hp, sizeof(HullProg), hipMemcpyHostToDevice));
+  h->hull_n = L;
+  return RMP2_OK;
+}
+
+int rmp2_closest_points_hulls(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
+                              int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (h->hull_n == 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls are off: rmp2_set_link_hulls first");
+  if (!q || !table || !p_link || !p_obs || R < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "bad argument");
+  if (int rc = check_hull_table(h, table)) return rc;
+  if (h->has_point && !dist) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "the set has attached-point leaves: dist is required");
+  if (R == 0 || table->n_spheres == 0) return RMP2_OK;
+  if (int rc = use_device(h)) return rc;
+  return launch_hull_stage(h, q, table, p_link, p_obs, dist, R, (hipStream_t)stream);
 }
 
 static int differentiate_impl(rmp2_handle* h, const float* q, const float* qd, int32_t frame, float* x, float* xd, float* J,

@@ -73,6 +73,14 @@ struct rmp2_handle {
   void* d_self = nullptr;               // SelfProg (rmp2_hip.hip)
   float* d_self_buf = nullptr;          // p_link | p_obs | dist of the stage when a step runs as self stage + explicit-pair step
   size_t self_buf_floats = 0;
+  // convex-hull link geometry (rmp2_set_link_hulls): off while hull_n == 0
+  int hull_n = 0;
+  void* d_hull = nullptr;               // HullProg (rmp2_hip.hip)
+  float4* d_hull_verts = nullptr;       // (x, y, z, -) per vertex, hulls back to back
+  float4* d_hull_planes = nullptr;      // (n, d) per face
+  size_t hull_verts_cap = 0, hull_planes_cap = 0;
+  float* d_hull_buf = nullptr;          // p_link | p_obs | dist of the stage when a step runs as hull stage + explicit-pair step
+  size_t hull_buf_floats = 0;
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
   mutable const char* last_kernel = "none";  // mapping the last control step / rollout was launched with (rmp2_last_kernel)
   std::string error;

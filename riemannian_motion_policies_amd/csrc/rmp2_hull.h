@@ -1,0 +1,279 @@
+// rmp2_hull.h -- nearest points of a convex hull and a point or segment (include/rmp2.h rmp2_set_link_hulls).
+//
+// The reference asks PyBullet for the closest points of a link's collision mesh -- loaded as its convex hull -- and an obstacle
+// (simulation.py:462-484).  Here the hull is a vertex set plus outward face planes in the leaf's frame coordinates, the obstacle's
+// axis (a sphere's centre, a capsule's segment) is brought into those coordinates, and GJK on the Minkowski difference
+// hull - segment finds the nearest pair; an axis that meets the hull takes the separating face of least translation.
+//
+// Everything is fp64 (the vertex and plane data are fp32, exactly representable): the support function is an argmax over the
+// hull's vertices and the stop test compares its value with |v|^2, both of which fp32 rounding would blur at the 1e-5 m the
+// stage promises.  Every loop is bounded: at most kHullGjkIters GJK iterations (a pair that has not converged by then keeps
+// the best simplex found), one pass over the vertices per support call, one pass over the planes for the face rule.
+// Host-compilable (__host__ __device__) so that the same code can be exercised on the CPU.
+#pragma once
+#include <math.h>
+
+namespace rmp2 {
+
+constexpr int kHullGjkIters = 32;
+constexpr double kHullTouch2 = 1e-14;   // |v|^2 below (1e-7 m)^2: the axis touches or meets the hull -> face rule
+
+struct HullHit {
+  double hp[3];   // nearest point of the hull (frame coordinates)
+  double xp[3];   // the axis point c: the sphere centre, or the segment point GJK picks (the meeting endpoint x* under the face rule)
+  double u[3];    // unit direction from c towards the hull point (-n_f* under the face rule)
+  double gap;     // signed surface gap: |hp - c| - r outside, -(t_f* + r) when the axis meets the hull
+  int iters;      // GJK iterations run (diagnostic)
+};
+
+__host__ __device__ inline double hdot(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+// Closest point of conv(W[0..n)) to the origin, GJK's distance subalgorithm: lam = barycentric weights; the simplex is reduced
+// in place to the smallest feature that holds the point.  Returns false when a full tetrahedron contains the origin.
+struct HullSimplex {
+  double W[4][3], H[4][3], S[4][3];
+  int id[4];
+  int n;
+  double lam[4];
+};
+
+__host__ __device__ inline void hs_keep(HullSimplex& s, int k, const int* idx, const double* lam) {
+  double W[4][3], H[4][3], S[4][3];
+  int id[4];
+  for (int i = 0; i < k; ++i)
+    for (int c = 0; c < 3; ++c) W[i][c] = s.W[idx[i]][c], H[i][c] = s.H[idx[i]][c], S[i][c] = s.S[idx[i]][c];
+  for (int i = 0; i < k; ++i) id[i] = s.id[idx[i]];
+  for (int i = 0; i < k; ++i) {
+    for (int c = 0; c < 3; ++c) s.W[i][c] = W[i][c], s.H[i][c] = H[i][c], s.S[i][c] = S[i][c];
+    s.id[i] = id[i];
+    s.lam[i] = lam[i];
+  }
+  s.n = k;
+}
+
+// segment i-j of the simplex: closest point to the origin as (which vertices, weights)
+__host__ __device__ inline double hs_segment(const double A[3], const double B[3], int& k, double lam[2], int sel[2], int ia, int ib) {
+  const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+  const double den = hdot(ab, ab);
+  const double t = den > 0.0 ? -hdot(A, ab) / den : 0.0;
+  if (!(t > 0.0)) {
+    k = 1, sel[0] = ia, lam[0] = 1.0;
+    return hdot(A, A);
+  }
+  if (t >= 1.0) {
+    k = 1, sel[0] = ib, lam[0] = 1.0;
+    return hdot(B, B);
+  }
+  k = 2, sel[0] = ia, sel[1] = ib, lam[0] = 1.0 - t, lam[1] = t;
+  const double p[3] = {A[0] + t * ab[0], A[1] + t * ab[1], A[2] + t * ab[2]};
+  return hdot(p, p);
+}
+
+// triangle (Ericson, Real-Time Collision Detection 5.1.5, with the query point at the origin); a degenerate triangle falls back
+// to the best of its three edges
+__host__ __device__ inline double hs_triangle(const double A[3], const double B[3], const double C[3], int& k, double lam[3], int sel[3],
+                                             int ia, int ib, int ic) {
+  const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, ac[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+  const double ap[3] = {-A[0], -A[1], -A[2]};
+  const double d1 = hdot(ab, ap), d2 = hdot(ac, ap);
+  if (d1 <= 0.0 && d2 <= 0.0) return k = 1, sel[0] = ia, lam[0] = 1.0, hdot(A, A);
+  const double bp[3] = {-B[0], -B[1], -B[2]};
+  const double d3 = hdot(ab, bp), d4 = hdot(ac, bp);
+  if (d3 >= 0.0 && d4 <= d3) return k = 1, sel[0] = ib, lam[0] = 1.0, hdot(B, B);
+  const double vc = d1 * d4 - d3 * d2;
+  if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+    int kk;
+    double l2[2];
+    int s2[2];
+    const double r = hs_segment(A, B, kk, l2, s2, ia, ib);
+    k = kk;
+    for (int i = 0; i < kk; ++i) sel[i] = s2[i], lam[i] = l2[i];
+    return r;
+  }
+  const double cp[3] = {-C[0], -C[1], -C[2]};
+  const double d5 = hdot(ab, cp), d6 = hdot(ac, cp);
+  if (d6 >= 0.0 && d5 <= d6) return k = 1, sel[0] = ic, lam[0] = 1.0, hdot(C, C);
+  const double vb = d5 * d2 - d1 * d6;
+  if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+    int kk;
+    double l2[2];
+    int s2[2];
+    const double r = hs_segment(A, C, kk, l2, s2, ia, ic);
+    k = kk;
+    for (int i = 0; i < kk; ++i) sel[i] = s2[i], lam[i] = l2[i];
+    return r;
+  }
+  const double va = d3 * d6 - d5 * d4;
+  if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
+    int kk;
+    double l2[2];
+    int s2[2];
+    const double r = hs_segment(B, C, kk, l2, s2, ib, ic);
+    k = kk;
+    for (int i = 0; i < kk; ++i) sel[i] = s2[i], lam[i] = l2[i];
+    return r;
+  }
+  const double sum = va + vb + vc;
+  if (!(sum > 0.0)) {   // degenerate (collinear) triangle: the best edge
+    double best = 1e300;
+    const double* P[3] = {A, B, C};
+    const int I[3] = {ia, ib, ic};
+    for (int e = 0; e < 3; ++e) {
+      int kk;
+      double l2[2];
+      int s2[2];
+      const double r = hs_segment(P[e], P[(e + 1) % 3], kk, l2, s2, I[e], I[(e + 1) % 3]);
+      if (r < best) {
+        best = r, k = kk;
+        for (int i = 0; i < kk; ++i) sel[i] = s2[i], lam[i] = l2[i];
+      }
+    }
+    return best;
+  }
+  const double v = vb / sum, w = vc / sum;
+  k = 3, sel[0] = ia, sel[1] = ib, sel[2] = ic, lam[0] = 1.0 - v - w, lam[1] = v, lam[2] = w;
+  const double p[3] = {A[0] + v * ab[0] + w * ac[0], A[1] + v * ab[1] + w * ac[1], A[2] + v * ab[2] + w * ac[2]};
+  return hdot(p, p);
+}
+
+__host__ __device__ inline bool hs_solve(HullSimplex& s) {
+  int k = 1, sel[3] = {0, 0, 0};
+  double lam[3] = {1.0, 0.0, 0.0};
+  if (s.n == 1) {
+    s.lam[0] = 1.0;
+    return true;
+  }
+  if (s.n == 2) {
+    double l2[2];
+    int s2[2];
+    hs_segment(s.W[0], s.W[1], k, l2, s2, 0, 1);
+    for (int i = 0; i < k; ++i) sel[i] = s2[i], lam[i] = l2[i];
+  } else if (s.n == 3) {
+    hs_triangle(s.W[0], s.W[1], s.W[2], k, lam, sel, 0, 1, 2);
+  } else {
+    // tetrahedron: the faces the origin lies outside of (opposite side from the fourth vertex; a flat tetrahedron counts every
+    // face as such) -- none: the origin is inside
+    const int F[4][4] = {{0, 1, 2, 3}, {0, 1, 3, 2}, {0, 2, 3, 1}, {1, 2, 3, 0}};
+    double best = 1e300;
+    bool any = false;
+    for (int f = 0; f < 4; ++f) {
+      const double* A = s.W[F[f][0]];
+      const double* B = s.W[F[f][1]];
+      const double* C = s.W[F[f][2]];
+      const double* D = s.W[F[f][3]];
+      const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, ac[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+      const double nrm[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
+      const double ad[3] = {D[0] - A[0], D[1] - A[1], D[2] - A[2]};
+      const double so = -hdot(nrm, A), sd = hdot(nrm, ad);
+      if (so * sd > 0.0) continue;   // origin on the fourth vertex's side of this face
+      any = true;
+      int kk, ss[3];
+      double ll[3];
+      const double r = hs_triangle(A, B, C, kk, ll, ss, F[f][0], F[f][1], F[f][2]);
+      if (r < best) {
+        best = r, k = kk;
+        for (int i = 0; i < kk; ++i) sel[i] = ss[i], lam[i] = ll[i];
+      }
+    }
+    if (!any) return false;
+  }
+  hs_keep(s, k, sel, lam);
+  return true;
+}
+
+// The nearest points of the convex hull (V: nv vertices as float4 .xyz; Pl: nf planes (n, d), n . x <= d inside) and the
+// segment a-b (a == b: a point) of radius r, all in the hull's coordinates.
+__host__ __device__ inline HullHit hull_closest(const float4* __restrict__ V, int nv, const float4* __restrict__ Pl, int nf,
+                                                const double a[3], const double b[3], double r) {
+  HullHit out;
+  HullSimplex s;
+  const bool seg = a[0] != b[0] || a[1] != b[1] || a[2] != b[2];
+  {
+    const float4 v0 = V[0];
+    const double h0[3] = {(double)v0.x, (double)v0.y, (double)v0.z};
+    for (int c = 0; c < 3; ++c) s.H[0][c] = h0[c], s.S[0][c] = a[c], s.W[0][c] = h0[c] - a[c];
+    s.id[0] = 0;
+    s.n = 1;
+    s.lam[0] = 1.0;
+  }
+  double v[3] = {s.W[0][0], s.W[0][1], s.W[0][2]};
+  double vv = hdot(v, v);
+  bool touch = false;
+  int it = 0;
+  for (; it < kHullGjkIters; ++it) {
+    if (vv <= kHullTouch2) {
+      touch = true;
+      break;
+    }
+    // support of hull - segment in -v: the hull vertex maximising -v . x, the endpoint maximising v . x
+    int jb = 0;
+    double best = -1e300;
+    for (int j = 0; j < nv; ++j) {
+      const float4 q = V[j];
+      const double d = -(v[0] * (double)q.x + v[1] * (double)q.y + v[2] * (double)q.z);
+      if (d > best) best = d, jb = j;
+    }
+    const bool use_b = seg && hdot(v, b) > hdot(v, a);
+    const double* e = use_b ? b : a;
+    const int idw = 2 * jb + (use_b ? 1 : 0);
+    bool dup = false;
+    for (int i = 0; i < s.n; ++i) dup = dup || s.id[i] == idw;
+    if (dup) break;
+    const float4 q = V[jb];
+    const double hw[3] = {(double)q.x, (double)q.y, (double)q.z};
+    const double w[3] = {hw[0] - e[0], hw[1] - e[1], hw[2] - e[2]};
+    if (vv - hdot(v, w) <= 1e-13 * vv) break;   // no vertex brings the difference measurably closer to the origin
+    HullSimplex prev = s;
+    for (int c = 0; c < 3; ++c) s.H[s.n][c] = hw[c], s.S[s.n][c] = e[c], s.W[s.n][c] = w[c];
+    s.id[s.n] = idw;
+    ++s.n;
+    if (!hs_solve(s)) {   // a tetrahedron of the difference contains the origin: the axis meets the hull
+      touch = true;
+      break;
+    }
+    double nvv[3] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < s.n; ++i)
+      for (int c = 0; c < 3; ++c) nvv[c] += s.lam[i] * s.W[i][c];
+    const double nv2 = hdot(nvv, nvv);
+    if (!(nv2 < vv)) {   // no progress (rounding): keep the previous simplex
+      s = prev;
+      break;
+    }
+    for (int c = 0; c < 3; ++c) v[c] = nvv[c];
+    vv = nv2;
+  }
+  out.iters = it;
+  if (!touch) {
+    double hp[3] = {0.0, 0.0, 0.0}, xp[3] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < s.n; ++i)
+      for (int c = 0; c < 3; ++c) hp[c] += s.lam[i] * s.H[i][c], xp[c] += s.lam[i] * s.S[i][c];
+    const double d[3] = {hp[0] - xp[0], hp[1] - xp[1], hp[2] - xp[2]};
+    const double dn = sqrt(hdot(d, d));
+    if (dn * dn > kHullTouch2) {
+      for (int c = 0; c < 3; ++c) out.hp[c] = hp[c], out.xp[c] = xp[c], out.u[c] = d[c] / dn;
+      out.gap = dn - r;
+      return out;
+    }
+  }
+  // the axis meets (or touches) the hull: the face of least translation t_f = d_f - min over the endpoints of n_f . x
+  int fb = 0;
+  double tb = 1e300, mb = 0.0;
+  bool at_b = false;
+  for (int f = 0; f < nf; ++f) {
+    const float4 p = Pl[f];
+    const double n[3] = {(double)p.x, (double)p.y, (double)p.z};
+    const double ma = hdot(n, a), mbb = hdot(n, b);
+    const double m = mbb < ma ? mbb : ma;
+    const double t = (double)p.w - m;
+    if (t < tb) tb = t, fb = f, mb = m, at_b = mbb < ma;
+  }
+  (void)mb;
+  const float4 p = Pl[fb];
+  const double n[3] = {(double)p.x, (double)p.y, (double)p.z};
+  const double* x = at_b ? b : a;
+  for (int c = 0; c < 3; ++c) out.xp[c] = x[c], out.hp[c] = x[c] + tb * n[c], out.u[c] = -n[c];
+  out.gap = -(tb + r);
+  return out;
+}
+
+}  // namespace rmp2

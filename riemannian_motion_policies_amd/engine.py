@@ -50,6 +50,7 @@ class Engine:
         _native.check(self._lib.rmp2_create(C.byref(desc), self.device.index or 0, C.byref(self._h)))
         self._dist_leaves = D.distance_leaf_indices(desc)
         self._self_counts = None   # self pairs per pair leaf (set_self_collision), None = off
+        self._hulls_key = None     # the link hulls the handle holds (set_link_hulls), None = off
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -344,6 +345,50 @@ class Engine:
         _native.check(self._lib.rmp2_closest_points_links(self._h, q.data_ptr(), C.byref(table), lc_ptr, p_link.data_ptr(),
                                                           p_obs.data_ptr(), R, s), self._h)
         return p_link, p_obs
+
+    def set_link_hulls(self, hulls) -> None:
+        """Convex-hull link geometry (include/rmp2.h rmp2_set_link_hulls): `hulls` = urdf.link_hulls(...) (one hull per distance /
+        attached-point leaf, leaf order, in each leaf's frame coordinates) or a tuple (vert_offset, verts, face_offset, planes).
+        Every later step with a shared sphere / capsule table forms each pair from the leaf's hull (the hull stage, then the
+        explicit-pair step).  None turns it off."""
+        if hulls is None:
+            if self._hulls_key is not None:
+                _native.check(self._lib.rmp2_set_link_hulls(self._h, 0, None, None, None, None), self._h)
+            self._hulls_key = None
+            return
+        vo, v, fo, p = (hulls.vert_offset, hulls.verts, hulls.face_offset, hulls.planes) if hasattr(hulls, "planes") else hulls
+        vo, fo = np.ascontiguousarray(vo, dtype=np.int32), np.ascontiguousarray(fo, dtype=np.int32)
+        v, p = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4)
+        n = len(self._dist_leaves)
+        if vo.shape != (n + 1,) or fo.shape != (n + 1,):
+            raise ValueError(f"link hulls: one hull per distance / attached-point leaf ({n}), offsets [{n + 1}]")
+        if vo[-1] != len(v) or fo[-1] != len(p):
+            raise ValueError("link hulls: the offsets must end at the number of vertices / planes")
+        key = (vo.tobytes(), v.tobytes(), fo.tobytes(), p.tobytes())
+        if key == self._hulls_key:
+            return   # (the same hulls: nothing to upload)
+        _native.check(self._lib.rmp2_set_link_hulls(self._h, n, vo.ctypes.data, v.ctypes.data, fo.ctypes.data, p.ctypes.data), self._h)
+        self._hulls_key = key
+
+    @property
+    def has_link_hulls(self) -> bool:
+        return self._hulls_key is not None
+
+    def closest_points_hulls(self, q: torch.Tensor, table):
+        """The hull stage on its own (rmp2_closest_points_hulls) for the shared table built by obstacles(spheres=...):
+        (p_link, p_obs, dist) [R, L K, 3], [R, L K, 3], [R, L K]; pair leaf i owns pairs [i K, (i + 1) K).  Distance leaves: the
+        nearest points of hull and primitive in the base frame; attached-point leaves: relative_position, normal_vec, distance."""
+        if self._hulls_key is None:
+            raise ValueError("link hulls are off: set_link_hulls first")
+        q = _f32(q, self.device)
+        R, P = q.shape[0], len(self._dist_leaves) * int(table.n_spheres)
+        p_link = torch.empty((R, P, 3), dtype=torch.float32, device=self.device)
+        p_obs = torch.empty_like(p_link)
+        dist = torch.empty((R, P), dtype=torch.float32, device=self.device)
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        _native.check(self._lib.rmp2_closest_points_hulls(self._h, q.data_ptr(), C.byref(table), p_link.data_ptr(), p_obs.data_ptr(),
+                                                          dist.data_ptr(), R, s), self._h)
+        return p_link, p_obs, dist
 
     def set_self_collision(self, pairs, capsules) -> None:
         """Self collision (include/rmp2.h rmp2_set_self_collision): `pairs` = [(leaf ordinal, frame B or -1)] as

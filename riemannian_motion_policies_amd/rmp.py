@@ -55,8 +55,9 @@ class _StageSource:
     """One call of RmpCore.update_distances: the inputs of the closest-point stage (snapshots: the caller may advance q or move
     the obstacles in place afterwards) and, once somebody asks for them, its output arrays."""
 
-    def __init__(self, core, eng, q, single, prim, lc, n_leaves, primitive=None, self_counts=None):
+    def __init__(self, core, eng, q, single, prim, lc, n_leaves, primitive=None, self_counts=None, hulls=None):
         self.core, self.eng, self.single, self.n_leaves = core, eng, single, n_leaves
+        self.hulls = hulls                # urdf.link_hulls (update_distances(link_hulls=)), None = capsules / frame origins
         self.self_counts = self_counts    # self pairs per leaf (update_distances(self_collision=True)), None = off
         self.primitive = primitive    # None (by record size) | "cylinder"
         # "the q the stage was given, unmodified": the tensor OBJECT (holding it pins its storage: the allocator cannot hand the
@@ -96,7 +97,12 @@ class _StageSource:
     def arrays(self):
         if self._arrays is None:
             table = self.eng.obstacles(spheres=self.prim, primitive=self.primitive)
-            pl, po = self.eng.closest_points(self.q, table, link_capsules=self.lc)
+            if self.hulls is not None:        # the hull stage (rmp2_closest_points_hulls)
+                self.eng.set_self_collision([], None)
+                self.eng.set_link_hulls(self.hulls)
+                pl, po, _ = self.eng.closest_points_hulls(self.q, table)
+            else:
+                pl, po = self.eng.closest_points(self.q, table, link_capsules=self.lc)
             if self.self_counts is not None:   # each leaf's range: its K obstacle pairs, then its self pairs (rmp2_step's layout)
                 self.eng.set_self_collision(*self.core._self_collision_list(self.eng))
                 spl, spo, _ = self.eng.self_pairs(self.q)
@@ -236,7 +242,7 @@ class RmpCore:
             self._self_key = key
         return self._self_list
 
-    def update_distances(self, q, primitives, link_capsules=None, primitive=None, self_collision=False):
+    def update_distances(self, q, primitives, link_capsules=None, primitive=None, self_collision=False, link_hulls=None):
         """The closest-point preprocessing stage on the device (simulation.py:462-484 calculate_distances followed by
         data_management.py:16-31 update): for every TaskmapJointFrame4x4ToDistance leaf and every obstacle primitive
         ([K,4] spheres or [K,8] capsules) the nearest points of the link (its capsule from `link_capsules`, rows in leaf order;
@@ -251,7 +257,11 @@ class RmpCore:
         self_collision=True: the reference's self-avoidance pairs as well (simulation.py:411-441; urdf.self_collision_pairs over
         the core's distance leaves, the base link included): each leaf's holders then hold its K obstacle pairs followed by its
         self pairs, the other links being obstacles of the step (include/rmp2.h rmp2_set_self_collision).  `primitives` may
-        have zero rows."""
+        have zero rows.
+        link_hulls=urdf.link_hulls(...) (one hull per distance leaf, leaf order): the link is its convex hull instead of a capsule
+        (include/rmp2.h rmp2_set_link_hulls) -- the nearest points of hull and sphere / capsule primitive; the fused route then
+        hands the primitives and the hulls to the step, which runs the hull stage itself.  Not with link_capsules or
+        self_collision."""
         single = q.dim() == 1 if isinstance(q, torch.Tensor) else np.ndim(q) == 1
         eng = self.engine_for(q)
         qt = as_tensor(q, eng.device)
@@ -264,12 +274,18 @@ class RmpCore:
             raise NotImplementedError("mixing explicit-pair and sphere distance task maps in one core")
         if len(dist_idx) != len(eng._dist_leaves):
             raise NotImplementedError("update_distances: attached-point leaves (TaskmapRelative4x4) carry their own pair data")
+        if link_hulls is not None and (link_capsules is not None or self_collision):
+            raise ValueError("update_distances: link_hulls replaces link_capsules and does not combine with self_collision")
+        if link_hulls is not None and primitive == "cylinder":
+            raise NotImplementedError("update_distances: link_hulls take sphere or capsule primitives, not cylinders")
         prim = as_tensor(primitives, eng.device)
         lc = None if link_capsules is None else as_tensor(link_capsules, eng.device)
+        if link_hulls is None:
+            eng.set_link_hulls(None)
         if self_collision:
             eng.set_self_collision(*self._self_collision_list(eng))
         src = _StageSource(self, eng, qt, single, prim, lc, len(leaves), primitive=primitive,
-                           self_counts=eng.self_counts if self_collision else None)
+                           self_counts=eng.self_counts if self_collision else None, hulls=link_hulls)
         self._stage = src
         names = self._table.frame_names
         frames = []
@@ -296,6 +312,11 @@ class RmpCore:
                 h = getattr(last, attr, None)
                 if not (isinstance(h, ArrayVar) and h.owner is src):
                     return None
+        if src.hulls is not None:         # the step runs the hull stage itself: the engine carries the hulls
+            eng.set_self_collision([], None)
+            eng.set_link_hulls(src.hulls)
+            return eng.obstacles(spheres=src.prim, primitive=src.primitive)
+        eng.set_link_hulls(None)
         if src.self_counts is not None:   # the step forms the self pairs itself: the engine carries the list
             eng.set_self_collision(*self._self_collision_list(eng))
             if src.K == 0:
@@ -322,6 +343,7 @@ class RmpCore:
         if pair_rmps:
             if all(isinstance(last, TaskmapSphereDistance) for _, _, last in pair_rmps):
                 eng.set_self_collision([], None)
+                eng.set_link_hulls(None)
                 sp = spheres if spheres is not None else self.spheres
                 if sp is None:
                     raise ValueError("TaskmapSphereDistance leaves need evaluate(..., spheres=[K,4])")
@@ -361,6 +383,7 @@ class RmpCore:
                 obstacles = eng.obstacles(p_link=p_link, p_obs=p_obs, dist=torch.cat(dd, dim=1) if has_point else None,
                                           pair_counts=counts)
                 eng.set_self_collision([], None)   # (explicit arrays: the self pairs, if any, are in them already)
+                eng.set_link_hulls(None)
             else:
                 raise NotImplementedError("mixing explicit-pair and sphere distance task maps in one core")
         out = eng.step(q2, qd2, goal=goal, obstacles=obstacles)
@@ -409,6 +432,7 @@ class RmpCore:
         if pair_rmps:
             if all(isinstance(last, TaskmapSphereDistance) for _, _, last in pair_rmps):
                 eng.set_self_collision([], None)
+                eng.set_link_hulls(None)
                 sp = spheres if spheres is not None else self.spheres
                 if sp is None:
                     raise ValueError("TaskmapSphereDistance leaves need evaluate(..., spheres=[K,4])")
@@ -442,6 +466,7 @@ class RmpCore:
                 obstacles = eng.obstacles(p_link=dev_parts[k], p_obs=dev_parts[k + 1], dist=dev_parts[k + 2] if has_point else None,
                                           pair_counts=[a.shape[1] for a in pl])
                 eng.set_self_collision([], None)   # (explicit arrays: the self pairs, if any, are in them already)
+                eng.set_link_hulls(None)
             else:
                 raise NotImplementedError("mixing explicit-pair and sphere distance task maps in one core")
         out = eng.step(q2, qd2, goal=goal, obstacles=obstacles)

@@ -423,6 +423,105 @@ def self_collision_capsules(urdf_filepath: str, table: KinematicTable, default_r
     return out
 
 
+# ---- convex-hull link geometry (simulation.py:462-484: PyBullet loads each .obj collision mesh as its convex hull) ------------
+
+MAX_HULL_VERTICES = 512   # include/rmp2.h RMP2_MAX_HULL_VERTICES
+MAX_HULL_FACES = 1024     # include/rmp2.h RMP2_MAX_HULL_FACES
+
+
+def read_obj_vertices(path: str) -> np.ndarray:
+    """The `v ` lines of a Wavefront .obj as [n, 3] float64."""
+    with open(path) as f:
+        v = [list(map(float, line.split()[1:4])) for line in f if line.startswith("v ")]
+    return np.asarray(v, dtype=np.float64).reshape(-1, 3)
+
+
+def collision_meshes(urdf_filepath: str) -> dict:
+    """{link name: (vertices [n, 3] float64, xyz [3], rpy [3])} for every link whose <collision> geometry is a <mesh>: the
+    mesh's vertex set as written in its .obj (`package://` resolved against the URDF's directory) and the collision origin that
+    places it on the link.  The package's kinematics-only URDFs have no meshes (an empty dict)."""
+    root = ElementTree.parse(urdf_filepath).getroot()
+    here = os.path.dirname(os.path.abspath(urdf_filepath))
+    out = {}
+    for link in root.findall("link"):
+        col = link.find("collision")
+        geom = col.find("geometry") if col is not None else None
+        mesh = geom.find("mesh") if geom is not None else None
+        if mesh is None:
+            continue
+        origin = col.find("origin")
+        path = os.path.join(here, mesh.attrib["filename"].replace("package://", ""))
+        out[link.attrib["name"]] = (read_obj_vertices(path),
+                                    np.asarray(_floats(origin.attrib.get("xyz") if origin is not None else None), dtype=np.float64),
+                                    np.asarray(_floats(origin.attrib.get("rpy") if origin is not None else None), dtype=np.float64))
+    return out
+
+
+@dataclass
+class LinkHulls:
+    """Convex hulls of the pair leaves' links, packed for rmp2_set_link_hulls: hull i (the i-th distance / attached-point leaf
+    in leaf order) has vertices verts[vert_offset[i]:vert_offset[i + 1]] and face planes planes[face_offset[i]:face_offset[i + 1]]
+    = (n, d) with unit outward n and n . x <= d inside, all in the leaf's FRAME coordinates."""
+    vert_offset: np.ndarray   # [L + 1] int32
+    verts: np.ndarray         # [V, 3] float32
+    face_offset: np.ndarray   # [L + 1] int32
+    planes: np.ndarray        # [F, 4] float32
+
+    def __len__(self) -> int:
+        return len(self.vert_offset) - 1
+
+    def hull(self, i: int):
+        """(vertices [n, 3], planes [m, 4]) of hull i."""
+        return (self.verts[self.vert_offset[i]:self.vert_offset[i + 1]], self.planes[self.face_offset[i]:self.face_offset[i + 1]])
+
+
+def convex_hull(points: np.ndarray):
+    """(vertices [n, 3] float64, planes [m, 4] float64) of the convex hull of `points` [k, 3]: the hull's vertices (a subset of
+    the points) and one outward unit plane (n, d), n . x <= d inside, per facet direction (coplanar triangles merged)."""
+    from scipy.spatial import ConvexHull   # (setup time only)
+    h = ConvexHull(np.asarray(points, dtype=np.float64))
+    verts = h.points[h.vertices]
+    eq = h.equations            # (n, offset) with n . x + offset <= 0 inside, n unit
+    planes = np.concatenate([eq[:, :3], -eq[:, 3:4]], axis=1)
+    keep = []
+    for p in planes:            # merge the triangles of one facet (same plane to 1e-9)
+        if not any(np.abs(p - q).max() <= 1e-9 for q in keep):
+            keep.append(p)
+    return verts, np.asarray(keep, dtype=np.float64)
+
+
+def link_hulls(table: KinematicTable, frames: Sequence[str], meshes: dict) -> LinkHulls:
+    """One convex hull per pair leaf (`frames` in leaf order, as link_capsules takes them), in that leaf's FRAME coordinates:
+    the mesh vertices of the frame's link placed by its collision origin (rotation_from_rpy_reference_order, as the fitted
+    capsules are), then their convex hull.  `meshes` maps link names to (vertices, xyz, rpy) -- collision_meshes(urdf) -- or to
+    a bare [n, 3] vertex set already in link coordinates.  A frame whose link has no entry is an error; so is a hull beyond
+    MAX_HULL_VERTICES / MAX_HULL_FACES."""
+    vo, fo, V, P = [0], [0], [], []
+    for fr in frames:
+        link = table.link_names[table.frame_index(fr)]
+        if link not in meshes:
+            raise ValueError(f"link_hulls: no collision mesh for link {link!r} (frame {fr!r}): pass its vertex set in `meshes`")
+        m = meshes[link]
+        if isinstance(m, (tuple, list)):
+            verts, xyz, rpy = m
+            Rc = rotation_from_rpy_reference_order(rpy).astype(np.float64)
+            pts = np.asarray(verts, dtype=np.float64) @ Rc.T + np.asarray(xyz, dtype=np.float64)
+        else:
+            pts = np.asarray(m, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != 3 or len(pts) < 4:
+            raise ValueError(f"link_hulls: link {link!r} needs at least 4 vertices [n, 3]")
+        hv, hp = convex_hull(pts)
+        if len(hv) > MAX_HULL_VERTICES or len(hp) > MAX_HULL_FACES:
+            raise ValueError(f"link_hulls: the hull of {link!r} has {len(hv)} vertices / {len(hp)} faces (at most "
+                             f"{MAX_HULL_VERTICES} / {MAX_HULL_FACES})")
+        V.append(hv)
+        P.append(hp)
+        vo.append(vo[-1] + len(hv))
+        fo.append(fo[-1] + len(hp))
+    return LinkHulls(np.asarray(vo, np.int32), np.ascontiguousarray(np.concatenate(V), dtype=np.float32).reshape(-1, 3),
+                     np.asarray(fo, np.int32), np.ascontiguousarray(np.concatenate(P), dtype=np.float32).reshape(-1, 4))
+
+
 def panda_table() -> KinematicTable:
     return compile_urdf(PANDA_URDF, PANDA_ORDER)
 
