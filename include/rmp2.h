@@ -495,11 +495,41 @@ int rmp2_self_pairs(rmp2_handle *h, const float *q, float *p_link, float *p_obs,
  * capture (step once outside it first).  Obstacle input NONE, or an empty table, steps as without hulls.
  * RMP2_ERR_UNSUPPORTED, with a message naming the combination: rmp2_rollout, rmp2_step_pair, rmp2_exchange_step, RAGGED_SPHERES
  * lists, CYLINDER tables, caller-supplied EXPLICIT_PAIRS, link_capsules given together with hulls, hulls together with self
- * collision.  Out of scope: hull-versus-hull self pairs, cylinder obstacles. */
+ * collision (hull self pairs: rmp2_set_self_collision_hulls).  Out of scope: cylinder obstacles. */
 int rmp2_set_link_hulls(rmp2_handle *h, int32_t n_hulls, const int32_t *vert_offset, const float *verts, const int32_t *face_offset,
                         const float *planes);
 int rmp2_closest_points_hulls(rmp2_handle *h, const float *q, const rmp2_obstacles *table, float *p_link, float *p_obs, float *dist,
                               int32_t R, void *stream);
+
+/* ---- hull-versus-hull self pairs: the reference's full distance state on the collision meshes ----------------------------
+ * The reference asks PyBullet for link-vs-obstacle AND link-vs-link closest points, both on the links' collision meshes loaded as
+ * convex hulls (simulation.py:411-484).  rmp2_set_self_collision_hulls is rmp2_set_self_collision with hulls in place of the
+ * capsules: the same pairs (leaf ordinal's link A against frame B's link, an obstacle for the step; urdf.self_collision_pairs), and
+ * n_hulls == n_frames + 1 entries packed as for rmp2_set_link_hulls -- entry f is frame f's link in FRAME coordinates, the last the
+ * base link in base coordinates (urdf.self_collision_hulls).  An entry may be empty (no vertices, no planes) only when no pair names
+ * its frame as A or B; with an obstacle table every pair leaf needs one.  Limits and argument checks as rmp2_set_link_hulls
+ * (RMP2_ERR_INVALID_ARGUMENT naming the limit).  Synchronous.
+ *   n_pairs == 0 (or rmp2_set_self_collision(h, 0, ...)) turns self collision off, either geometry: the handle then steps bit
+ *   for bit as a fresh one.  rmp2_set_self_collision with capsules replaces the hulls and this call replaces the capsules.
+ *   RMP2_ERR_UNSUPPORTED on a handle with link hulls; rmp2_set_link_hulls is refused on a handle with hull self pairs.
+ * Per self pair, both hulls in A's frame (B placed by R_A^T R_B, R_A^T (p_B - p_A)):
+ *   separated: GJK on the Minkowski difference A - B (B's support in direction d taken in B's own coordinates against
+ *     R_AB^T d), h_A and h_B the nearest points, g = |h_A - h_B|, u = (h_A - h_B) / g; p_link = h_A, p_obs = h_B.
+ *   overlapping or touching (|v|^2 <= 1e-14, or a GJK tetrahedron holding the origin): over the face normals n of A and the
+ *     negated face normals of B, s(n) = min_{y in B} n . y - max_{x in A} n . x (the plane offset d for the hull's own faces);
+ *     n* = argmax s (A's faces first, the first maximum), y* the vertex of B attaining the min; p_obs = y*, p_link = y* - s n*,
+ *     g = s < 0, u = -n*.  Edge-edge axes are not weighed: conservative against PyBullet's EPA, and unpinned (no reference depths).
+ *   Either way p_link - p_obs = g u.  FK_DISTANCE leaves: both points in the base frame.  FK_POINT leaves: p_link =
+ *   relative_position (h_A in the joint frame), p_obs = normal_vec = sign(g) u (base frame), dist = |g|.
+ *   Bounded: at most 64 GJK steps per pair (fp64; the best simplex is kept), one pass over each hull's planes for the face rule.
+ * rmp2_self_pairs on such a handle gives the hull pairs (layout of rmp2_set_self_collision).  rmp2_step with obstacle input NONE
+ * or a SHARED_SPHERES sphere / capsule table: each pair leaf's range is [K obstacle pairs | S_l self pairs], the obstacle pairs
+ * formed on the same leaf hulls, bit-identical to rmp2_closest_points_hulls on a handle whose link hulls are those hulls; then
+ * the explicit-pair step.  Buffer, growth and capture refusals as rmp2_set_self_collision's staged step.  RMP2_ERR_UNSUPPORTED,
+ * naming the combination: rmp2_rollout, rmp2_step_pair, rmp2_exchange_step, RAGGED_SPHERES lists, CYLINDER tables,
+ * caller-supplied EXPLICIT_PAIRS, link_capsules given, a table on a set with attached-point leaves. */
+int rmp2_set_self_collision_hulls(rmp2_handle *h, int32_t n_pairs, const int32_t *pairs, int32_t n_hulls, const int32_t *vert_offset,
+                                  const float *verts, const int32_t *face_offset, const float *planes);
 
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,

@@ -74,6 +74,8 @@ def lib():
     l.rmp2_set_self_collision.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     l.rmp2_self_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_set_link_hulls.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.rmp2_set_self_collision_hulls.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
     l.rmp2_closest_points_hulls.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(D.Obstacles), C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int32, C.c_void_p]
     l.rmp2_differentiate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,

@@ -1149,6 +1149,10 @@ struct HullProg {
   int32_t is_point[RMP2_MAX_LEAVES];          // ordinal -> 1: FK_POINT
   int32_t vert_off[RMP2_MAX_LEAVES + 1];
   int32_t face_off[RMP2_MAX_LEAVES + 1];
+  // hull self pairs (rmp2_set_self_collision_hulls): S self pairs per robot follow the obstacle pairs in each leaf's range, leaf o's
+  // range starting at o K + extra_before[o]; 0 for link hulls (pair leaf o owns [o K, (o + 1) K))
+  int32_t n_extra;
+  int32_t extra_before[RMP2_MAX_LEAVES];
 };
 
 constexpr int kHullRobots = 16;   // robots per wave (as kClosestRobots)
@@ -1199,11 +1203,12 @@ rmp2_hull_stage_kernel(const DevProgram* __restrict__ prog, const HullProg* __re
   }
   __syncthreads();
   const int n_live = min(kHullRobots, R - r0);
-  const int P = L * K;
+  const int P = L * K + hp->n_extra;
   for (int o = 0; o < L; ++o) {
     const int v0 = hp->vert_off[o], nv = hp->vert_off[o + 1] - v0;
     const int f0 = hp->face_off[o], nf = hp->face_off[o + 1] - f0;
     const bool point = hp->is_point[o] != 0;
+    const int obegin = o * K + hp->extra_before[o];
     for (int it = lane; it < n_live * K; it += kWave) {
       const int r = it / K, k = it - r * K;
       const float4 ca = CAPS ? table[2 * k] : table[k];
@@ -1221,7 +1226,7 @@ rmp2_hull_stage_kernel(const DevProgram* __restrict__ prog, const HullProg* __re
       }
       const double rad = ca.w;
       const HullHit hh = hull_closest(hverts + v0, nv, hplanes + f0, nf, a, b, rad);
-      const size_t pair = (size_t)(r0 + r) * P + (size_t)o * K + k;
+      const size_t pair = (size_t)(r0 + r) * P + (size_t)obegin + k;
       if (point) {   // relative_position (frame), normal_vec = sign(g) u (base), distance |g|  (link_pair_fields' conventions)
         const double sg = hh.gap >= 0.0 ? 1.0 : -1.0;
         f32x3 nvb;
@@ -1244,6 +1249,167 @@ rmp2_hull_stage_kernel(const DevProgram* __restrict__ prog, const HullProg* __re
       }
       if (dist) __builtin_nontemporal_store((float)fabs(hh.gap), dist + pair);
     }
+  }
+}
+
+// ---- hull-versus-hull self pairs (include/rmp2.h rmp2_set_self_collision_hulls) -------------------------------------------
+// The pair list of a handle with hull self pairs, compiled by rmp2_set_self_collision_hulls.  Hull entry e (frame e, the base
+// n_frames) owns the vertices [hv0[e], hv0[e] + hnv[e]) and the planes [hf0[e], hf0[e] + hnf[e]) of the handle's two arrays;
+// frame slots are the frames some pair names as A or B (rows of the stage's LDS; the base needs none).
+struct SelfHullProg {
+  int32_t n_pairs;                           // S = self pairs per robot, grouped by pair-leaf ordinal
+  int32_t n_slots;                           // frame slots
+  int32_t pad_[2];
+  int32_t slot_of_frame[RMP2_MAX_FRAMES];    // frame -> slot, -1: not named by a pair (the marker of the walk)
+  int32_t is_point[RMP2_MAX_LEAVES];         // ordinal -> 1: FK_POINT
+  int32_t pair_leaf[RMP2_MAX_SELF_PAIRS];    // self pair -> A's pair-leaf ordinal
+  int32_t pair_sa[RMP2_MAX_SELF_PAIRS];      // self pair -> A's frame slot
+  int32_t pair_sb[RMP2_MAX_SELF_PAIRS];      // self pair -> B's frame slot, -1: the base (identity)
+  int32_t pair_ea[RMP2_MAX_SELF_PAIRS];      // self pair -> A's hull entry
+  int32_t pair_eb[RMP2_MAX_SELF_PAIRS];      // self pair -> B's hull entry
+  int32_t hv0[RMP2_MAX_FRAMES + 1], hnv[RMP2_MAX_FRAMES + 1];
+  int32_t hf0[RMP2_MAX_FRAMES + 1], hnf[RMP2_MAX_FRAMES + 1];
+};
+
+constexpr int kSelfHullRobots = 64;   // robots per wave: one lane per robot
+
+// visit_frame's pose update without velocities, the parent chosen by selects (identity from the base) rather than by branches:
+// the hull self stage's walk needs no scratch this way.  cur = R (row-major) then p.
+__device__ __forceinline__ void walk_frame_position(float cur[12], const DevOp& op, float qv, bool from_base) {
+  const float ax[3] = {op.axis[0], op.axis[1], op.axis[2]};
+  float Rl[9], tl[3];
+  if (op.jtype == RMP2_JOINT_REVOLUTE) {
+    float sn, cs;
+    sincosf(qv, &sn, &cs);
+    const float omc = 1.0f - cs;
+    const float ut[9] = {0.f, -ax[2], ax[1], ax[2], 0.f, -ax[0], -ax[1], ax[0], 0.f};
+    float Rv[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) Rv[3 * r + k] = cs * (r == k ? 1.f : 0.f) + sn * ut[3 * r + k] + omc * (ax[r] * ax[k]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) Rl[3 * r + k] = op.Tc[4 * r + 0] * Rv[k] + op.Tc[4 * r + 1] * Rv[3 + k] + op.Tc[4 * r + 2] * Rv[6 + k];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tl[r] = op.Tc[4 * r + 3];
+  } else {
+    const float qp = op.jtype == RMP2_JOINT_PRISMATIC ? qv : 0.f;
+    const float tv[3] = {qp * ax[0], qp * ax[1], qp * ax[2]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) Rl[3 * r + k] = op.Tc[4 * r + k];
+      tl[r] = op.Tc[4 * r + 0] * tv[0] + op.Tc[4 * r + 1] * tv[1] + op.Tc[4 * r + 2] * tv[2] + op.Tc[4 * r + 3];
+    }
+  }
+  float Rp[12];
+#pragma unroll
+  for (int c = 0; c < 12; ++c) Rp[c] = from_base ? ((c == 0 || c == 4 || c == 8) ? 1.f : 0.f) : cur[c];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cur[3 * i + k] = Rp[3 * i + 0] * Rl[k] + Rp[3 * i + 1] * Rl[3 + k] + Rp[3 * i + 2] * Rl[6 + k];
+    cur[9 + i] = Rp[3 * i + 0] * tl[0] + Rp[3 * i + 1] * tl[1] + Rp[3 * i + 2] * tl[2] + Rp[9 + i];
+  }
+}
+
+// The hull self-pair stage.  One wave per nr (64 unless the frame slots overflow 64 KiB of LDS) robots, a lane per robot in both
+// phases.  Phase 1: a walk of the unpruned program (`prog_full`) puts the frame of every slot into LDS, [slot][12][nr] floats
+// (rows of R with the origin in the 4th column), so each lane reads its own robot's frames without bank conflicts.  Phase 2: the
+// self pairs one after another -- the pair, and with it both hulls, is wave-uniform, so their vertices and planes are read at
+// uniform addresses through the scalar cache and the support loops have a uniform trip count --: B is placed in A's frame
+// (R_A^T R_B, R_A^T (p_B - p_A)) and rmp2_hull.h hull_pair_closest finds the pair (fp64 GJK, at most kPairGjkIters steps; the face
+// rule where the hulls overlap).  Self pair j of leaf o goes to entry (o + 1) K + j of the robot's P pairs: each leaf's range is
+// [K obstacle pairs | S_l self pairs] (K = 0 without a table; with one, every pair leaf is a distance leaf).
+template <int SLOTS>
+__global__ void __launch_bounds__(kWave)
+rmp2_self_hull_stage_kernel(const DevProgram* __restrict__ prog_full, const SelfHullProg* __restrict__ sp, const float4* __restrict__ hverts,
+                            const float4* __restrict__ hplanes, const float* __restrict__ q, float* __restrict__ p_link,
+                            float* __restrict__ p_obs, float* __restrict__ dist, int P, int K, int R, int nr) {
+  extern __shared__ float frs[];   // [n_slots][12][nr]
+  const int lane = threadIdx.x;
+  const int robot = blockIdx.x * nr + lane;
+  if (lane >= nr || robot >= R) return;   // (no barrier below: a lane reads only what it wrote)
+  {
+    const float* my_q = q + (size_t)robot * prog_full->n_dof;
+    float cur[12];   // R row-major, then p  (visit_frame's positions; no velocities)
+    float saved[SLOTS > 0 ? SLOTS : 1][12];
+#pragma unroll
+    for (int c = 0; c < 12; ++c) cur[c] = 0.f;
+    for (int k = 0; k < prog_full->n_ops; ++k) {
+      const DevOp& op = prog_full->ops[k];
+      if (SLOTS > 0 && op.restore >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+#pragma unroll
+          for (int c = 0; c < 12; ++c) cur[c] = op.restore == s ? saved[s][c] : cur[c];
+      }
+      walk_frame_position(cur, op, op.qidx >= 0 ? my_q[op.qidx] : 0.f, op.restore == -2);
+      if (SLOTS > 0 && op.save >= 0) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s)
+#pragma unroll
+          for (int c = 0; c < 12; ++c) saved[s][c] = op.save == s ? cur[c] : saved[s][c];
+      }
+      const int fs = sp->slot_of_frame[op.frame];
+      if (fs < 0) continue;
+      float* rec = frs + (size_t)fs * 12 * nr + lane;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rec[(4 * i + c) * nr] = cur[3 * i + c];
+        rec[(4 * i + 3) * nr] = cur[9 + i];
+      }
+    }
+  }
+  const size_t row = (size_t)robot * P;
+  for (int j = 0; j < sp->n_pairs; ++j) {
+    const int o = sp->pair_leaf[j], sa = sp->pair_sa[j], sb = sp->pair_sb[j], ea = sp->pair_ea[j], eb = sp->pair_eb[j];
+    float A[12], B[12];
+#pragma unroll
+    for (int c = 0; c < 12; ++c) A[c] = frs[((size_t)sa * 12 + c) * nr + lane];
+    if (sb >= 0) {
+#pragma unroll
+      for (int c = 0; c < 12; ++c) B[c] = frs[((size_t)sb * 12 + c) * nr + lane];
+    } else {   // the fixed base
+#pragma unroll
+      for (int c = 0; c < 12; ++c) B[c] = (c == 0 || c == 5 || c == 10) ? 1.f : 0.f;
+    }
+    // B in A's frame: Rm = R_A^T R_B, t = R_A^T (p_B - p_A)   (R_X[i][c] = X[4 i + c], p_X[i] = X[4 i + 3])
+    double Rm[9], t[3];
+    const double dp[3] = {(double)B[3] - (double)A[3], (double)B[7] - (double)A[7], (double)B[11] - (double)A[11]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        Rm[3 * i + c] = (double)A[i] * (double)B[c] + (double)A[4 + i] * (double)B[4 + c] + (double)A[8 + i] * (double)B[8 + c];
+      t[i] = (double)A[i] * dp[0] + (double)A[4 + i] * dp[1] + (double)A[8 + i] * dp[2];
+    }
+    const PairHit hh = hull_pair_closest(hverts + sp->hv0[ea], sp->hnv[ea], hplanes + sp->hf0[ea], sp->hnf[ea], hverts + sp->hv0[eb],
+                                         sp->hnv[eb], hplanes + sp->hf0[eb], sp->hnf[eb], Rm, t);
+    const size_t pair = row + (size_t)K * (o + 1) + j;
+    if (sp->is_point[o]) {   // relative_position (frame), normal_vec = sign(g) u (base), distance |g|  (link_pair_fields' conventions)
+      const double sg = hh.gap >= 0.0 ? 1.0 : -1.0;
+      f32x3 nvb;
+      nvb.x = (float)(sg * (A[0] * hh.u[0] + A[1] * hh.u[1] + A[2] * hh.u[2]));
+      nvb.y = (float)(sg * (A[4] * hh.u[0] + A[5] * hh.u[1] + A[6] * hh.u[2]));
+      nvb.z = (float)(sg * (A[8] * hh.u[0] + A[9] * hh.u[1] + A[10] * hh.u[2]));
+      __builtin_nontemporal_store(f32x3{(float)hh.pa[0], (float)hh.pa[1], (float)hh.pa[2]}, reinterpret_cast<f32x3*>(p_link + 3 * pair));
+      __builtin_nontemporal_store(nvb, reinterpret_cast<f32x3*>(p_obs + 3 * pair));
+    } else {                 // the two points in the base frame: p_link = R_A pa + p_A, p_obs = R_A pb + p_A
+      f32x3 L3, O3;
+      L3.x = (float)(A[0] * hh.pa[0] + A[1] * hh.pa[1] + A[2] * hh.pa[2] + A[3]);
+      L3.y = (float)(A[4] * hh.pa[0] + A[5] * hh.pa[1] + A[6] * hh.pa[2] + A[7]);
+      L3.z = (float)(A[8] * hh.pa[0] + A[9] * hh.pa[1] + A[10] * hh.pa[2] + A[11]);
+      O3.x = (float)(A[0] * hh.pb[0] + A[1] * hh.pb[1] + A[2] * hh.pb[2] + A[3]);
+      O3.y = (float)(A[4] * hh.pb[0] + A[5] * hh.pb[1] + A[6] * hh.pb[2] + A[7]);
+      O3.z = (float)(A[8] * hh.pb[0] + A[9] * hh.pb[1] + A[10] * hh.pb[2] + A[11]);
+      __builtin_nontemporal_store(L3, reinterpret_cast<f32x3*>(p_link + 3 * pair));
+      __builtin_nontemporal_store(O3, reinterpret_cast<f32x3*>(p_obs + 3 * pair));
+    }
+    if (dist) __builtin_nontemporal_store((float)fabs(hh.gap), dist + pair);
   }
 }
 
@@ -2307,6 +2473,10 @@ int rmp2_destroy(rmp2_handle* h) {
   if (h->d_hull_verts) (void)hipFree(h->d_hull_verts);
   if (h->d_hull_planes) (void)hipFree(h->d_hull_planes);
   if (h->d_hull_buf) (void)hipFree(h->d_hull_buf);
+  if (h->d_shull) (void)hipFree(h->d_shull);
+  if (h->d_shull_obs) (void)hipFree(h->d_shull_obs);
+  if (h->d_shull_verts) (void)hipFree(h->d_shull_verts);
+  if (h->d_shull_planes) (void)hipFree(h->d_shull_planes);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
   return RMP2_OK;
@@ -2485,6 +2655,36 @@ static int launch_self_stage(rmp2_handle* h, const float* q, const rmp2_obstacle
   return RMP2_OK;
 }
 
+static int launch_hull_stage(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
+                             int32_t R, hipStream_t s);
+
+// Launch of the hull self-pair stage: with `table` (a SHARED_SPHERES sphere / capsule table, K > 0) rmp2_hull_stage_kernel first
+// forms the K obstacle pairs of each leaf on the leaves' hulls, then rmp2_self_hull_stage_kernel the self pairs behind them;
+// without, the self pairs alone.  P = pairs per robot of the layout.
+static int launch_self_hull_stage(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
+                                  int P, int32_t R, hipStream_t s) {
+  const int K = table ? table->n_spheres : 0;
+  if (K > 0)
+    if (int rc = launch_hull_stage(h, q, table, p_link, p_obs, dist, R, s)) return rc;
+  const int slots = h->shull_slots;
+  int nr = kSelfHullRobots;
+  while (nr > 1 && sizeof(float) * 12 * (size_t)slots * nr > 64 * 1024) nr /= 2;
+  const size_t lds_bytes = sizeof(float) * 12 * (size_t)(slots > 0 ? slots : 1) * nr;
+  const int blocks = (R + nr - 1) / nr;
+  const SelfHullProg* sp = static_cast<const SelfHullProg*>(h->d_shull);
+#define RMP2_SELF_HULL_STAGE_(SLOTS_)                                                                                           \
+  hipLaunchKernelGGL((rmp2_self_hull_stage_kernel<SLOTS_>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog_full, sp,      \
+                     h->d_shull_verts, h->d_shull_planes, q, p_link, p_obs, dist, P, K, (int)R, nr)
+  switch (h->n_slots_full) {   // (the kernel walks the unpruned program: its save slots, not the step's)
+    case 0: RMP2_SELF_HULL_STAGE_(0); break;
+    case 1: RMP2_SELF_HULL_STAGE_(1); break;
+    default: RMP2_SELF_HULL_STAGE_(2); break;
+  }
+#undef RMP2_SELF_HULL_STAGE_
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
 // The staged step of a handle with self collision (include/rmp2.h): validates the obstacle input, forms every pair leaf's range
 // [K obstacle pairs | S_l self pairs] in the handle's buffer and describes it as EXPLICIT_PAIRS in `staged`.
 static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs, const RolloutArgs& ro, int32_t R, void* stream,
@@ -2511,6 +2711,11 @@ static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs,
       return fail(h, RMP2_ERR_UNSUPPORTED, "self collision with an obstacle table on a set with attached-point leaves: not supported "
                                            "(obstacle input NONE, or a set of distance leaves)");
   }
+  if (h->self_hulls && mode == RMP2_OBS_SHARED_SPHERES && obs->link_capsules)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "link_capsules given together with hull self pairs: the obstacle pairs are formed on the same "
+                                         "hulls (turn the hulls off with rmp2_set_self_collision(h, 0, ...) to step on capsules)");
+  if (h->self_hulls && with_table && h->shull_leaf_empty)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs with an obstacle table: every distance leaf needs a hull (an entry is empty)");
   const size_t K = with_table ? (size_t)obs->n_spheres : 0;
   const size_t L = h->pair_leaves.size();
   size_t P = 0;
@@ -2548,7 +2753,11 @@ static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs,
   float* const pl = h->d_self_buf;
   float* const po = pl + arr;
   float* const dd = h->has_point ? po + arr : nullptr;
-  if (int rc = launch_self_stage(h, q, with_table ? obs : nullptr, pl, po, dd, (int)P, R, s)) return rc;
+  if (h->self_hulls) {
+    if (int rc = launch_self_hull_stage(h, q, with_table ? obs : nullptr, pl, po, dd, (int)P, R, s)) return rc;
+  } else if (int rc = launch_self_stage(h, q, with_table ? obs : nullptr, pl, po, dd, (int)P, R, s)) {
+    return rc;
+  }
   std::memset(&staged, 0, sizeof(staged));
   staged.mode = RMP2_OBS_EXPLICIT_PAIRS;
   staged.n_pairs = (int32_t)P;
@@ -2558,16 +2767,21 @@ static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs,
 }
 
 // Launch of rmp2_hull_stage_kernel over a SHARED_SPHERES sphere / capsule table (K > 0): pair leaf o owns pairs [o K, (o + 1) K).
+// The hulls are the handle's link hulls, or with hull self pairs the pair leaves' hulls of that list (whose HullProg places each
+// leaf's obstacle pairs in front of its self pairs).
 static int launch_hull_stage(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
                              int32_t R, hipStream_t s) {
-  const int L = h->hull_n, K = table->n_spheres;
+  const bool self = h->self_hulls && h->self_n_pairs > 0;
+  const int L = self ? (int)h->pair_leaves.size() : h->hull_n, K = table->n_spheres;
   const size_t lds_bytes = sizeof(float4) * 3 * (size_t)L * kHullRobots;
   const int blocks = (R + kHullRobots - 1) / kHullRobots;
-  const HullProg* hp = static_cast<const HullProg*>(h->d_hull);
+  const HullProg* hp = static_cast<const HullProg*>(self ? h->d_shull_obs : h->d_hull);
+  const float4* hv = self ? h->d_shull_verts : h->d_hull_verts;
+  const float4* hpl = self ? h->d_shull_planes : h->d_hull_planes;
   const float4* tab = reinterpret_cast<const float4*>(table->spheres);
 #define RMP2_HULL_STAGE_(SLOTS_, CAPS_)                                                                                      \
   hipLaunchKernelGGL((rmp2_hull_stage_kernel<SLOTS_, CAPS_>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog, hp,      \
-                     h->d_hull_verts, h->d_hull_planes, q, tab, K, p_link, p_obs, dist, (int)R)
+                     hv, hpl, q, tab, K, p_link, p_obs, dist, (int)R)
   const bool caps = table->primitive == RMP2_PRIM_CAPSULE;
   switch (h->n_slots) {
     case 0: if (caps) RMP2_HULL_STAGE_(0, true); else RMP2_HULL_STAGE_(0, false); break;
@@ -3169,9 +3383,10 @@ int rmp2_closest_points_links(rmp2_handle* h, const float* q, const rmp2_obstacl
 int rmp2_set_self_collision(rmp2_handle* h, int32_t n_pairs, const int32_t* pairs, const float* capsules) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   if (n_pairs < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "n_pairs < 0");
-  if (n_pairs == 0 || !pairs) {   // off: the handle steps as one on which this was never called
+  if (n_pairs == 0 || !pairs) {   // off (either geometry): the handle steps as one on which this was never called
     h->self_n_pairs = 0;
     h->self_counts.clear();
+    h->self_hulls = false;
     return RMP2_OK;
   }
   if (h->hull_n > 0)
@@ -3238,6 +3453,7 @@ int rmp2_set_self_collision(rmp2_handle* h, int32_t n_pairs, const int32_t* pair
   h->self_n_b = sp.n_b;
   h->self_counts = counts;
   h->self_n_pairs = n_pairs;
+  h->self_hulls = false;   // (capsules replace hull self pairs)
   return RMP2_OK;
 }
 
@@ -3250,6 +3466,7 @@ int rmp2_self_pairs(rmp2_handle* h, const float* q, float* p_link, float* p_obs,
   if (point_pairs && !dist) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "attached-point leaves have self pairs: dist is required");
   if (R == 0) return RMP2_OK;
   if (int rc = use_device(h)) return rc;
+  if (h->self_hulls) return launch_self_hull_stage(h, q, nullptr, p_link, p_obs, dist, h->self_n_pairs, R, (hipStream_t)stream);
   return launch_self_stage(h, q, nullptr, p_link, p_obs, dist, h->self_n_pairs, R, (hipStream_t)stream);
 }
 
@@ -3319,6 +3536,150 @@ int rmp2_set_link_hulls(rmp2_handle* h, int32_t n_hulls, const int32_t* vert_off
   HIP_TRY(h, hipMemcpy(h->d_hull_planes, hpl.data(), sizeof(float4) * NF, hipMemcpyHostToDevice));
   HIP_TRY(h, hipMemcpy(h->d_hull, &hp, sizeof(HullProg), hipMemcpyHostToDevice));
   h->hull_n = L;
+  return RMP2_OK;
+}
+
+int rmp2_set_self_collision_hulls(rmp2_handle* h, int32_t n_pairs, const int32_t* pairs, int32_t n_hulls, const int32_t* vert_offset,
+                                  const float* verts, const int32_t* face_offset, const float* planes) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (n_pairs < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "n_pairs < 0");
+  if (n_pairs == 0 || !pairs) return rmp2_set_self_collision(h, 0, nullptr, nullptr);   // off (either geometry)
+  if (h->hull_n > 0)
+    return fail(h, RMP2_ERR_UNSUPPORTED, "hull self pairs together with link hulls: not supported (turn the link hulls off first; the "
+                                         "hull self pairs form the obstacle pairs on the same hulls)");
+  if (n_pairs > RMP2_MAX_SELF_PAIRS)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self collision: at most " + std::to_string(RMP2_MAX_SELF_PAIRS) + " pairs, got " +
+                                                  std::to_string(n_pairs));
+  const int F = h->n_frames, L = (int)h->pair_leaves.size();
+  if (n_hulls != F + 1)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: one hull entry per frame and the base (" + std::to_string(F + 1) +
+                                                  "), got " + std::to_string(n_hulls));
+  if (!vert_offset || !verts || !face_offset || !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: null array");
+  if (vert_offset[0] != 0 || face_offset[0] != 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: offsets must start at 0");
+  for (int e = 0; e <= F; ++e) {
+    const int nv = vert_offset[e + 1] - vert_offset[e], nf = face_offset[e + 1] - face_offset[e];
+    if (nv < 0 || nf < 0 || (nv == 0) != (nf == 0))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull entry " + std::to_string(e) + ": needs vertices and face planes, or neither");
+    if (nv > RMP2_MAX_HULL_VERTICES || nf > RMP2_MAX_HULL_FACES)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull entry " + std::to_string(e) + ": " + std::to_string(nv) + " vertices / " +
+                                                    std::to_string(nf) + " faces, at most RMP2_MAX_HULL_VERTICES = " +
+                                                    std::to_string(RMP2_MAX_HULL_VERTICES) + " / RMP2_MAX_HULL_FACES = " +
+                                                    std::to_string(RMP2_MAX_HULL_FACES));
+  }
+  const size_t NV = (size_t)vert_offset[F + 1], NF = (size_t)face_offset[F + 1];
+  for (size_t i = 0; i < NV; ++i)
+    if (!std::isfinite(verts[3 * i]) || !std::isfinite(verts[3 * i + 1]) || !std::isfinite(verts[3 * i + 2]))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: vertex " + std::to_string(i) + " is not finite");
+  for (size_t i = 0; i < NF; ++i) {
+    const float* pl = planes + 4 * i;
+    const double n2 = (double)pl[0] * pl[0] + (double)pl[1] * pl[1] + (double)pl[2] * pl[2];
+    if (!std::isfinite(pl[3]) || !(std::fabs(n2 - 1.0) <= 1e-4))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: plane " + std::to_string(i) + " needs a unit normal and a finite offset");
+  }
+  // the pairs (rmp2_set_self_collision's rule), grouped by ordinal
+  int ord_of_leaf[RMP2_MAX_LEAVES];
+  for (int l = 0; l < RMP2_MAX_LEAVES; ++l) ord_of_leaf[l] = -1;
+  for (int o = 0; o < L; ++o) ord_of_leaf[h->pair_leaves[o]] = o;
+  std::vector<std::vector<int>> by_leaf(L);
+  auto entry_empty = [&](int e) { return vert_offset[e + 1] == vert_offset[e]; };
+  for (int k = 0; k < n_pairs; ++k) {
+    const int leaf = pairs[2 * k], b = pairs[2 * k + 1];
+    const int o = (leaf >= 0 && leaf < h->n_leaves) ? ord_of_leaf[leaf] : -1;
+    if (o < 0)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": leaf " + std::to_string(leaf) +
+                                                    " is not a distance or attached-point leaf");
+    if (b < -1 || b >= F)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B " + std::to_string(b) + " out of range");
+    if (b == h->pair_leaf_frame[o])
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B is the leaf's own frame");
+    if (entry_empty(h->pair_leaf_frame[o]) || entry_empty(b < 0 ? F : b))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": its hull entry " +
+                                                    std::to_string(entry_empty(h->pair_leaf_frame[o]) ? h->pair_leaf_frame[o] : (b < 0 ? F : b)) +
+                                                    " is empty");
+    by_leaf[o].push_back(b);
+  }
+  // device arrays: the pair leaves' hulls first, in ordinal order (the obstacle half's HullProg), then every other non-empty entry
+  HullProg hp;
+  std::memset(&hp, 0, sizeof(hp));
+  hp.n_leaves = L;
+  for (int l = 0; l < RMP2_MAX_LEAVES; ++l) hp.ord_of_leaf[l] = -1;
+  SelfHullProg sp;
+  std::memset(&sp, 0, sizeof(sp));
+  for (int f = 0; f < RMP2_MAX_FRAMES; ++f) sp.slot_of_frame[f] = -1;
+  std::vector<float4> hv, hpl;
+  std::vector<int> placed(F + 1, -1);
+  auto append = [&](int e) {
+    for (int i = vert_offset[e]; i < vert_offset[e + 1]; ++i) hv.push_back(make_float4(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2], 0.f));
+    for (int i = face_offset[e]; i < face_offset[e + 1]; ++i)
+      hpl.push_back(make_float4(planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]));
+  };
+  auto place = [&](int e) {   // the copy the self stage reads entry e from
+    placed[e] = 1;
+    sp.hv0[e] = (int)hv.size(), sp.hf0[e] = (int)hpl.size();
+    sp.hnv[e] = vert_offset[e + 1] - vert_offset[e], sp.hnf[e] = face_offset[e + 1] - face_offset[e];
+    append(e);
+  };
+  bool leaf_empty = false;
+  for (int o = 0; o < L; ++o) {   // (two leaves on one frame share nothing here: each gets its own copy, as rmp2_set_link_hulls)
+    const int e = h->pair_leaf_frame[o];
+    hp.ord_of_leaf[h->pair_leaves[o]] = o;
+    hp.is_point[o] = h->pair_leaf_point[o];
+    hp.vert_off[o] = (int)hv.size(), hp.face_off[o] = (int)hpl.size();
+    leaf_empty = leaf_empty || entry_empty(e);
+    if (placed[e] < 0) place(e);
+    else append(e);
+  }
+  hp.vert_off[L] = (int)hv.size(), hp.face_off[L] = (int)hpl.size();
+  for (int e = 0; e <= F; ++e)
+    if (placed[e] < 0 && !entry_empty(e)) place(e);
+  std::vector<int> counts(L);
+  int j = 0;
+  auto slot_of = [&](int f) {
+    if (sp.slot_of_frame[f] < 0) sp.slot_of_frame[f] = sp.n_slots++;
+    return sp.slot_of_frame[f];
+  };
+  for (int o = 0; o < L; ++o) {
+    hp.extra_before[o] = j;
+    counts[o] = (int)by_leaf[o].size();
+    sp.is_point[o] = h->pair_leaf_point[o];
+    for (int b : by_leaf[o]) {
+      const int fa = h->pair_leaf_frame[o];
+      sp.pair_leaf[j] = o;
+      sp.pair_sa[j] = slot_of(fa);
+      sp.pair_sb[j] = b < 0 ? -1 : slot_of(b);
+      sp.pair_ea[j] = fa;
+      sp.pair_eb[j] = b < 0 ? F : b;
+      ++j;
+    }
+  }
+  sp.n_pairs = j;
+  hp.n_extra = j;
+  if (int rc = use_device(h)) return rc;
+  const size_t nv_all = hv.size() > 0 ? hv.size() : 1, nf_all = hpl.size() > 0 ? hpl.size() : 1;
+  if (nv_all > h->shull_verts_cap) {
+    if (h->d_shull_verts) HIP_TRY(h, hipFree(h->d_shull_verts));
+    h->d_shull_verts = nullptr, h->shull_verts_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->d_shull_verts, sizeof(float4) * nv_all));
+    h->shull_verts_cap = nv_all;
+  }
+  if (nf_all > h->shull_planes_cap) {
+    if (h->d_shull_planes) HIP_TRY(h, hipFree(h->d_shull_planes));
+    h->d_shull_planes = nullptr, h->shull_planes_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->d_shull_planes, sizeof(float4) * nf_all));
+    h->shull_planes_cap = nf_all;
+  }
+  if (!h->d_shull) HIP_TRY(h, hipMalloc(&h->d_shull, sizeof(SelfHullProg)));
+  if (!h->d_shull_obs) HIP_TRY(h, hipMalloc(&h->d_shull_obs, sizeof(HullProg)));
+  // (synchronous copies: no launch still reads the old hulls)
+  if (!hv.empty()) HIP_TRY(h, hipMemcpy(h->d_shull_verts, hv.data(), sizeof(float4) * hv.size(), hipMemcpyHostToDevice));
+  if (!hpl.empty()) HIP_TRY(h, hipMemcpy(h->d_shull_planes, hpl.data(), sizeof(float4) * hpl.size(), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->d_shull, &sp, sizeof(SelfHullProg), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->d_shull_obs, &hp, sizeof(HullProg), hipMemcpyHostToDevice));
+  h->shull_slots = sp.n_slots;
+  h->shull_leaf_empty = leaf_empty;
+  h->self_counts = counts;
+  h->self_n_pairs = n_pairs;
+  h->self_hulls = true;
   return RMP2_OK;
 }
 

@@ -81,6 +81,15 @@ struct rmp2_handle {
   size_t hull_verts_cap = 0, hull_planes_cap = 0;
   float* d_hull_buf = nullptr;          // p_link | p_obs | dist of the stage when a step runs as hull stage + explicit-pair step
   size_t hull_buf_floats = 0;
+  // hull self pairs (rmp2_set_self_collision_hulls): the self-collision list above, on hulls while self_hulls is set
+  bool self_hulls = false;
+  bool shull_leaf_empty = false;        // some pair leaf has no hull: no obstacle pairs on such a handle
+  int shull_slots = 0;                  // frame slots of the stage's LDS
+  void* d_shull = nullptr;              // SelfHullProg (rmp2_hip.hip)
+  void* d_shull_obs = nullptr;          // HullProg of the pair leaves' hulls (the obstacle half)
+  float4* d_shull_verts = nullptr;      // the pair leaves' hulls first (ordinal order), then the other entries
+  float4* d_shull_planes = nullptr;
+  size_t shull_verts_cap = 0, shull_planes_cap = 0;
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
   mutable const char* last_kernel = "none";  // mapping the last control step / rollout was launched with (rmp2_last_kernel)
   std::string error;

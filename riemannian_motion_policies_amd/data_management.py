@@ -122,7 +122,8 @@ class Datamanager:
             T = T_all[self.fkine.table.frame_index(frame)]
             st["relative_position"].assign((p_link - T[:3, 3][None, :]) @ T[:3, :3])
 
-    def update_device(self, core, q, primitives, link_capsules=None, primitive=None, self_collision=False, link_hulls=None):
+    def update_device(self, core, q, primitives, link_capsules=None, primitive=None, self_collision=False, link_hulls=None,
+                      self_hulls=None):
         """The same five fields, filled on the device for a whole fleet without PyBullet and without a host hop: `core` is the
         RmpCore whose distance leaves read this manager's holders; its closest-point stage (rmp2_closest_points_links) writes
         pos_on_link / pos_on_obstacle for every (robot, leaf, primitive) pair, and distance, normal_vec and relative_position
@@ -132,10 +133,12 @@ class Datamanager:
         urdf.link_capsules(...) rows in the order of the core's distance leaves, or None for the frame origins as control points.
         self_collision=True: each frame's fields hold its K obstacle pairs followed by its self pairs (RmpCore.update_distances).
         link_hulls: urdf.link_hulls(...) in the order of the core's distance leaves -- the links' convex hulls instead of capsules
-        (mutually exclusive with link_capsules)."""
+        (mutually exclusive with link_capsules).  self_hulls: urdf.self_collision_hulls(...) -- self collision hull against hull,
+        the obstacle pairs on the same hulls (implies self_collision; not with link_capsules or link_hulls)."""
         import torch
         pairs = core.update_distances(q, primitives, link_capsules=link_capsules, primitive=primitive,
-                                      self_collision=self_collision, link_hulls=link_hulls)   # (lazy: nothing has run yet)
+                                      self_collision=self_collision, link_hulls=link_hulls,
+                                      self_hulls=self_hulls)   # (lazy: nothing has run yet)
         src = pairs.source
         eng, single = src.eng, src.single
         frames = pairs.frames

@@ -418,6 +418,44 @@ class Engine:
         # (the library keeps each leaf's pairs in the order given, leaves in leaf order)
         self._self_counts, self._self_key = counts, key
 
+    def set_self_collision_hulls(self, pairs, hulls) -> None:
+        """Self collision on the links' convex hulls (include/rmp2.h rmp2_set_self_collision_hulls): `pairs` as for
+        set_self_collision, `hulls` = urdf.self_collision_hulls(...) (n_frames + 1 entries: frame f's link in frame coordinates,
+        then the base link).  Every later step forms the self pairs hull against hull and the obstacle pairs of a shared sphere /
+        capsule table on the same leaf hulls.  Empty `pairs` turns self collision off (either geometry)."""
+        pairs = [(int(a), int(b)) for a, b in (pairs or [])]
+        if not pairs:
+            self.set_self_collision([], None)
+            return
+        dl = self._dist_leaves
+        if any(not 0 <= a < len(dl) for a, _ in pairs):
+            raise ValueError(f"leaf ordinals must lie in [0, {len(dl)})")
+        vo, v, fo, p = (hulls.vert_offset, hulls.verts, hulls.face_offset, hulls.planes) if hasattr(hulls, "planes") else hulls
+        vo, fo = np.ascontiguousarray(vo, dtype=np.int32), np.ascontiguousarray(fo, dtype=np.int32)
+        v, p = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4)
+        n = len(vo) - 1
+        if n != self.n_frames + 1 or len(fo) != n + 1:
+            raise ValueError(f"hull self pairs: one hull entry per frame and the base ({self.n_frames + 1}), offsets "
+                             f"[{self.n_frames + 2}]")
+        if vo[-1] != len(v) or fo[-1] != len(p):
+            raise ValueError("hull self pairs: the offsets must end at the number of vertices / planes")
+        key = ("hulls", tuple(pairs), vo.tobytes(), v.tobytes(), fo.tobytes(), p.tobytes())
+        if self._self_counts is not None and getattr(self, "_self_key", None) == key:
+            return   # (the same list: nothing to upload)
+        arr = np.ascontiguousarray([(dl[a], b) for a, b in pairs], dtype=np.int32)
+        _native.check(self._lib.rmp2_set_self_collision_hulls(self._h, len(pairs), arr.ctypes.data, n, vo.ctypes.data, v.ctypes.data,
+                                                              fo.ctypes.data, p.ctypes.data), self._h)
+        counts = [0] * len(dl)
+        for a, _ in pairs:
+            counts[a] += 1
+        self._self_counts, self._self_key = counts, key
+
+    @property
+    def has_self_hulls(self) -> bool:
+        """True while the self pairs are on hulls (set_self_collision_hulls)."""
+        key = getattr(self, "_self_key", None)
+        return self._self_counts is not None and key is not None and key[0] == "hulls"
+
     @property
     def self_counts(self):
         """Self pairs per distance / attached-point leaf (leaf order), or None when self collision is off."""
@@ -425,8 +463,9 @@ class Engine:
 
     def self_pairs(self, q: torch.Tensor):
         """The self-pair stage on its own (rmp2_self_pairs): (p_link, p_obs, dist) [R, S, 3], [R, S, 3], [R, S]; leaf ordinal
-        i's pairs at [S_0 + ... + S_{i-1}, + S_i).  Distance leaves: the nearest points of the two capsule surfaces (dist =
-        their distance); attached-point leaves: relative_position in the joint frame, normal_vec and distance."""
+        i's pairs at [S_0 + ... + S_{i-1}, + S_i).  Distance leaves: the nearest points of the two capsule surfaces -- of the
+        two hulls after set_self_collision_hulls -- (dist = their distance); attached-point leaves: relative_position in the joint
+        frame, normal_vec and distance."""
         if self._self_counts is None:
             raise ValueError("self collision is off: set_self_collision first")
         q = _f32(q, self.device)

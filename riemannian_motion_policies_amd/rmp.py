@@ -55,9 +55,10 @@ class _StageSource:
     """One call of RmpCore.update_distances: the inputs of the closest-point stage (snapshots: the caller may advance q or move
     the obstacles in place afterwards) and, once somebody asks for them, its output arrays."""
 
-    def __init__(self, core, eng, q, single, prim, lc, n_leaves, primitive=None, self_counts=None, hulls=None):
+    def __init__(self, core, eng, q, single, prim, lc, n_leaves, primitive=None, self_counts=None, hulls=None, self_hulls=None):
         self.core, self.eng, self.single, self.n_leaves = core, eng, single, n_leaves
         self.hulls = hulls                # urdf.link_hulls (update_distances(link_hulls=)), None = capsules / frame origins
+        self.self_hulls = self_hulls      # urdf.self_collision_hulls (update_distances(self_hulls=)): self AND obstacle pairs on hulls
         self.self_counts = self_counts    # self pairs per leaf (update_distances(self_collision=True)), None = off
         self.primitive = primitive    # None (by record size) | "cylinder"
         # "the q the stage was given, unmodified": the tensor OBJECT (holding it pins its storage: the allocator cannot hand the
@@ -97,14 +98,22 @@ class _StageSource:
     def arrays(self):
         if self._arrays is None:
             table = self.eng.obstacles(spheres=self.prim, primitive=self.primitive)
-            if self.hulls is not None:        # the hull stage (rmp2_closest_points_hulls)
+            if self.self_hulls is not None:   # the obstacle half on the leaves' hulls (rmp2_closest_points_hulls), bit for bit
+                if self.K > 0:                # (on a second handle that keeps them: this one keeps its hull self list)
+                    aux = self.core._leaf_hull_engine(self.eng, self.self_hulls)
+                    pl, po, _ = aux.closest_points_hulls(self.q, aux.obstacles(spheres=self.prim, primitive=self.primitive))
+                else:
+                    pl = po = torch.empty((self.q.shape[0], 0, 3), dtype=torch.float32, device=self.eng.device)
+            elif self.hulls is not None:      # the hull stage (rmp2_closest_points_hulls)
                 self.eng.set_self_collision([], None)
                 self.eng.set_link_hulls(self.hulls)
                 pl, po, _ = self.eng.closest_points_hulls(self.q, table)
             else:
                 pl, po = self.eng.closest_points(self.q, table, link_capsules=self.lc)
             if self.self_counts is not None:   # each leaf's range: its K obstacle pairs, then its self pairs (rmp2_step's layout)
-                self.eng.set_self_collision(*self.core._self_collision_list(self.eng))
+                if self.self_hulls is not None:
+                    self.eng.set_link_hulls(None)
+                self.core._set_self(self.eng, self.self_hulls)
                 spl, spo, _ = self.eng.self_pairs(self.q)
                 K, so = self.K, [sum(self.self_counts[:i]) for i in range(self.n_leaves + 1)]
                 pl = torch.cat([t for i in range(self.n_leaves) for t in (pl[:, i * K:(i + 1) * K], spl[:, so[i]:so[i + 1]])], 1)
@@ -242,7 +251,30 @@ class RmpCore:
             self._self_key = key
         return self._self_list
 
-    def update_distances(self, q, primitives, link_capsules=None, primitive=None, self_collision=False, link_hulls=None):
+    def _leaf_hull_engine(self, eng, self_hulls):
+        """A second handle on `eng`'s descriptor and device whose link hulls are the pair leaves' rows of `self_hulls`: the
+        explicit route forms the obstacle half there, so `eng` keeps its hull self list (no re-upload per read).  Kept per
+        engine; set_link_hulls skips the upload while the hulls are the same."""
+        from .engine import Engine
+        cache = self.__dict__.setdefault("_leaf_hull_engines", {})
+        aux = cache.get(id(eng))
+        if aux is None or aux[0] is not eng:
+            aux = (eng, Engine(eng.desc, eng.device))
+            cache[id(eng)] = aux
+        frames = [eng.desc.leaves[i].frame for i in eng._dist_leaves]
+        aux[1].set_link_hulls(self_hulls.subset(frames))
+        return aux[1]
+
+    def _set_self(self, eng, self_hulls=None):
+        """Put this core's self-avoidance list on the engine: on the capsules, or on `self_hulls` (urdf.self_collision_hulls)."""
+        pairs, caps = self._self_collision_list(eng)
+        if self_hulls is None:
+            eng.set_self_collision(pairs, caps)
+        else:
+            eng.set_self_collision_hulls(pairs, self_hulls)
+
+    def update_distances(self, q, primitives, link_capsules=None, primitive=None, self_collision=False, link_hulls=None,
+                         self_hulls=None):
         """The closest-point preprocessing stage on the device (simulation.py:462-484 calculate_distances followed by
         data_management.py:16-31 update): for every TaskmapJointFrame4x4ToDistance leaf and every obstacle primitive
         ([K,4] spheres or [K,8] capsules) the nearest points of the link (its capsule from `link_capsules`, rows in leaf order;
@@ -261,7 +293,10 @@ class RmpCore:
         link_hulls=urdf.link_hulls(...) (one hull per distance leaf, leaf order): the link is its convex hull instead of a capsule
         (include/rmp2.h rmp2_set_link_hulls) -- the nearest points of hull and sphere / capsule primitive; the fused route then
         hands the primitives and the hulls to the step, which runs the hull stage itself.  Not with link_capsules or
-        self_collision."""
+        self_collision.
+        self_hulls=urdf.self_collision_hulls(...) (n_frames + 1 entries): self collision on the hulls, hull against hull, and the
+        obstacle pairs on the same leaf hulls (include/rmp2.h rmp2_set_self_collision_hulls) -- the reference's full distance
+        state.  Implies self_collision; not with link_capsules or link_hulls."""
         single = q.dim() == 1 if isinstance(q, torch.Tensor) else np.ndim(q) == 1
         eng = self.engine_for(q)
         qt = as_tensor(q, eng.device)
@@ -274,6 +309,12 @@ class RmpCore:
             raise NotImplementedError("mixing explicit-pair and sphere distance task maps in one core")
         if len(dist_idx) != len(eng._dist_leaves):
             raise NotImplementedError("update_distances: attached-point leaves (TaskmapRelative4x4) carry their own pair data")
+        if self_hulls is not None and (link_capsules is not None or link_hulls is not None):
+            raise ValueError("update_distances: self_hulls forms the obstacle pairs on the same hulls: not with link_capsules or "
+                             "link_hulls")
+        if self_hulls is not None and primitive == "cylinder":
+            raise NotImplementedError("update_distances: self_hulls take sphere or capsule primitives, not cylinders")
+        self_collision = self_collision or self_hulls is not None
         if link_hulls is not None and (link_capsules is not None or self_collision):
             raise ValueError("update_distances: link_hulls replaces link_capsules and does not combine with self_collision")
         if link_hulls is not None and primitive == "cylinder":
@@ -283,9 +324,9 @@ class RmpCore:
         if link_hulls is None:
             eng.set_link_hulls(None)
         if self_collision:
-            eng.set_self_collision(*self._self_collision_list(eng))
+            self._set_self(eng, self_hulls)
         src = _StageSource(self, eng, qt, single, prim, lc, len(leaves), primitive=primitive,
-                           self_counts=eng.self_counts if self_collision else None, hulls=link_hulls)
+                           self_counts=eng.self_counts if self_collision else None, hulls=link_hulls, self_hulls=self_hulls)
         self._stage = src
         names = self._table.frame_names
         frames = []
@@ -317,6 +358,11 @@ class RmpCore:
             eng.set_link_hulls(src.hulls)
             return eng.obstacles(spheres=src.prim, primitive=src.primitive)
         eng.set_link_hulls(None)
+        if src.self_hulls is not None:    # the step forms both halves on the hulls itself: the engine carries the hull list
+            self._set_self(eng, src.self_hulls)
+            if src.K == 0:
+                return eng.obstacles()
+            return eng.obstacles(spheres=src.prim, primitive=src.primitive)
         if src.self_counts is not None:   # the step forms the self pairs itself: the engine carries the list
             eng.set_self_collision(*self._self_collision_list(eng))
             if src.K == 0:

@@ -474,6 +474,16 @@ class LinkHulls:
         """(vertices [n, 3], planes [m, 4]) of hull i."""
         return (self.verts[self.vert_offset[i]:self.vert_offset[i + 1]], self.planes[self.face_offset[i]:self.face_offset[i + 1]])
 
+    def subset(self, entries: Sequence[int]) -> "LinkHulls":
+        """The hulls `entries` (in that order) packed on their own: self_collision_hulls(...).subset(leaf frames) are the
+        pair leaves' hulls, bit for bit those link_hulls builds."""
+        V = [self.hull(int(e))[0] for e in entries]
+        P = [self.hull(int(e))[1] for e in entries]
+        vo = np.concatenate([[0], np.cumsum([len(v) for v in V])]).astype(np.int32)
+        fo = np.concatenate([[0], np.cumsum([len(p) for p in P])]).astype(np.int32)
+        return LinkHulls(vo, np.ascontiguousarray(np.concatenate(V) if V else np.zeros((0, 3)), dtype=np.float32).reshape(-1, 3),
+                         fo, np.ascontiguousarray(np.concatenate(P) if P else np.zeros((0, 4)), dtype=np.float32).reshape(-1, 4))
+
 
 def convex_hull(points: np.ndarray):
     """(vertices [n, 3] float64, planes [m, 4] float64) of the convex hull of `points` [k, 3]: the hull's vertices (a subset of
@@ -490,6 +500,44 @@ def convex_hull(points: np.ndarray):
     return verts, np.asarray(keep, dtype=np.float64)
 
 
+def _link_hull(link: str, meshes: dict, what: str):
+    """(vertices, planes) float64 of `link`'s convex hull in the coordinates its entry of `meshes` is placed in (link_hulls)."""
+    if link not in meshes:
+        raise ValueError(f"{what}: no collision mesh for link {link!r}: pass its vertex set in `meshes`")
+    m = meshes[link]
+    if isinstance(m, (tuple, list)):
+        verts, xyz, rpy = m
+        Rc = rotation_from_rpy_reference_order(rpy).astype(np.float64)
+        pts = np.asarray(verts, dtype=np.float64) @ Rc.T + np.asarray(xyz, dtype=np.float64)
+    else:
+        pts = np.asarray(m, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or len(pts) < 4:
+        raise ValueError(f"{what}: link {link!r} needs at least 4 vertices [n, 3]")
+    hv, hp = convex_hull(pts)
+    if len(hv) > MAX_HULL_VERTICES or len(hp) > MAX_HULL_FACES:
+        raise ValueError(f"{what}: the hull of {link!r} has {len(hv)} vertices / {len(hp)} faces (at most "
+                         f"{MAX_HULL_VERTICES} / {MAX_HULL_FACES})")
+    return hv, hp
+
+
+def self_collision_hulls(urdf_filepath: str, table: KinematicTable, meshes: dict) -> LinkHulls:
+    """Hulls [n_frames + 1] for rmp2_set_self_collision_hulls, laid out as self_collision_capsules: entry f is frame f's link in
+    FRAME coordinates, built exactly as link_hulls builds it (so the pair leaves' entries are bit for bit link_hulls(table,
+    leaf frames, meshes)); the last entry is the base link (base_link_name) in base coordinates.  Frames without a collision
+    shape get an empty entry (self_collision_pairs never pairs them); a collision frame whose link has no mesh is an error."""
+    F = table.n_frames
+    links = [table.link_names[f] if table.has_collision[f] else None for f in range(F)] + [base_link_name(urdf_filepath, table)]
+    vo, fo, V, P = [0], [0], [], []
+    for link in links:
+        hv, hp = (np.zeros((0, 3)), np.zeros((0, 4))) if link is None else _link_hull(link, meshes, "self_collision_hulls")
+        V.append(hv)
+        P.append(hp)
+        vo.append(vo[-1] + len(hv))
+        fo.append(fo[-1] + len(hp))
+    return LinkHulls(np.asarray(vo, np.int32), np.ascontiguousarray(np.concatenate(V), dtype=np.float32).reshape(-1, 3),
+                     np.asarray(fo, np.int32), np.ascontiguousarray(np.concatenate(P), dtype=np.float32).reshape(-1, 4))
+
+
 def link_hulls(table: KinematicTable, frames: Sequence[str], meshes: dict) -> LinkHulls:
     """One convex hull per pair leaf (`frames` in leaf order, as link_capsules takes them), in that leaf's FRAME coordinates:
     the mesh vertices of the frame's link placed by its collision origin (rotation_from_rpy_reference_order, as the fitted
@@ -501,19 +549,7 @@ def link_hulls(table: KinematicTable, frames: Sequence[str], meshes: dict) -> Li
         link = table.link_names[table.frame_index(fr)]
         if link not in meshes:
             raise ValueError(f"link_hulls: no collision mesh for link {link!r} (frame {fr!r}): pass its vertex set in `meshes`")
-        m = meshes[link]
-        if isinstance(m, (tuple, list)):
-            verts, xyz, rpy = m
-            Rc = rotation_from_rpy_reference_order(rpy).astype(np.float64)
-            pts = np.asarray(verts, dtype=np.float64) @ Rc.T + np.asarray(xyz, dtype=np.float64)
-        else:
-            pts = np.asarray(m, dtype=np.float64)
-        if pts.ndim != 2 or pts.shape[1] != 3 or len(pts) < 4:
-            raise ValueError(f"link_hulls: link {link!r} needs at least 4 vertices [n, 3]")
-        hv, hp = convex_hull(pts)
-        if len(hv) > MAX_HULL_VERTICES or len(hp) > MAX_HULL_FACES:
-            raise ValueError(f"link_hulls: the hull of {link!r} has {len(hv)} vertices / {len(hp)} faces (at most "
-                             f"{MAX_HULL_VERTICES} / {MAX_HULL_FACES})")
+        hv, hp = _link_hull(link, meshes, "link_hulls")
         V.append(hv)
         P.append(hp)
         vo.append(vo[-1] + len(hv))

@@ -12,7 +12,7 @@ for b in blocks:
     except Exception:
         pass
     g = lambda k: (re.search(k + r": (\d+)", b) or [None, "?"])[1]
-    rows.append((name, g("VGPRs"), g("AGPRs"), g("SGPRs"), g("ScratchSize \[bytes/lane\]"), g("VGPR Spill"), g("SGPR Spill"), g("Occupancy \[waves/SIMD\]"), g("LDS Size \[bytes/block\]")))
+    rows.append((name, g("VGPRs"), g("AGPRs"), g("SGPRs"), g("ScratchSize \[bytes/lane\]"), g("VGPRs? Spill"), g("SGPRs? Spill"), g("Occupancy \[waves/SIMD\]"), g("LDS Size \[bytes/block\]")))
 print(f"{'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'scr':>6} {'vspill':>6} {'sspill':>6} {'occ':>4}  kernel")
 for r in rows:
     if flt in r[0]:
