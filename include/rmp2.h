@@ -531,6 +531,37 @@ int rmp2_closest_points_hulls(rmp2_handle *h, const float *q, const rmp2_obstacl
 int rmp2_set_self_collision_hulls(rmp2_handle *h, int32_t n_pairs, const int32_t *pairs, int32_t n_hulls, const int32_t *vert_offset,
                                   const float *verts, const int32_t *face_offset, const float *planes);
 
+/* ---- inverse dynamics: the joint torques that realise the policy's q'' ----------------------------------------------------
+ * The reference drives its robot in TORQUE_CONTROL with p.calculateInverseDynamics(q, qd, qdd) of the policy's q''
+ * (simulation.py:369-386).  rmp2_inverse_dynamics gives, per robot, the generalised forces tau at which the fixed-base tree reaches
+ * the accelerations qdd at the state (q, qd) under gravity g:
+ *   tau = M(q) qdd + C(q, qd) qd + G(q),
+ * the rigid-body model of the inertial table (no joint damping or friction, no limits, no rotor inertia).  tau_j is the torque
+ * about the joint axis z_j of a revolute joint, the force along z_j of a prismatic one.  tau[R][n_dof] is in the caller's q order;
+ * fixed joints have no entry; a movable joint missing from the joint order (q_index = -1) is held at q = qd = qdd = 0 and has no
+ * entry, as in the FK.  The fixed base link's own inertia plays no part.  The robots stand at the base-frame origin; g is given
+ * in the base frame.
+ *
+ * rmp2_set_inertials: copy the inertial table into the handle.  inertials: host [n_frames][10], frame f's record describing the
+ * link that moves with frame f (the joint's child link) in FRAME coordinates: (m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz), c the
+ * centre of mass and the tensor taken about c in frame axes (the URDF's ixy etc. as matrix entries; urdf.inertial_table builds
+ * it from the <inertial> elements).  gravity: host [3], or NULL for (0, 0, -9.81) (p.setGravity, simulation.py:329).  Synchronous.
+ * n_frames == 0 switches the feature off.  RMP2_ERR_INVALID_ARGUMENT, naming the frame: a frame count other than the robot's, a
+ * non-finite value, m < 0, a negative diagonal moment; also a non-finite gravity.
+ *
+ * rmp2_inverse_dynamics: q, qd, qdd device [R][n_dof], tau device [R][n_dof]; stream-ordered, no host synchronisation and no
+ * allocation (it can be captured in a graph).  R == 0 is a no-op.  Refused (RMP2_ERR_INVALID_ARGUMENT) without inertials.
+ * Inputs and tau are fp32; a NaN or Inf in a robot's q, qd or qdd gives a non-finite tau for that robot and leaves the others
+ * unaffected.  One forward walk per robot over every frame (csrc/rmp2_dynamics.h); rmp2_step, rmp2_forward_kinematics and
+ * rmp2_rollout are untouched by the table.
+ *
+ * Where this departs from PyBullet: the reference loads its URDFs without URDF_USE_INERTIA_FROM_FILE, and PyBullet then replaces
+ * the file's inertia tensors by an approximation from the collision shape; the engine uses the table the caller gives (urdf
+ * builds it from the file).  Parity with the reference's torques is UNPINNED: no PyBullet result backs these numbers; the tests
+ * pin them against two independent fp64 derivations (Newton-Euler and Lagrangian). */
+int rmp2_set_inertials(rmp2_handle *h, int32_t n_frames, const float *inertials, const float *gravity);
+int rmp2_inverse_dynamics(rmp2_handle *h, const float *q, const float *qd, const float *qdd, float *tau, int32_t R, void *stream);
+
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,
  * plain steps on shared or ragged sphere tables, both fleets beyond 8 192 robots -- the two steps are ONE grid (the first

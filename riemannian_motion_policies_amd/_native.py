@@ -78,6 +78,8 @@ def lib():
                                                 C.c_void_p]
     l.rmp2_closest_points_hulls.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(D.Obstacles), C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int32, C.c_void_p]
+    l.rmp2_set_inertials.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    l.rmp2_inverse_dynamics.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_differentiate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_differentiate_euler.argtypes = l.rmp2_differentiate.argtypes

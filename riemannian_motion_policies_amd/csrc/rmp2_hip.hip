@@ -26,6 +26,7 @@
 
 #include "rmp2_host.h"
 #include "rmp2_hull.h"
+#include "rmp2_dynamics.h"
 
 using namespace rmp2;
 
@@ -2191,6 +2192,50 @@ int dispatch_solve(const rmp2_handle* h, const float* q, const float* qd, const 
 }  // namespace
 
 // =========================================================================================
+// device: inverse dynamics (rmp2_inverse_dynamics; the walk is rmp2_dynamics.h inverse_dynamics_robot)
+// =========================================================================================
+namespace {
+
+// One lane per robot over the UNPRUNED program (the step's pruned program drops frames without a leaf, which still carry mass);
+// the ops and the inertial records are read at wave-uniform addresses.  N: the handle's template size (dofs), SLOTS: the save
+// slots of the unpruned program.
+template <int N, int SLOTS>
+__global__ void __launch_bounds__(kWave)
+rmp2_inverse_dynamics_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay, float az,
+                             const float* __restrict__ q, const float* __restrict__ qd, const float* __restrict__ qdd,
+                             float* __restrict__ tau, int R) {
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const float base_acc[3] = {ax, ay, az};
+  inverse_dynamics_robot<N, SLOTS>(prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, qdd + row, tau + row);
+}
+
+template <int N>
+void launch_inverse_dynamics(const rmp2_handle* h, const float* q, const float* qd, const float* qdd, float* tau, int R,
+                             hipStream_t s) {
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  switch (h->n_slots_full) {
+    case 0:
+      hipLaunchKernelGGL((rmp2_inverse_dynamics_kernel<N, 0>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd,
+                         qdd, tau, R);
+      break;
+    case 1:
+      hipLaunchKernelGGL((rmp2_inverse_dynamics_kernel<N, 1>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd,
+                         qdd, tau, R);
+      break;
+    default:
+      hipLaunchKernelGGL((rmp2_inverse_dynamics_kernel<N, 2>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd,
+                         qdd, tau, R);
+      break;
+  }
+}
+
+}  // namespace
+
+// =========================================================================================
 // C ABI
 // =========================================================================================
 extern "C" {
@@ -2477,6 +2522,7 @@ int rmp2_destroy(rmp2_handle* h) {
   if (h->d_shull_obs) (void)hipFree(h->d_shull_obs);
   if (h->d_shull_verts) (void)hipFree(h->d_shull_verts);
   if (h->d_shull_planes) (void)hipFree(h->d_shull_planes);
+  if (h->d_inert) (void)hipFree(h->d_inert);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
   return RMP2_OK;
@@ -3739,6 +3785,62 @@ int rmp2_differentiate(rmp2_handle* h, const float* q, const float* qd, int32_t 
 int rmp2_differentiate_euler(rmp2_handle* h, const float* q, const float* qd, int32_t frame, float* x, float* xd,
                              float* J, float* c, int32_t R, void* stream) {
   return differentiate_impl(h, q, qd, frame, x, xd, J, c, R, stream, 1);
+}
+
+int rmp2_set_inertials(rmp2_handle* h, int32_t n_frames, const float* inertials, const float* gravity) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (n_frames < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inertials: n_frames < 0");
+  if (n_frames == 0) {   // off: rmp2_inverse_dynamics is refused again
+    h->inert_n = 0;
+    return RMP2_OK;
+  }
+  if (n_frames != h->n_frames)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inertials: one record per frame (" + std::to_string(h->n_frames) + "), got " +
+                                                  std::to_string(n_frames));
+  if (!inertials) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inertials: null array");
+  float acc[3] = {0.f, 0.f, 9.81f};
+  if (gravity) {
+    for (int k = 0; k < 3; ++k) {
+      if (!std::isfinite(gravity[k])) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inertials: gravity is not finite");
+      acc[k] = -gravity[k];
+    }
+  }
+  static const char* const kField[kInertialFloats] = {"m", "cx", "cy", "cz", "Ixx", "Iyy", "Izz", "Ixy", "Ixz", "Iyz"};
+  for (int f = 0; f < n_frames; ++f) {
+    const float* r = inertials + (size_t)f * kInertialFloats;
+    for (int k = 0; k < kInertialFloats; ++k)
+      if (!std::isfinite(r[k]))
+        return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inertials: frame " + std::to_string(f) + ": " + kField[k] + " is not finite");
+    if (r[0] < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inertials: frame " + std::to_string(f) + ": mass < 0");
+    for (int k = 4; k < 7; ++k)
+      if (r[k] < 0.f)
+        return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inertials: frame " + std::to_string(f) + ": " + kField[k] + " < 0");
+  }
+  if (int rc = use_device(h)) return rc;
+  if (!h->d_inert) HIP_TRY(h, hipMalloc(&h->d_inert, sizeof(float) * kInertialFloats * RMP2_MAX_FRAMES));
+  // (a synchronous copy: no launch still reads the old table)
+  HIP_TRY(h, hipMemcpy(h->d_inert, inertials, sizeof(float) * kInertialFloats * n_frames, hipMemcpyHostToDevice));
+  for (int k = 0; k < 3; ++k) h->base_acc[k] = acc[k];
+  h->inert_n = n_frames;
+  return RMP2_OK;
+}
+
+int rmp2_inverse_dynamics(rmp2_handle* h, const float* q, const float* qd, const float* qdd, float* tau, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (R < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inverse dynamics: R < 0");
+  if (h->inert_n == 0)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inverse dynamics: no inertial table on this handle (call rmp2_set_inertials first)");
+  if (R == 0) return RMP2_OK;
+  if (!q || !qd || !qdd || !tau) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "inverse dynamics: null array");
+  if (int rc = use_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  switch (h->n_template) {
+    case 2: launch_inverse_dynamics<2>(h, q, qd, qdd, tau, R, s); break;
+    case 9: launch_inverse_dynamics<9>(h, q, qd, qdd, tau, R, s); break;
+    default: launch_inverse_dynamics<16>(h, q, qd, qdd, tau, R, s); break;
+  }
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
 }
 
 }  // extern "C"

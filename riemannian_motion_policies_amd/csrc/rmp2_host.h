@@ -90,6 +90,10 @@ struct rmp2_handle {
   float4* d_shull_verts = nullptr;      // the pair leaves' hulls first (ordinal order), then the other entries
   float4* d_shull_planes = nullptr;
   size_t shull_verts_cap = 0, shull_planes_cap = 0;
+  // inverse dynamics (rmp2_set_inertials): off while inert_n == 0
+  int inert_n = 0;
+  float* d_inert = nullptr;             // [n_frames][10] inertial records
+  float base_acc[3] = {0.f, 0.f, 9.81f};  // -g
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
   mutable const char* last_kernel = "none";  // mapping the last control step / rollout was launched with (rmp2_last_kernel)
   std::string error;

@@ -51,6 +51,7 @@ class Engine:
         self._dist_leaves = D.distance_leaf_indices(desc)
         self._self_counts = None   # self pairs per pair leaf (set_self_collision), None = off
         self._hulls_key = None     # the link hulls the handle holds (set_link_hulls), None = off
+        self._inertials_key = None  # the inertial table and gravity the handle holds (set_inertials), None = off
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -477,6 +478,49 @@ class Engine:
         _native.check(self._lib.rmp2_self_pairs(self._h, q.data_ptr(), p_link.data_ptr(), p_obs.data_ptr(), dist.data_ptr(), R, s),
                       self._h)
         return p_link, p_obs, dist
+
+    def set_inertials(self, table, gravity=(0.0, 0.0, -9.81)) -> None:
+        """Inverse dynamics' rigid-body model (include/rmp2.h rmp2_set_inertials): `table` [n_frames, 10] = urdf.inertial_table
+        (frame f's child link in frame coordinates: m, centre of mass, tensor about it), `gravity` in the base frame.  None turns
+        the feature off.  The same table and gravity again upload nothing."""
+        if table is None:
+            if self._inertials_key is not None:
+                _native.check(self._lib.rmp2_set_inertials(self._h, 0, None, None), self._h)
+            self._inertials_key = None
+            return
+        t = np.ascontiguousarray(table.detach().cpu() if isinstance(table, torch.Tensor) else table, dtype=np.float32)
+        g = np.ascontiguousarray(gravity, dtype=np.float32)
+        if t.ndim != 2 or t.shape[1] != 10:
+            raise ValueError(f"inertials must be [n_frames, 10], got {list(t.shape)}")
+        if g.shape != (3,):
+            raise ValueError(f"gravity must have 3 entries, got {list(g.shape)}")
+        key = (t.tobytes(), g.tobytes())
+        if key == self._inertials_key:
+            return   # (the same table: nothing to upload)
+        _native.check(self._lib.rmp2_set_inertials(self._h, t.shape[0], t.ctypes.data, g.ctypes.data), self._h)
+        self._inertials_key = key
+
+    @property
+    def has_inertials(self) -> bool:
+        return self._inertials_key is not None
+
+    def inverse_dynamics(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Joint torques tau [R, n] = M(q) qdd + C(q, qd) qd + G(q) (include/rmp2.h rmp2_inverse_dynamics) on the current stream;
+        q, qd, qdd [R, n] on the engine's device.  Needs set_inertials."""
+        q, qd, qdd = _f32(q, self.device), _f32(qd, self.device), _f32(qdd, self.device)
+        if q.dim() != 2 or q.shape[1] != self.n_dof or qd.shape != q.shape or qdd.shape != q.shape:
+            raise ValueError(f"q, qd, qdd must all be [R, {self.n_dof}], got {list(q.shape)}, {list(qd.shape)}, {list(qdd.shape)}")
+        R = q.shape[0]
+        if out is None:
+            out = torch.empty((R, self.n_dof), dtype=torch.float32, device=self.device)
+        else:
+            _require_resident(self.device, out=out)
+            if tuple(out.shape) != (R, self.n_dof):
+                raise ValueError(f"out must be [{R}, {self.n_dof}]")
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        _native.check(self._lib.rmp2_inverse_dynamics(self._h, q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), out.data_ptr(), R, s),
+                      self._h)
+        return out
 
     def differentiate(self, q: torch.Tensor, qd: torch.Tensor, frame: int):
         q, qd = _f32(q, self.device), _f32(qd, self.device)

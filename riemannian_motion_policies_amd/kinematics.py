@@ -13,7 +13,7 @@ import torch
 
 from . import descriptor as D
 from .taskmap import _to_str
-from .urdf import KinematicTable, compile_urdf
+from .urdf import KinematicTable, compile_urdf, inertial_table, read_inertials
 
 
 class HostTensor(np.ndarray):
@@ -139,6 +139,7 @@ class UrdfForwardKinematic:
         self.frame_names = list(self.table.frame_names)
         self.device = device
         self._engine = None
+        self._inertials = None   # read_inertials(urdf_filepath), on first use
 
     def _fk_engine(self):
         if self._engine is None:
@@ -175,3 +176,30 @@ class UrdfForwardKinematic:
         qd2 = np.atleast_2d(np.asarray(qd, dtype=np.float32)) if as_np else qd
         out = self._fk_engine().differentiate_euler(q2, qd2, self.table.frame_index(_to_str(frame)))
         return tuple(o.cpu().numpy() for o in out) if as_np else out
+
+    def inverse_dynamics(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), inertials=None):
+        """Joint torques tau = M(q) qdd + C(q, qd) qd + G(q) of the robot for the accelerations qdd (what the reference's
+        simulation.step asks p.calculateInverseDynamics for, simulation.py:369-386), on the GPU (rmp2_inverse_dynamics).
+        q, qd, qdd [n] or [R, n]; host inputs give host outputs, CUDA tensors give a CUDA tensor.  `inertials`: a dict as
+        urdf.read_inertials returns it, or an [n_frames, 10] table (urdf.inertial_table); by default the <inertial> elements of
+        this object's URDF (an error when it has none).  `gravity` in the base frame."""
+        if inertials is None:
+            if self._inertials is None:
+                self._inertials = read_inertials(self.filepath)
+            if not self._inertials:
+                raise ValueError(f"{self.filepath}: the URDF has no <inertial> elements; pass inertials= (urdf.read_inertials of a "
+                                 "URDF that has them, or an [n_frames, 10] table)")
+            inertials = self._inertials
+        table = inertial_table(self.table, inertials) if isinstance(inertials, dict) else inertials
+        eng = self._fk_engine()
+        eng.set_inertials(table, gravity)
+        as_np = not isinstance(q, torch.Tensor)
+        one = (np.ndim(q) if as_np else q.dim()) == 1
+        if as_np:
+            q2, qd2, qdd2 = (np.atleast_2d(np.asarray(x, dtype=np.float32)) for x in (q, qd, qdd))
+        else:
+            q2, qd2, qdd2 = (x.reshape(1, -1) if one else x for x in (q, qd, qdd))
+        tau = eng.inverse_dynamics(q2, qd2, qdd2)
+        if one:
+            tau = tau[0]
+        return tau.cpu().numpy() if as_np else tau

@@ -558,6 +558,54 @@ def link_hulls(table: KinematicTable, frames: Sequence[str], meshes: dict) -> Li
                      np.asarray(fo, np.int32), np.ascontiguousarray(np.concatenate(P), dtype=np.float32).reshape(-1, 4))
 
 
+# ---- inertial data (rmp2_set_inertials: the rigid-body model of the inverse dynamics, simulation.py:369-386) -----------------
+
+INERTIAL_FLOATS = 10   # (m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz): include/rmp2.h rmp2_set_inertials
+
+
+def read_inertials(urdf_filepath: str) -> dict:
+    """{link name: (mass, xyz [3], rpy [3], inertia6 [6])} of every link with an <inertial> element: the mass, the inertial origin
+    (the centre of mass and the axes the tensor is written in, in link coordinates; 0 where absent) and the tensor as written,
+    inertia6 = (ixx, iyy, izz, ixy, ixz, iyz).  A link without <inertial> is massless (the URDF default) and has no entry.  The
+    package's kinematics-only URDFs carry no inertials (an empty dict)."""
+    root = ElementTree.parse(urdf_filepath).getroot()
+    out = {}
+    for link in root.findall("link"):
+        inr = link.find("inertial")
+        if inr is None:
+            continue
+        origin = inr.find("origin")
+        mass = inr.find("mass")
+        ten = inr.find("inertia")
+        i6 = [float(ten.attrib.get(k, "0")) if ten is not None else 0.0 for k in ("ixx", "iyy", "izz", "ixy", "ixz", "iyz")]
+        out[link.attrib["name"]] = (float(mass.attrib["value"]) if mass is not None else 0.0,
+                                    np.asarray(_floats(origin.attrib.get("xyz") if origin is not None else None), dtype=np.float64),
+                                    np.asarray(_floats(origin.attrib.get("rpy") if origin is not None else None), dtype=np.float64),
+                                    np.asarray(i6, dtype=np.float64))
+    return out
+
+
+def inertial_table(table: KinematicTable, inertials: dict) -> np.ndarray:
+    """float32 [n_frames, 10] for rmp2_set_inertials: frame f's record describes its child link (table.link_names[f]) in FRAME
+    coordinates, (m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz) -- c the centre of mass, the tensor about c in frame axes.
+    `inertials` is read_inertials(urdf) (or a dict of the same shape): the tensor is rotated from the inertial origin's axes into
+    the frame's, I = R I_origin R^T with R = rotation_from_rpy_reference_order(rpy) -- the convention of the collision origins in
+    link_hulls.  The reference's URDFs all have zero inertial rpy, so nothing the reference runs tells that order from the URDF
+    standard's apart.  A frame whose link has no entry is massless; the fixed base link's entry plays no part."""
+    out = np.zeros((table.n_frames, INERTIAL_FLOATS), dtype=np.float32)
+    for f, link in enumerate(table.link_names):
+        if link not in inertials:
+            continue
+        m, xyz, rpy, i6 = inertials[link]
+        ixx, iyy, izz, ixy, ixz, iyz = (float(v) for v in i6)
+        I = np.array([[ixx, ixy, ixz], [ixy, iyy, iyz], [ixz, iyz, izz]], dtype=np.float64)
+        Rm = rotation_from_rpy_reference_order(rpy).astype(np.float64)
+        I = Rm @ I @ Rm.T
+        c = np.asarray(xyz, dtype=np.float64)
+        out[f] = [float(m), c[0], c[1], c[2], I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]]
+    return out
+
+
 def panda_table() -> KinematicTable:
     return compile_urdf(PANDA_URDF, PANDA_ORDER)
 
