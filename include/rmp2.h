@@ -199,12 +199,16 @@ typedef struct rmp2_obstacles {
                                               most 9 dofs and an inertia leaf, solve = AUTO or a certifying PINV, and 2-dof robots
                                               with either resolve (their closed-form 2 x 2 resolve is the pseudo-inverse) -- shared
                                               tables, ragged lists, rollouts; a plain step beyond those limits -- more dofs, the
-                                              all-Jacobi PINV, bigger tables, CYLINDER tables -- runs as the stage into a buffer of
-                                              the handle followed by the explicit-pair step (two launches, same numbers as calling
-                                              the two entry points).  RAGGED lists take that route with one more launch (one pair per
-                                              list entry, a repeated index counted twice as in the fused form, filler pairs 1e9 m
-                                              away up to the fleet's longest list); the list lengths are read back from csr_offset,
-                                              so that form synchronises the stream and is refused inside a stream capture.
+                                              all-Jacobi PINV, bigger tables, CYLINDER tables -- runs as the stage into the
+                                              handle's stage buffer followed by the explicit-pair step (two launches, same numbers as
+                                              calling the two entry points).  RAGGED lists take that route with one more launch (one
+                                              pair per list entry, a repeated index counted twice as in the fused form, filler pairs
+                                              1e9 m away up to the fleet's longest list); the list lengths are read back from
+                                              csr_offset, so that form synchronises the stream and is refused inside a stream capture.
+                                              The stage buffer holds 24 n_dist K (+ 24 n_dist L over ragged lists) bytes per robot,
+                                              grown on demand like the other staged routes' (see rmp2_set_self_collision): refused
+                                              with RMP2_ERR_UNSUPPORTED and the byte count beyond the free device memory, and inside a
+                                              stream capture.
                                               Rollouts beyond the fused limits, and sets with attached-point leaves over ragged
                                               lists: RMP2_ERR_UNSUPPORTED. */
 } rmp2_obstacles;
@@ -448,10 +452,12 @@ int rmp2_closest_points_links(rmp2_handle *h, const float *q, const rmp2_obstacl
  * rmp2_step on a handle with self collision: the stage, then the explicit-pair step (two launches).  Obstacle input NONE, or
  * SHARED_SPHERES with sphere or capsule records (with or without link_capsules) on sets without attached-point leaves: leaf l's
  * range is then [K obstacle pairs | S_l self pairs], the obstacle half bit-identical to rmp2_closest_points_links on the same
- * inputs (its default wave form).  Memory: a buffer of the handle of 24 P (+ 4 P with attached-point leaves) bytes per robot,
- * P = sum over the pair leaves of (K + S_l) -- config 3 with 32 spheres and 44 self pairs: 7 200 B per robot, 472 MB at 65 536
- * robots.  Grown on demand (refused with the byte count when it exceeds the free device memory, and inside a stream capture:
- * step once outside it first).  RMP2_ERR_UNSUPPORTED, with a message naming the combination: RAGGED_SPHERES lists, CYLINDER
+ * inputs (its default wave form).  Memory: the handle's stage buffer, here 24 P (+ 4 P with attached-point leaves) bytes per
+ * robot, P = sum over the pair leaves of (K + S_l) -- config 3 with 32 spheres and 44 self pairs: 7 200 B per robot, 472 MB at
+ * 65 536 robots.  A handle has ONE stage buffer, shared by its staged routes (self collision, link hulls, link_capsules beyond the
+ * fused limits: at most one runs per step); its size depends on the route in use.  It grows on demand to the largest need seen
+ * (refused with the byte count when it exceeds the free device memory, and inside a stream capture: step once outside it first),
+ * so a graph captured on a staged step stays valid only until the buffer grows -- on this route or another.  RMP2_ERR_UNSUPPORTED, with a message naming the combination: RAGGED_SPHERES lists, CYLINDER
  * tables, caller-supplied EXPLICIT_PAIRS, a table with attached-point leaves, rmp2_rollout, rmp2_step_pair and
  * rmp2_exchange_step.  Out of scope: those forms, a symmetric (two-body) self-pair Jacobian, mesh-exact distances (capsules
  * stand in, as for obstacles). */
@@ -490,9 +496,11 @@ int rmp2_self_pairs(rmp2_handle *h, const float *q, float *p_link, float *p_obs,
  * else it may be NULL).  The device iteration is bounded: at most 32 GJK steps per pair (fp64), one pass over the planes.
  *
  * rmp2_step on a handle with hulls and a SHARED_SPHERES sphere / capsule table: this stage into a buffer of the handle, then the
- * explicit-pair step (two launches; the same numbers as calling the two).  Memory: 24 P (+ 4 P with attached-point leaves)
- * bytes per robot, P = L*K; grown on demand, refused with the byte count beyond the free device memory and inside a stream
- * capture (step once outside it first).  Obstacle input NONE, or an empty table, steps as without hulls.
+ * explicit-pair step (two launches; the same numbers as calling the two).  Memory: the handle's stage buffer (rmp2_set_self_collision),
+ * here 24 P (+ 4 P with attached-point leaves) bytes per robot, P = L*K; grown on demand, refused with the byte count beyond the
+ * free device memory and inside a stream capture (step once outside it first).  The handle keeps one set of hull arrays, for
+ * whichever hull geometry is on: these hulls, or those of rmp2_set_self_collision_hulls.  Obstacle input NONE, or an empty table,
+ * steps as without hulls.
  * RMP2_ERR_UNSUPPORTED, with a message naming the combination: rmp2_rollout, rmp2_step_pair, rmp2_exchange_step, RAGGED_SPHERES
  * lists, CYLINDER tables, caller-supplied EXPLICIT_PAIRS, link_capsules given together with hulls, hulls together with self
  * collision (hull self pairs: rmp2_set_self_collision_hulls).  Out of scope: cylinder obstacles. */
@@ -508,7 +516,8 @@ int rmp2_closest_points_hulls(rmp2_handle *h, const float *q, const rmp2_obstacl
  * n_hulls == n_frames + 1 entries packed as for rmp2_set_link_hulls -- entry f is frame f's link in FRAME coordinates, the last the
  * base link in base coordinates (urdf.self_collision_hulls).  An entry may be empty (no vertices, no planes) only when no pair names
  * its frame as A or B; with an obstacle table every pair leaf needs one.  Limits and argument checks as rmp2_set_link_hulls
- * (RMP2_ERR_INVALID_ARGUMENT naming the limit).  Synchronous.
+ * (RMP2_ERR_INVALID_ARGUMENT naming the limit).  Synchronous.  The hulls go to the handle's one set of hull arrays, which
+ * rmp2_set_link_hulls uses too (the two geometries exclude each other).
  *   n_pairs == 0 (or rmp2_set_self_collision(h, 0, ...)) turns self collision off, either geometry: the handle then steps bit
  *   for bit as a fresh one.  rmp2_set_self_collision with capsules replaces the hulls and this call replaces the capsules.
  *   RMP2_ERR_UNSUPPORTED on a handle with link hulls; rmp2_set_link_hulls is refused on a handle with hull self pairs.

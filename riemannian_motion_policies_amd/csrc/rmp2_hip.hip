@@ -22,6 +22,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rmp2_host.h"
@@ -1679,6 +1680,33 @@ int use_device(rmp2_handle* h) {
   return RMP2_OK;
 }
 
+// True while `s` is being captured into a graph: no allocation, no synchronisation.
+bool capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+}
+
+// A grow-on-demand buffer of the handle: the old allocation freed (hipFree synchronises the device: no launch still reads it),
+// `bytes` allocated in its place.
+template <class T>
+int realloc_device(rmp2_handle* h, T** p, size_t bytes) {
+  if (*p) HIP_TRY(h, hipFree(*p));
+  *p = nullptr;
+  HIP_TRY(h, hipMalloc(p, bytes));
+  return RMP2_OK;
+}
+
+// f(std::integral_constant<int, S>) with S = n, the save slots of a program: the SLOTS argument of a kernel template.  rmp2_create
+// refuses programs with more than 2.
+template <class F>
+auto with_slots(int n, F&& f) {
+  switch (n) {
+    case 0: return f(std::integral_constant<int, 0>());
+    case 1: return f(std::integral_constant<int, 1>());
+    default: return f(std::integral_constant<int, 2>());
+  }
+}
+
 // Structural zeros of the position Jacobian.  The reference differentiates the frame's position through the chain of LOCAL
 // transforms (kinematics.py:243-270): where the origin of frame f lies ON the axis of a revolute ancestor joint j for every q
 // -- joint f's own axis; consecutive joints whose <origin xyz> is 0 (Panda joints 1/2, 5/6); a tool frame straight up the last
@@ -2061,13 +2089,13 @@ void launch_step(const rmp2_handle* h, const float* q, const float* qd, const fl
 template <int N, bool STRICT>
 int dispatch_slots(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs, const ObsArgs& o,
                    const OutArgs& out, int R, hipStream_t s) {
-  switch (h->n_slots) {
-    case 0: launch_step<N, 0, STRICT>(h, q, qd, goal, gs, o, out, R, s); return RMP2_OK;
-    case 1: launch_step<N, 1, STRICT>(h, q, qd, goal, gs, o, out, R, s); return RMP2_OK;
-    case 2: launch_step<N, 2, STRICT>(h, q, qd, goal, gs, o, out, R, s); return RMP2_OK;
-    default: return RMP2_ERR_UNSUPPORTED;
-  }
+  with_slots(h->n_slots, [&](auto S) { launch_step<N, S, STRICT>(h, q, qd, goal, gs, o, out, R, s); });
+  return RMP2_OK;
 }
+
+// the quad mapping's launchers (rmp2_quad_tu.hip), [N == 9][save slots]
+constexpr decltype(&launch_quad_n9_s0) kLaunchQuad[2][3] = {{launch_quad_n2_s0, launch_quad_n2_s1, launch_quad_n2_s2},
+                                                            {launch_quad_n9_s0, launch_quad_n9_s1, launch_quad_n9_s2}};
 
 template <int N>
 int dispatch_solve(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs, const ObsArgs& o,
@@ -2108,22 +2136,14 @@ int dispatch_solve(const rmp2_handle* h, const float* q, const float* qd, const 
       void* const fence = hm->step_fence;
       hm->step_fence = nullptr;        // the completion fence belongs to the LAST kernel of the step
       hm->quad_skip_resolve = true;
-      bool ok = true;
-      switch (h->n_slots) {
-        case 0: launch_quad_n9_s0(h, q, qd, goal, gs, o, o2, ro, R, s); break;
-        case 1: launch_quad_n9_s1(h, q, qd, goal, gs, o, o2, ro, R, s); break;
-        case 2: launch_quad_n9_s2(h, q, qd, goal, gs, o, o2, ro, R, s); break;
-        default: ok = false; break;
-      }
+      with_slots(h->n_slots, [&](auto S) { kLaunchQuad[1][S](h, q, qd, goal, gs, o, o2, ro, R, s); });
       hm->quad_skip_resolve = false;
       hm->step_fence = fence;
-      if (ok) {
-        if (out.M || out.f)
-          hipLaunchKernelGGL(rmp2_system_copy_kernel, dim3((R + kWave - 1) / kWave), dim3(kWave), 0, s, o2.M, o2.f, out.M, out.f, n, R);
-        RMP2_STEP_LAUNCH(h, (rmp2_pinv_kernel<9>), dim3((R + kWave - 1) / kWave), dim3(kWave), 0, s, o2.M, o2.f, out.qdd, out.status, n, R);
-        h->last_kernel = "rmp2_step_quad_kernel up to (M, f) + rmp2_pinv_kernel (one lane per robot, Jacobi pseudo-inverse)";
-        return RMP2_OK;
-      }
+      if (out.M || out.f)
+        hipLaunchKernelGGL(rmp2_system_copy_kernel, dim3((R + kWave - 1) / kWave), dim3(kWave), 0, s, o2.M, o2.f, out.M, out.f, n, R);
+      RMP2_STEP_LAUNCH(h, (rmp2_pinv_kernel<9>), dim3((R + kWave - 1) / kWave), dim3(kWave), 0, s, o2.M, o2.f, out.qdd, out.status, n, R);
+      h->last_kernel = "rmp2_step_quad_kernel up to (M, f) + rmp2_pinv_kernel (one lane per robot, Jacobi pseudo-inverse)";
+      return RMP2_OK;
     }
     return dispatch_slots<N, true>(h, q, qd, goal, gs, o, out, R, s);
   }
@@ -2181,12 +2201,49 @@ int dispatch_solve(const rmp2_handle* h, const float* q, const float* qd, const 
   const bool lane = !rollout && !o.link_caps && (h->kernel_choice == 1 ||
                                  (h->kernel_choice == 0 && !h->has_distance && !h->has_point && !h->strict && R > 49152));
   if (lane) return dispatch_slots<N, false>(h, q, qd, goal, gs, o, out, R, s);
-  switch (h->n_slots) {
-    case 0: (N == 2 ? launch_quad_n2_s0 : launch_quad_n9_s0)(h, q, qd, goal, gs, o, out, ro, R, s); return RMP2_OK;
-    case 1: (N == 2 ? launch_quad_n2_s1 : launch_quad_n9_s1)(h, q, qd, goal, gs, o, out, ro, R, s); return RMP2_OK;
-    case 2: (N == 2 ? launch_quad_n2_s2 : launch_quad_n9_s2)(h, q, qd, goal, gs, o, out, ro, R, s); return RMP2_OK;
-    default: return RMP2_ERR_UNSUPPORTED;
+  with_slots(h->n_slots, [&](auto S) { kLaunchQuad[N == 9][S](h, q, qd, goal, gs, o, out, ro, R, s); });
+  return RMP2_OK;
+}
+
+// Pairs a stage wrote, described as EXPLICIT_PAIRS in `out`: leaves[i] (descriptor indices, ascending) owns the next count(i) pairs,
+// every other leaf none.
+template <class Count>
+void explicit_pairs(const std::vector<int>& leaves, Count count, float* p_link, float* p_obs, float* dist, rmp2_obstacles& out) {
+  std::memset(&out, 0, sizeof(out));
+  out.mode = RMP2_OBS_EXPLICIT_PAIRS;
+  int acc = 0;
+  for (int l = 0, i = 0; l <= RMP2_MAX_LEAVES; ++l) {
+    out.pair_begin[l] = acc;
+    if (i < (int)leaves.size() && leaves[i] == l) acc += (int)count(i++);
   }
+  out.n_pairs = acc;
+  out.p_link = p_link, out.p_obs = p_obs, out.dist = dist;
+}
+
+// The (leaf, B) list of the self-collision setters (include/rmp2.h rmp2_set_self_collision): each leaf a pair leaf, each B a frame or
+// -1 (the base) and not the leaf's own frame, then check(k, ordinal, B) (RMP2_OK or a refusal); B frames grouped by ordinal, in the
+// order given.
+template <class Check>
+int group_self_pairs(rmp2_handle* h, int32_t n_pairs, const int32_t* pairs, std::vector<std::vector<int>>& by_leaf, Check check) {
+  const int F = h->n_frames, L = (int)h->pair_leaves.size();
+  int ord_of_leaf[RMP2_MAX_LEAVES];
+  for (int l = 0; l < RMP2_MAX_LEAVES; ++l) ord_of_leaf[l] = -1;
+  for (int o = 0; o < L; ++o) ord_of_leaf[h->pair_leaves[o]] = o;
+  by_leaf.assign(L, {});
+  for (int k = 0; k < n_pairs; ++k) {
+    const int leaf = pairs[2 * k], b = pairs[2 * k + 1];
+    const int o = (leaf >= 0 && leaf < h->n_leaves) ? ord_of_leaf[leaf] : -1;
+    if (o < 0)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": leaf " + std::to_string(leaf) +
+                                                    " is not a distance or attached-point leaf");
+    if (b < -1 || b >= F)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B " + std::to_string(b) + " out of range");
+    if (b == h->pair_leaf_frame[o])
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B is the leaf's own frame");
+    if (int rc = check(k, o, b)) return rc;
+    by_leaf[o].push_back(b);
+  }
+  return RMP2_OK;
 }
 
 }  // namespace
@@ -2217,20 +2274,10 @@ void launch_inverse_dynamics(const rmp2_handle* h, const float* q, const float* 
                              hipStream_t s) {
   const dim3 grid((R + kWave - 1) / kWave), block(kWave);
   const float* a = h->base_acc;
-  switch (h->n_slots_full) {
-    case 0:
-      hipLaunchKernelGGL((rmp2_inverse_dynamics_kernel<N, 0>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd,
-                         qdd, tau, R);
-      break;
-    case 1:
-      hipLaunchKernelGGL((rmp2_inverse_dynamics_kernel<N, 1>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd,
-                         qdd, tau, R);
-      break;
-    default:
-      hipLaunchKernelGGL((rmp2_inverse_dynamics_kernel<N, 2>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd,
-                         qdd, tau, R);
-      break;
-  }
+  with_slots(h->n_slots_full, [&](auto S) {
+    hipLaunchKernelGGL((rmp2_inverse_dynamics_kernel<N, S>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd,
+                       qdd, tau, R);
+  });
 }
 
 }  // namespace
@@ -2324,6 +2371,22 @@ int rmp2_leaf_evaluate(int device, const rmp2_leaf* leaf, int32_t k, const float
   return RMP2_OK;
 }
 
+// The descriptor checks of rmp2_validate and rmp2_create: the step's pruned program P (and the hex kernel's ops) and the unpruned
+// program Pfull compile, and fit the kernels' limits.
+static int compile_desc(const rmp2_desc& d, DevProgram& P, int& n_slots, DevProgram& Pfull, int& n_slots_full, std::vector<HexOp>& hops) {
+  std::string err;
+  int rc = compile_program(d, P, n_slots, err, /*prune=*/true, &hops);
+  if (rc == RMP2_OK) rc = compile_program(d, Pfull, n_slots_full, err, /*prune=*/false);
+  if (rc != RMP2_OK) return fail(nullptr, rc, err);
+  // 10 .. 16 dofs: the hex kernel (one metric row per lane, 16 lanes per robot) is the only mapping instantiated; it carries every
+  // leaf kind and both resolves
+  if (d.robot.n_dof > 9 && d.goal_floats > 16)
+    return fail(nullptr, RMP2_ERR_UNSUPPORTED, "more than 16 goal floats per robot with n_dof > 9");
+  if (n_slots > 2 || n_slots_full > 2)   // (with_slots stops at 2)
+    return fail(nullptr, RMP2_ERR_UNSUPPORTED, "kinematic tree needs more than 2 saved branch states");
+  return RMP2_OK;
+}
+
 int rmp2_validate(const rmp2_desc* desc) {
   if (!desc) return fail(nullptr, RMP2_ERR_INVALID_ARGUMENT, "null argument");
   if (desc->abi_version != RMP2_ABI_VERSION)
@@ -2331,16 +2394,8 @@ int rmp2_validate(const rmp2_desc* desc) {
   // (DevProgram is ~20 KB: on the heap, like rmp2_create's copies are short-lived stack objects of the same size)
   std::vector<DevProgram> P(2);
   int n_slots = 0, n_slots_full = 0;
-  std::string err;
   std::vector<HexOp> hops;
-  int rc = compile_program(*desc, P[0], n_slots, err, /*prune=*/true, &hops);
-  if (rc == RMP2_OK) rc = compile_program(*desc, P[1], n_slots_full, err, /*prune=*/false);
-  if (rc != RMP2_OK) return fail(nullptr, rc, err);
-  if (desc->robot.n_dof > 9 && desc->goal_floats > 16)
-    return fail(nullptr, RMP2_ERR_UNSUPPORTED, "more than 16 goal floats per robot with n_dof > 9");
-  if (n_slots > 2 || n_slots_full > 2)
-    return fail(nullptr, RMP2_ERR_UNSUPPORTED, "kinematic tree needs more than 2 saved branch states");
-  return RMP2_OK;
+  return compile_desc(*desc, P[0], n_slots, P[1], n_slots_full, hops);
 }
 
 int rmp2_create(const rmp2_desc* desc, int device, rmp2_handle** out) {
@@ -2353,19 +2408,8 @@ int rmp2_create(const rmp2_desc* desc, int device, rmp2_handle** out) {
     return fail(nullptr, RMP2_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
   DevProgram P, Pfull;
   int n_slots = 0, n_slots_full = 0;
-  std::string err;
   std::vector<HexOp> hops;
-  int rc = compile_program(*desc, P, n_slots, err, /*prune=*/true, &hops);
-  if (rc == RMP2_OK) rc = compile_program(*desc, Pfull, n_slots_full, err, /*prune=*/false);
-  if (rc != RMP2_OK) return fail(nullptr, rc, err);
-  if (desc->robot.n_dof > 9) {
-    // 10 .. 16 dofs: the hex kernel (one metric row per lane, 16 lanes per robot) is the only mapping instantiated; it
-    // carries every leaf kind and both resolves
-    if (desc->goal_floats > 16)
-      return fail(nullptr, RMP2_ERR_UNSUPPORTED, "more than 16 goal floats per robot with n_dof > 9");
-  }
-  if (n_slots > 2 || n_slots_full > 2)
-    return fail(nullptr, RMP2_ERR_UNSUPPORTED, "kinematic tree needs more than 2 saved branch states");
+  if (int rc = compile_desc(*desc, P, n_slots, Pfull, n_slots_full, hops)) return rc;
   rmp2_handle* h = new (std::nothrow) rmp2_handle();
   if (!h) return fail(nullptr, RMP2_ERR_HIP, "out of host memory");
   h->device = device;
@@ -2511,21 +2555,27 @@ int rmp2_destroy(rmp2_handle* h) {
   if (h->d_pair_begin) (void)hipFree(h->d_pair_begin);
   if (h->d_scratch) (void)hipFree(h->d_scratch);
   if (h->d_system) (void)hipFree(h->d_system);
-  if (h->d_pairs) (void)hipFree(h->d_pairs);
+  if (h->d_stage) (void)hipFree(h->d_stage);
   if (h->d_self) (void)hipFree(h->d_self);
-  if (h->d_self_buf) (void)hipFree(h->d_self_buf);
   if (h->d_hull) (void)hipFree(h->d_hull);
   if (h->d_hull_verts) (void)hipFree(h->d_hull_verts);
   if (h->d_hull_planes) (void)hipFree(h->d_hull_planes);
-  if (h->d_hull_buf) (void)hipFree(h->d_hull_buf);
   if (h->d_shull) (void)hipFree(h->d_shull);
-  if (h->d_shull_obs) (void)hipFree(h->d_shull_obs);
-  if (h->d_shull_verts) (void)hipFree(h->d_shull_verts);
-  if (h->d_shull_planes) (void)hipFree(h->d_shull_planes);
   if (h->d_inert) (void)hipFree(h->d_inert);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
   return RMP2_OK;
+}
+
+// Whether the step itself forms the pairs of link geometry on `obs` (include/rmp2.h rmp2_obstacles.link_capsules): tables of at most
+// 256 primitives, no CYLINDER, robots with at most 9 dofs and 16 goal floats, solve = pinv only where the quad mapping certifies or
+// computes it.  Beyond, plain steps of distance-leaf sets are staged (stage_link_geometry) and the others refused (prepare_step).
+static bool fused_link_geometry_fits(const rmp2_handle* h, const rmp2_obstacles* obs) {
+  if (obs->n_spheres > kLdsSpheres || obs->primitive == RMP2_PRIM_CYLINDER || h->n_template > 9 || h->goal_floats > 16) return false;
+  // (2-dof robots: the quad mapping's closed-form 2 x 2 resolve IS the pseudo-inverse with TensorFlow's cutoff, for every robot;
+  // sets with attached-point leaves resolve as they do on explicit arrays: the rank-deficient ones through the careful pass)
+  if (h->n_template == 2) return true;
+  return !(h->strict && !quad_certifies_strict(h)) && (h->has_point || !h->likely_singular);
 }
 
 // Argument checks of a control step and the kernels' view of its obstacle / output arguments (R > 0).
@@ -2577,7 +2627,7 @@ static int prepare_step(rmp2_handle* h, const float* q, const float* qd, const f
         return fail(h, RMP2_ERR_INVALID_ARGUMENT, "sphere table missing");
       if (obs->primitive != RMP2_PRIM_SPHERE && obs->primitive != RMP2_PRIM_CAPSULE && obs->primitive != RMP2_PRIM_CYLINDER)
         return fail(h, RMP2_ERR_INVALID_ARGUMENT, "unknown obstacle primitive");
-      if (obs->primitive == RMP2_PRIM_CYLINDER && (obs->link_capsules || h->has_point))   // (plain steps over a shared table never get here: step_impl)
+      if (obs->primitive == RMP2_PRIM_CYLINDER && (obs->link_capsules || h->has_point))   // (plain steps over a shared table never get here: stage_link_geometry)
         return fail(h, RMP2_ERR_UNSUPPORTED, "cylinder tables with link geometry in a rollout / over ragged lists / for attached-point leaves: the "
                                              "nearest points of a segment and a cylinder are an iteration -- rmp2_closest_points_links + EXPLICIT_PAIRS");
       if (o.mode == RMP2_OBS_RAGGED_SPHERES && (!obs->csr_offset || (!obs->csr_index && obs->n_spheres > 0)))
@@ -2604,10 +2654,7 @@ static int prepare_step(rmp2_handle* h, const float* q, const float* qd, const f
       if ((o.mode != RMP2_OBS_SHARED_SPHERES && !ragged_ok) || obs->n_spheres > kLdsSpheres)
         return fail(h, RMP2_ERR_UNSUPPORTED, "link_capsules: SHARED_SPHERES / RAGGED_SPHERES tables of at most 256 primitives "
                                              "(otherwise: rmp2_closest_points_links + EXPLICIT_PAIRS)");
-      // (sets with attached-point leaves resolve as they do on explicit arrays: the rank-deficient ones through the careful pass)
-      // (2-dof robots: the quad mapping's closed-form 2 x 2 resolve IS the pseudo-inverse with TensorFlow's cutoff, for every robot)
-      if ((!h->has_point && (((h->strict && !quad_certifies_strict(h)) || h->likely_singular) && h->n_template != 2)) ||
-          (h->has_point && h->strict && !quad_certifies_strict(h) && h->n_template != 2) || h->n_template > 9 || h->goal_floats > 16)
+      if (!fused_link_geometry_fits(h, obs))
         return fail(h, RMP2_ERR_UNSUPPORTED, "link_capsules: robots with at most 9 dofs; solve = pinv only where the quad mapping "
                                              "certifies or computes it (otherwise: rmp2_closest_points_links + EXPLICIT_PAIRS)");
       o.link_caps = obs->link_capsules;
@@ -2622,7 +2669,7 @@ static bool needs_system_buffer(const rmp2_handle* h) {
   return (h->strict || h->likely_singular) && !quad_certifies_strict(h) && h->n_template == 9;
 }
 
-// Link geometry over RAGGED lists beyond the fused limits (step_impl): the closest-point stage has written, per robot, the pairs of
+// Link geometry over RAGGED lists beyond the fused limits (stage_link_geometry): the closest-point stage has written, per robot, the pairs of
 // every distance leaf with EVERY primitive of the table (leaf i owns pairs [i K, (i + 1) K)); this kernel lays out what the robot's
 // list asks for -- one pair per LIST ENTRY, so that an index a list repeats counts twice, as the fused list walk counts it -- at L
 // slots per leaf, L = the longest list of the fleet.  Slots beyond a robot's list (and entries outside the table) hold a filler
@@ -2651,10 +2698,8 @@ __global__ void __launch_bounds__(kWave) rmp2_gather_list_pairs_kernel(const flo
 }
 
 static int grow_system_buffer(rmp2_handle* h, int32_t R) {
-  if (h->d_system) HIP_TRY(h, hipFree(h->d_system));
-  h->d_system = nullptr;
   h->system_robots = 0;
-  HIP_TRY(h, hipMalloc(&h->d_system, sizeof(double) * (size_t)R * h->n_dof * (h->n_dof + 1)));
+  if (int rc = realloc_device(h, &h->d_system, sizeof(double) * (size_t)R * h->n_dof * (h->n_dof + 1))) return rc;
   h->system_robots = (size_t)R;
   return RMP2_OK;
 }
@@ -2701,8 +2746,28 @@ static int launch_self_stage(rmp2_handle* h, const float* q, const rmp2_obstacle
   return RMP2_OK;
 }
 
+// Launch of rmp2_hull_stage_kernel over a SHARED_SPHERES sphere / capsule table (K > 0): pair leaf o owns pairs [o K, (o + 1) K).
+// The hulls are the handle's HullProg: its link hulls, or with hull self pairs the pair leaves' hulls of that list (whose HullProg
+// places each leaf's obstacle pairs in front of its self pairs).
 static int launch_hull_stage(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
-                             int32_t R, hipStream_t s);
+                             int32_t R, hipStream_t s) {
+  const int L = (int)h->pair_leaves.size(), K = table->n_spheres;
+  const size_t lds_bytes = sizeof(float4) * 3 * (size_t)L * kHullRobots;
+  const int blocks = (R + kHullRobots - 1) / kHullRobots;
+  const HullProg* hp = static_cast<const HullProg*>(h->d_hull);
+  const float4* tab = reinterpret_cast<const float4*>(table->spheres);
+#define RMP2_HULL_STAGE_(CAPS_)                                                                                              \
+  hipLaunchKernelGGL((rmp2_hull_stage_kernel<S, CAPS_>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog, hp,           \
+                     h->d_hull_verts, h->d_hull_planes, q, tab, K, p_link, p_obs, dist, (int)R)
+  const bool caps = table->primitive == RMP2_PRIM_CAPSULE;
+  with_slots(h->n_slots, [&](auto S) {
+    if (caps) RMP2_HULL_STAGE_(true);
+    else RMP2_HULL_STAGE_(false);
+  });
+#undef RMP2_HULL_STAGE_
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
 
 // Launch of the hull self-pair stage: with `table` (a SHARED_SPHERES sphere / capsule table, K > 0) rmp2_hull_stage_kernel first
 // forms the K obstacle pairs of each leaf on the leaves' hulls, then rmp2_self_hull_stage_kernel the self pairs behind them;
@@ -2718,25 +2783,48 @@ static int launch_self_hull_stage(rmp2_handle* h, const float* q, const rmp2_obs
   const size_t lds_bytes = sizeof(float) * 12 * (size_t)(slots > 0 ? slots : 1) * nr;
   const int blocks = (R + nr - 1) / nr;
   const SelfHullProg* sp = static_cast<const SelfHullProg*>(h->d_shull);
-#define RMP2_SELF_HULL_STAGE_(SLOTS_)                                                                                           \
-  hipLaunchKernelGGL((rmp2_self_hull_stage_kernel<SLOTS_>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog_full, sp,      \
-                     h->d_shull_verts, h->d_shull_planes, q, p_link, p_obs, dist, P, K, (int)R, nr)
-  switch (h->n_slots_full) {   // (the kernel walks the unpruned program: its save slots, not the step's)
-    case 0: RMP2_SELF_HULL_STAGE_(0); break;
-    case 1: RMP2_SELF_HULL_STAGE_(1); break;
-    default: RMP2_SELF_HULL_STAGE_(2); break;
-  }
-#undef RMP2_SELF_HULL_STAGE_
+  with_slots(h->n_slots_full, [&](auto S) {   // (the kernel walks the unpruned program: its save slots, not the step's)
+    hipLaunchKernelGGL((rmp2_self_hull_stage_kernel<S>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog_full, sp,
+                       h->d_hull_verts, h->d_hull_planes, q, p_link, p_obs, dist, P, K, (int)R, nr);
+  });
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }
 
+// Grows the handle's stage buffer (rmp2_host.h d_stage) to `need` floats for the stage of `what` (a step of R robots).  Refused inside
+// a stream capture and beyond free device memory.
+static int grow_stage_buffer(rmp2_handle* h, size_t need, int32_t R, hipStream_t s, const std::string& what) {
+  if (need <= h->stage_floats) return RMP2_OK;
+  if (capturing(s))
+    return fail(h, RMP2_ERR_UNSUPPORTED, what + " as stage + explicit-pair step: the handle's pair buffer must grow -- step once "
+                                                "outside the capture first");
+  if (int rc = use_device(h)) return rc;
+  if (h->d_stage) HIP_TRY(h, hipFree(h->d_stage));   // (synchronises the device: no launch still reads the old buffer)
+  h->d_stage = nullptr, h->stage_floats = 0;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+  if (sizeof(float) * need > free_b)
+    return fail(h, RMP2_ERR_UNSUPPORTED, what + ": the stage's pair buffer needs " + std::to_string(sizeof(float) * need) + " bytes (" +
+                                             std::to_string(sizeof(float) * need / (size_t)R) + " per robot), " + std::to_string(free_b) +
+                                             " bytes of device memory are free -- step a smaller fleet");
+  HIP_TRY(h, hipMalloc(&h->d_stage, sizeof(float) * need));
+  h->stage_floats = need;
+  return RMP2_OK;
+}
+
+// The stage buffer as p_link | p_obs [R][P][3] (+ dist [R][P] with attached-point leaves) -- 24 P (+ 4 P) bytes per robot
+// (include/rmp2.h) --, grown for the stage of `what`.
+static int stage_arrays(rmp2_handle* h, size_t P, int32_t R, hipStream_t s, const char* what, float*& pl, float*& po, float*& dd) {
+  const size_t arr = (size_t)R * P * 3;
+  if (int rc = grow_stage_buffer(h, 2 * arr + (h->has_point ? (size_t)R * P : 0), R, s, what)) return rc;
+  if (int rc = use_device(h)) return rc;
+  pl = h->d_stage, po = pl + arr, dd = h->has_point ? po + arr : nullptr;
+  return RMP2_OK;
+}
+
 // The staged step of a handle with self collision (include/rmp2.h): validates the obstacle input, forms every pair leaf's range
-// [K obstacle pairs | S_l self pairs] in the handle's buffer and describes it as EXPLICIT_PAIRS in `staged`.
-static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs, const RolloutArgs& ro, int32_t R, void* stream,
-                      rmp2_obstacles& staged) {
-  if (ro.n_iters != 1 || ro.substeps != 0)
-    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
+// [K obstacle pairs | S_l self pairs] in the handle's stage buffer, described as EXPLICIT_PAIRS in `staged` and put in *obs.
+static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles*& obs, int32_t R, hipStream_t s, rmp2_obstacles& staged) {
   const int mode = obs ? obs->mode : RMP2_OBS_NONE;
   if (mode == RMP2_OBS_EXPLICIT_PAIRS)
     return fail(h, RMP2_ERR_UNSUPPORTED, "self collision with caller-supplied EXPLICIT_PAIRS: the self pairs would have to be merged "
@@ -2762,80 +2850,20 @@ static int stage_self(rmp2_handle* h, const float* q, const rmp2_obstacles* obs,
                                          "hulls (turn the hulls off with rmp2_set_self_collision(h, 0, ...) to step on capsules)");
   if (h->self_hulls && with_table && h->shull_leaf_empty)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs with an obstacle table: every distance leaf needs a hull (an entry is empty)");
-  const size_t K = with_table ? (size_t)obs->n_spheres : 0;
-  const size_t L = h->pair_leaves.size();
+  const int K = with_table ? obs->n_spheres : 0;
+  auto pairs_of = [&](int o) { return (size_t)(h->pair_leaf_point[o] ? 0 : K) + (size_t)h->self_counts[o]; };
   size_t P = 0;
-  int32_t pb[RMP2_MAX_LEAVES + 1];
-  for (int l = 0, o = 0; l <= RMP2_MAX_LEAVES; ++l) {
-    pb[l] = (int32_t)P;
-    if (o < (int)L && h->pair_leaves[o] == l) {
-      P += (h->pair_leaf_point[o] ? 0 : K) + (size_t)h->self_counts[o];
-      ++o;
-    }
-  }
+  for (int o = 0; o < (int)h->pair_leaves.size(); ++o) P += pairs_of(o);
   if (P > (size_t)INT32_MAX / 4) return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: too many pairs per robot");
-  // buffer: p_link | p_obs [R][P][3] (+ dist [R][P] with attached-point leaves) -- 24 P (+ 4 P) bytes per robot (include/rmp2.h)
-  const size_t arr = (size_t)R * P * 3;
-  const size_t need = 2 * arr + (h->has_point ? (size_t)R * P : 0);
-  hipStream_t s = (hipStream_t)stream;
-  if (need > h->self_buf_floats) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-      return fail(h, RMP2_ERR_UNSUPPORTED, "self collision as stage + explicit-pair step: the handle's pair buffer must grow -- step once "
-                                           "outside the capture first");
-    if (int rc = use_device(h)) return rc;
-    if (h->d_self_buf) HIP_TRY(h, hipFree(h->d_self_buf));   // (synchronises the device: no launch still reads the old buffer)
-    h->d_self_buf = nullptr, h->self_buf_floats = 0;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
-    if (sizeof(float) * need > free_b)
-      return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: the stage's pair buffer needs " + std::to_string(sizeof(float) * need) +
-                                               " bytes (" + std::to_string(sizeof(float) * need / (size_t)R) + " per robot), " +
-                                               std::to_string(free_b) + " bytes of device memory are free -- step a smaller fleet");
-    HIP_TRY(h, hipMalloc(&h->d_self_buf, sizeof(float) * need));
-    h->self_buf_floats = need;
-  }
-  if (int rc = use_device(h)) return rc;
-  float* const pl = h->d_self_buf;
-  float* const po = pl + arr;
-  float* const dd = h->has_point ? po + arr : nullptr;
+  float *pl, *po, *dd;
+  if (int rc = stage_arrays(h, P, R, s, "self collision", pl, po, dd)) return rc;
   if (h->self_hulls) {
     if (int rc = launch_self_hull_stage(h, q, with_table ? obs : nullptr, pl, po, dd, (int)P, R, s)) return rc;
   } else if (int rc = launch_self_stage(h, q, with_table ? obs : nullptr, pl, po, dd, (int)P, R, s)) {
     return rc;
   }
-  std::memset(&staged, 0, sizeof(staged));
-  staged.mode = RMP2_OBS_EXPLICIT_PAIRS;
-  staged.n_pairs = (int32_t)P;
-  for (int l = 0; l <= RMP2_MAX_LEAVES; ++l) staged.pair_begin[l] = pb[l];
-  staged.p_link = pl, staged.p_obs = po, staged.dist = dd;
-  return RMP2_OK;
-}
-
-// Launch of rmp2_hull_stage_kernel over a SHARED_SPHERES sphere / capsule table (K > 0): pair leaf o owns pairs [o K, (o + 1) K).
-// The hulls are the handle's link hulls, or with hull self pairs the pair leaves' hulls of that list (whose HullProg places each
-// leaf's obstacle pairs in front of its self pairs).
-static int launch_hull_stage(rmp2_handle* h, const float* q, const rmp2_obstacles* table, float* p_link, float* p_obs, float* dist,
-                             int32_t R, hipStream_t s) {
-  const bool self = h->self_hulls && h->self_n_pairs > 0;
-  const int L = self ? (int)h->pair_leaves.size() : h->hull_n, K = table->n_spheres;
-  const size_t lds_bytes = sizeof(float4) * 3 * (size_t)L * kHullRobots;
-  const int blocks = (R + kHullRobots - 1) / kHullRobots;
-  const HullProg* hp = static_cast<const HullProg*>(self ? h->d_shull_obs : h->d_hull);
-  const float4* hv = self ? h->d_shull_verts : h->d_hull_verts;
-  const float4* hpl = self ? h->d_shull_planes : h->d_hull_planes;
-  const float4* tab = reinterpret_cast<const float4*>(table->spheres);
-#define RMP2_HULL_STAGE_(SLOTS_, CAPS_)                                                                                      \
-  hipLaunchKernelGGL((rmp2_hull_stage_kernel<SLOTS_, CAPS_>), dim3(blocks), dim3(kWave), lds_bytes, s, h->d_prog, hp,      \
-                     hv, hpl, q, tab, K, p_link, p_obs, dist, (int)R)
-  const bool caps = table->primitive == RMP2_PRIM_CAPSULE;
-  switch (h->n_slots) {
-    case 0: if (caps) RMP2_HULL_STAGE_(0, true); else RMP2_HULL_STAGE_(0, false); break;
-    case 1: if (caps) RMP2_HULL_STAGE_(1, true); else RMP2_HULL_STAGE_(1, false); break;
-    default: if (caps) RMP2_HULL_STAGE_(2, true); else RMP2_HULL_STAGE_(2, false); break;
-  }
-#undef RMP2_HULL_STAGE_
-  HIP_TRY(h, hipGetLastError());
+  explicit_pairs(h->pair_leaves, pairs_of, pl, po, dd, staged);
+  obs = &staged;
   return RMP2_OK;
 }
 
@@ -2859,167 +2887,117 @@ static int check_hull_table(rmp2_handle* h, const rmp2_obstacles* t) {
   return RMP2_OK;
 }
 
-// The staged step of a handle with link hulls (include/rmp2.h): the hull stage into the handle's buffer, described as
-// EXPLICIT_PAIRS in `staged` (*used = true); obstacle input NONE or an empty table: nothing to stage (*used = false).
-static int stage_hulls(rmp2_handle* h, const float* q, const rmp2_obstacles* obs, const RolloutArgs& ro, int32_t R, void* stream,
-                       rmp2_obstacles& staged, bool* used) {
-  *used = false;
-  if (ro.n_iters != 1 || ro.substeps != 0)
-    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
+// The staged step of a handle with link hulls (include/rmp2.h): the hull stage into the handle's stage buffer, described as
+// EXPLICIT_PAIRS in `staged` and put in *obs; obstacle input NONE or an empty table: nothing to stage (*obs unchanged).
+static int stage_hulls(rmp2_handle* h, const float* q, const rmp2_obstacles*& obs, int32_t R, hipStream_t s, rmp2_obstacles& staged) {
   if (!obs || obs->mode == RMP2_OBS_NONE) return RMP2_OK;
   if (int rc = check_hull_table(h, obs)) return rc;
   if (obs->n_spheres == 0) return RMP2_OK;
   if (!q) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "q, qd and out->qdd are required");
-  const size_t K = (size_t)obs->n_spheres, L = (size_t)h->hull_n;
-  const size_t P = L * K;
+  const int K = obs->n_spheres;
+  const size_t P = h->pair_leaves.size() * (size_t)K;
   if (P > (size_t)INT32_MAX / 4) return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: too many pairs per robot");
-  // buffer: p_link | p_obs [R][P][3] (+ dist [R][P] with attached-point leaves) -- 24 P (+ 4 P) bytes per robot (include/rmp2.h)
-  const size_t arr = (size_t)R * P * 3;
-  const size_t need = 2 * arr + (h->has_point ? (size_t)R * P : 0);
-  hipStream_t s = (hipStream_t)stream;
-  if (need > h->hull_buf_floats) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-      return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls as stage + explicit-pair step: the handle's pair buffer must grow -- step once "
-                                           "outside the capture first");
-    if (int rc = use_device(h)) return rc;
-    if (h->d_hull_buf) HIP_TRY(h, hipFree(h->d_hull_buf));   // (synchronises the device: no launch still reads the old buffer)
-    h->d_hull_buf = nullptr, h->hull_buf_floats = 0;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
-    if (sizeof(float) * need > free_b)
-      return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: the stage's pair buffer needs " + std::to_string(sizeof(float) * need) +
-                                               " bytes (" + std::to_string(sizeof(float) * need / (size_t)R) + " per robot), " +
-                                               std::to_string(free_b) + " bytes of device memory are free -- step a smaller fleet");
-    HIP_TRY(h, hipMalloc(&h->d_hull_buf, sizeof(float) * need));
-    h->hull_buf_floats = need;
-  }
-  if (int rc = use_device(h)) return rc;
-  float* const pl = h->d_hull_buf;
-  float* const po = pl + arr;
-  float* const dd = h->has_point ? po + arr : nullptr;
+  float *pl, *po, *dd;
+  if (int rc = stage_arrays(h, P, R, s, "link hulls", pl, po, dd)) return rc;
   if (int rc = launch_hull_stage(h, q, obs, pl, po, dd, R, s)) return rc;
-  std::memset(&staged, 0, sizeof(staged));
-  staged.mode = RMP2_OBS_EXPLICIT_PAIRS;
-  staged.n_pairs = (int32_t)P;
-  for (int l = 0, o = 0, acc = 0; l <= RMP2_MAX_LEAVES; ++l) {
-    staged.pair_begin[l] = acc;
-    if (o < (int)h->pair_leaves.size() && h->pair_leaves[o] == l) acc += (int)K, ++o;
-  }
-  staged.p_link = pl, staged.p_obs = po, staged.dist = dd;
-  *used = true;
+  explicit_pairs(h->pair_leaves, [K](int) { return K; }, pl, po, dd, staged);
+  obs = &staged;
   return RMP2_OK;
 }
 
+// Link geometry of the distance leaves beyond what the fused forms take (include/rmp2.h rmp2_obstacles.link_capsules: robots with more
+// than nine dofs, solve = pinv where the quad mapping does not certify it, sets without an inertia leaf, tables beyond 256 primitives,
+// CYLINDER tables -- whose segment-cylinder closed form is an iteration): the step runs as the reference's own data flow instead
+// (simulation.py:462-484 -> data_management.py:22-37 -> taskmap.py:115-138) -- the closest-point stage into the handle's stage buffer,
+// then the explicit-pair step on it.  Same pairs, same semantics; two launches.  (Plain control steps of distance-leaf sets; rollouts
+// keep the fused forms' limits.)
+static bool stages_link_geometry(const rmp2_handle* h, const rmp2_obstacles* obs, const RolloutArgs& ro) {
+  return obs && obs->link_capsules && (obs->mode == RMP2_OBS_SHARED_SPHERES || obs->mode == RMP2_OBS_RAGGED_SPHERES) && !h->has_point &&
+         ro.n_iters == 1 && ro.substeps == 0 && obs->n_spheres > 0 && obs->spheres && !h->distance_leaves.empty() &&
+         !fused_link_geometry_fits(h, obs);
+}
+
+// The staged link-geometry step (stages_link_geometry): rmp2_closest_points_links pairs every distance leaf with every primitive
+// (leaf i owns pairs [i K, (i + 1) K)).  RAGGED lists take one more launch: rmp2_gather_list_pairs_kernel lays out one pair per list
+// entry at L = the fleet's longest list slots per leaf -- L is read back from csr_offset, so this form synchronises the stream and is
+// refused inside a stream capture.  The result is described as EXPLICIT_PAIRS in `staged` and put in *obs.
+static int stage_link_geometry(rmp2_handle* h, const float* q, const rmp2_obstacles*& obs, int32_t R, hipStream_t s,
+                               rmp2_obstacles& staged) {
+  const bool ragged_lists = obs->mode == RMP2_OBS_RAGGED_SPHERES;
+  const int K = obs->n_spheres;
+  const size_t n_dist = h->distance_leaves.size();
+  const size_t P_all = n_dist * (size_t)K;   // the stage's pairs per robot: every leaf with every primitive
+  int L = 0;
+  if (ragged_lists) {
+    if (!obs->csr_offset || !obs->csr_index) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "RAGGED_SPHERES needs csr_offset / csr_index");
+    if (capturing(s))
+      return fail(h, RMP2_ERR_UNSUPPORTED, "link geometry over ragged lists as stage + explicit-pair step reads the list lengths back: "
+                                           "not inside a stream capture");
+    if (int rc = use_device(h)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(s));   // (the lists may have been written on this stream)
+    std::vector<int32_t> offs((size_t)R + 1);
+    HIP_TRY(h, hipMemcpy(offs.data(), obs->csr_offset, sizeof(int32_t) * offs.size(), hipMemcpyDeviceToHost));
+    size_t longest = 0;
+    for (int32_t r = 0; r < R; ++r) {
+      if (offs[r + 1] < offs[r]) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "csr_offset must not decrease");
+      longest = std::max(longest, (size_t)(offs[r + 1] - offs[r]));
+    }
+    longest = std::max<size_t>(longest, 1);   // (every list empty: one filler pair per leaf)
+    if (n_dist * longest > (size_t)INT32_MAX / 4) return fail(h, RMP2_ERR_UNSUPPORTED, "ragged lists too long for the explicit-pair step");
+    L = (int)longest;
+  }
+  // buffer: p_link [all | out] then p_obs [all | out], all = [R][P_all][3], out = [R][n_dist L][3] over ragged lists
+  const size_t all = (size_t)R * P_all * 3;
+  const size_t arr = all + (ragged_lists ? (size_t)R * n_dist * L * 3 : 0);
+  if (int rc = grow_stage_buffer(h, 2 * arr, R, s, "link geometry")) return rc;
+  float* const pl = h->d_stage;
+  float* const po = pl + arr;
+  rmp2_obstacles table = *obs;
+  table.link_capsules = nullptr;
+  table.mode = RMP2_OBS_SHARED_SPHERES;   // (the stage pairs every leaf with every primitive; a ragged fleet's lists pick below)
+  table.csr_offset = table.csr_index = nullptr;
+  if (int rc = rmp2_closest_points_links(h, q, &table, obs->link_capsules, pl, po, R, s)) return rc;
+  if (ragged_lists) {
+    hipLaunchKernelGGL(rmp2_gather_list_pairs_kernel, dim3(R), dim3(kWave), 0, s, pl, po, obs->csr_offset, obs->csr_index, pl + all,
+                       po + all, (int)n_dist, K, L, (int)R);
+    HIP_TRY(h, hipGetLastError());
+    // leaf ranges at L slots per distance leaf (the stage's were K per leaf; prepare_step uploads the new ones -- after the stage's
+    // own upload on the same stream, each from pageable memory, i.e. read before the call returns)
+    explicit_pairs(h->distance_leaves, [L](int) { return L; }, pl + all, po + all, nullptr, staged);
+  } else {
+    explicit_pairs(h->distance_leaves, [K](int) { return K; }, pl, po, nullptr, staged);   // (as the stage laid the pairs out)
+  }
+  obs = &staged;
+  return RMP2_OK;
+}
+
+// A control step: at most one stage -- chosen by the handle's state and the obstacle input -- writes the pairs of the step into the
+// handle's stage buffer, then the step itself runs.
 static int step_impl(rmp2_handle* h, const float* q, const float* qd, const float* goal, int32_t goal_stride,
                      const rmp2_obstacles* obs, const rmp2_outputs* out, const RolloutArgs& ro, int32_t R, void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   if (R < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "R < 0");
   if (R == 0) return RMP2_OK;  // empty fleet: nothing to do (pointers may be null)
-  // Link geometry of the distance leaves beyond what the fused forms take (include/rmp2.h rmp2_obstacles.link_capsules: robots with
-  // more than nine dofs, solve = pinv where the quad mapping does not certify it, sets without an inertia leaf, tables beyond 256
-  // primitives, CYLINDER tables -- whose segment-cylinder closed form is an iteration): the step runs as the reference's own data
-  // flow instead (simulation.py:462-484 -> data_management.py:22-37 -> taskmap.py:115-138) -- the closest-point stage into a buffer
-  // of the handle, then the explicit-pair step on it.  Same pairs, same semantics; two launches.  (Plain control steps; rollouts keep
-  // the fused forms' limits.)  RAGGED lists take the same route through one more launch: the stage over the whole table, then
-  // rmp2_gather_list_pairs_kernel lays out one pair per list entry at L = the fleet's longest list slots per leaf -- L is read back
-  // from csr_offset, so this form synchronises the stream and is refused inside a stream capture.
+  hipStream_t s = (hipStream_t)stream;
+  // (link hulls and self collision exclude each other; after either stage the input is EXPLICIT_PAIRS, never a link-geometry table)
   rmp2_obstacles staged;
-  if (h->hull_n > 0) {   // link hulls: the hull stage, then the explicit-pair step on its arrays
-    if (h->self_n_pairs > 0) return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls together with self collision: not supported");
-    bool used = false;
-    if (int rc = stage_hulls(h, q, obs, ro, R, stream, staged, &used)) return rc;
-    if (used) obs = &staged;
-  }
-  if (h->self_n_pairs > 0) {   // self collision: the self stage (+ the table's pairs), then the explicit-pair step on its arrays
-    if (int rc = stage_self(h, q, obs, ro, R, stream, staged)) return rc;
-    obs = &staged;
-  }
-  const bool ragged_lists = obs && obs->mode == RMP2_OBS_RAGGED_SPHERES;
-  if (obs && obs->link_capsules && (obs->mode == RMP2_OBS_SHARED_SPHERES || ragged_lists) && !h->has_point && ro.n_iters == 1 &&
-      ro.substeps == 0 && obs->n_spheres > 0 && obs->spheres && !h->distance_leaves.empty() &&
-      (obs->n_spheres > kLdsSpheres || obs->primitive == RMP2_PRIM_CYLINDER || (h->strict && !quad_certifies_strict(h) && h->n_template != 2) ||
-       (h->likely_singular && h->n_template != 2) || h->n_template > 9 || h->goal_floats > 16)) {
-    const size_t n_dist = h->distance_leaves.size();
-    const size_t P_all = n_dist * (size_t)obs->n_spheres;   // the stage's pairs per robot: every leaf with every primitive
-    hipStream_t s0 = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = s0 && hipStreamIsCapturing(s0, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    size_t L = 0;
-    if (ragged_lists) {
-      if (!obs->csr_offset || !obs->csr_index) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "RAGGED_SPHERES needs csr_offset / csr_index");
-      if (capturing)
-        return fail(h, RMP2_ERR_UNSUPPORTED, "link geometry over ragged lists as stage + explicit-pair step reads the list lengths back: "
-                                             "not inside a stream capture");
-      if (int rc = use_device(h)) return rc;
-      HIP_TRY(h, hipStreamSynchronize(s0));   // (the lists may have been written on this stream)
-      std::vector<int32_t> offs((size_t)R + 1);
-      HIP_TRY(h, hipMemcpy(offs.data(), obs->csr_offset, sizeof(int32_t) * offs.size(), hipMemcpyDeviceToHost));
-      for (int32_t r = 0; r < R; ++r) {
-        if (offs[r + 1] < offs[r]) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "csr_offset must not decrease");
-        L = std::max(L, (size_t)(offs[r + 1] - offs[r]));
-      }
-      L = std::max<size_t>(L, 1);   // (every list empty: one filler pair per leaf)
-      if (n_dist * L > (size_t)INT32_MAX / 4) return fail(h, RMP2_ERR_UNSUPPORTED, "ragged lists too long for the explicit-pair step");
-    }
-    const size_t P = ragged_lists ? n_dist * L : P_all;     // pairs per robot handed to the explicit-pair step
-    const size_t need_all = (size_t)R * P_all * 3;
-    const size_t need = need_all + (ragged_lists ? (size_t)R * P * 3 : 0);
-    if (need > h->pairs_floats) {
-      if (capturing)
-        return fail(h, RMP2_ERR_UNSUPPORTED, "link geometry as stage + explicit-pair step: the handle's pair buffer must grow -- step once "
-                                             "outside the capture first");
-      if (int rc = use_device(h)) return rc;
-      if (h->d_pairs) HIP_TRY(h, hipFree(h->d_pairs));   // (synchronises the device: no launch still reads the old buffer)
-      h->d_pairs = nullptr, h->pairs_floats = 0;
-      HIP_TRY(h, hipMalloc(&h->d_pairs, sizeof(float) * 2 * need));
-      h->pairs_floats = need;
-    }
-    float* const pl = h->d_pairs;
-    float* const po = h->d_pairs + h->pairs_floats;
-    rmp2_obstacles table = *obs;
-    table.link_capsules = nullptr;
-    table.mode = RMP2_OBS_SHARED_SPHERES;   // (the stage pairs every leaf with every primitive; a ragged fleet's lists pick below)
-    table.csr_offset = table.csr_index = nullptr;
-    if (int rc = rmp2_closest_points_links(h, q, &table, obs->link_capsules, pl, po, R, stream)) return rc;
-    std::memset(&staged, 0, sizeof(staged));
-    staged.mode = RMP2_OBS_EXPLICIT_PAIRS;
-    staged.n_pairs = (int32_t)P;
-    if (ragged_lists) {
-      float* const pl_out = pl + need_all;
-      float* const po_out = po + need_all;
-      hipLaunchKernelGGL(rmp2_gather_list_pairs_kernel, dim3(R), dim3(kWave), 0, s0, pl, po, obs->csr_offset, obs->csr_index, pl_out, po_out,
-                         (int)n_dist, (int)obs->n_spheres, (int)L, (int)R);
-      HIP_TRY(h, hipGetLastError());
-      staged.p_link = pl_out, staged.p_obs = po_out;
-      // leaf ranges at L slots per distance leaf (the stage's were K per leaf; prepare_step uploads the new ones -- after the stage's
-      // own upload on the same stream, each from pageable memory, i.e. read before the call returns)
-      int acc = 0;
-      for (int l = 0; l <= RMP2_MAX_LEAVES; ++l) {
-        staged.pair_begin[l] = acc;
-        if (l < h->n_leaves && std::find(h->distance_leaves.begin(), h->distance_leaves.end(), l) != h->distance_leaves.end()) acc += (int)L;
-      }
-    } else {
-      staged.p_link = pl, staged.p_obs = po;
-      for (int l = 0; l <= RMP2_MAX_LEAVES; ++l) staged.pair_begin[l] = h->h_pair_begin[l];   // (as the stage laid the pairs out)
-    }
-    obs = &staged;
-  }
+  int rc = RMP2_OK;
+  if (h->hull_n > 0) rc = stage_hulls(h, q, obs, R, s, staged);
+  else if (h->self_n_pairs > 0) rc = stage_self(h, q, obs, R, s, staged);
+  else if (stages_link_geometry(h, obs, ro)) rc = stage_link_geometry(h, q, obs, R, s, staged);
+  if (rc) return rc;
   ObsArgs o;
   OutArgs oa;
-  if (int rc = prepare_step(h, q, qd, goal, goal_stride, obs, out, ro, R, stream, o, oa)) return rc;
-  hipStream_t s = (hipStream_t)stream;
+  if ((rc = prepare_step(h, q, qd, goal, goal_stride, obs, out, ro, R, stream, o, oa))) return rc;
   if (needs_system_buffer(h) && (size_t)R > h->system_robots) {
     // the combined systems between the two kernels of the strict step (dispatch_solve): 8 n (n + 1) bytes per robot, owned by
-    // the handle, grown to the largest fleet stepped (hipFree synchronises the device: no launch still reads the old buffer).
-    // Not during a stream capture (an allocation there is illegal): rmp2_reserve(h, R) first.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+    // the handle, grown to the largest fleet stepped.  Not during a stream capture (an allocation there is illegal):
+    // rmp2_reserve(h, R) first.
+    if (capturing(s))
       return fail(h, RMP2_ERR_UNSUPPORTED, "this handle's two-kernel step needs its system buffer grown: call rmp2_reserve(h, R) "
                                            "before capturing the stream");
-    if (int rc = grow_system_buffer(h, R)) return rc;
+    if ((rc = grow_system_buffer(h, R))) return rc;
   }
-  int rc;
   if (h->n_template == 2)
     rc = dispatch_solve<2>(h, q, qd, goal, goal_stride, o, oa, ro, R, s);
   else if (h->n_template == 9)
@@ -3029,6 +3007,13 @@ static int step_impl(rmp2_handle* h, const float* q, const float* qd, const floa
   if (rc != RMP2_OK) return fail(h, rc, "no kernel instantiation for this robot");
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
+}
+
+// The staged handles (self collision, link hulls) step through rmp2_step only: refused by `entry`, `why` says what to do instead.
+static int refuse_staged(rmp2_handle* h, const char* entry, const char* why) {
+  const char* what = h->self_n_pairs > 0 ? "self collision" : (h->hull_n > 0 ? "link hulls" : nullptr);
+  if (!what) return RMP2_OK;
+  return fail(h, RMP2_ERR_UNSUPPORTED, std::string(what) + ": not in " + entry + " (" + why + ")");
 }
 
 int rmp2_step(rmp2_handle* h, const float* q, const float* qd, const float* goal, int32_t goal_stride,
@@ -3226,14 +3211,8 @@ int rmp2_exchange_step(rmp2_exchange* x, rmp2_handle* h, const float* q, const f
                        int32_t goal_stride, const float* next_local, int32_t next_local_is_ready, const rmp2_outputs* out,
                        int32_t R, void* stream, const float** table_out) {
   if (!x || !h) return RMP2_ERR_INVALID_ARGUMENT;
-  if (h->self_n_pairs > 0) {
-    x->error = "self collision: not in rmp2_exchange_step (the exchange's step is one launch on the gathered table)";
-    return fail(h, RMP2_ERR_UNSUPPORTED, x->error);
-  }
-  if (h->hull_n > 0) {
-    x->error = "link hulls: not in rmp2_exchange_step (the exchange's step is one launch on the gathered table)";
-    return fail(h, RMP2_ERR_UNSUPPORTED, x->error);
-  }
+  if (int rc = refuse_staged(h, "rmp2_exchange_step", "the exchange's step is one launch on the gathered table"))
+    return x->error = h->error, rc;
   if (x->n_pending < 1) return x->error = "no gathered table outstanding: rmp2_exchange_start first", RMP2_ERR_INVALID_ARGUMENT;
   const int b = x->pending[0];
   for (int i = 1; i < x->n_pending; ++i) x->pending[i - 1] = x->pending[i];
@@ -3295,11 +3274,7 @@ int rmp2_step_pair(rmp2_handle* ha, const float* qa, const float* qda, const flo
                    int32_t Rb, void* stream) {
   if (!ha || !hb) return RMP2_ERR_INVALID_ARGUMENT;
   for (rmp2_handle* hx : {ha, hb})
-    if (hx->self_n_pairs > 0)
-      return fail(hx, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_step_pair (step the two handles with rmp2_step)");
-  for (rmp2_handle* hx : {ha, hb})
-    if (hx->hull_n > 0)
-      return fail(hx, RMP2_ERR_UNSUPPORTED, "link hulls: not in rmp2_step_pair (step the two handles with rmp2_step)");
+    if (int rc = refuse_staged(hx, "rmp2_step_pair", "step the two handles with rmp2_step")) return rc;
   const RolloutArgs ro{1, 0, 0.f, nullptr, nullptr, 0};
   if (Ra > 0 && Rb > 0 && ha->device == hb->device && !ha->step_fence && !hb->step_fence) {
     ObsArgs oa_, ob_;
@@ -3319,10 +3294,7 @@ int rmp2_rollout(rmp2_handle* h, float* q, float* qd, const float* goal, int32_t
                  const rmp2_obstacles* obs, const rmp2_rollout_cfg* cfg, const rmp2_outputs* out, int32_t R,
                  void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
-  if (h->self_n_pairs > 0)
-    return fail(h, RMP2_ERR_UNSUPPORTED, "self collision: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
-  if (h->hull_n > 0)
-    return fail(h, RMP2_ERR_UNSUPPORTED, "link hulls: not in rmp2_rollout (the stage runs once per control step, outside the launch)");
+  if (int rc = refuse_staged(h, "rmp2_rollout", "the stage runs once per control step, outside the launch")) return rc;
   if (!cfg || cfg->n_control_steps < 1 || cfg->substeps < 0 || !(cfg->dt >= 0.f))
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, "rollout: need n_control_steps >= 1, substeps >= 0, dt >= 0");
   if (obs && obs->mode == RMP2_OBS_EXPLICIT_PAIRS)
@@ -3345,11 +3317,8 @@ int rmp2_forward_kinematics(rmp2_handle* h, const float* q, float* T, int32_t R,
   if (int rc = use_device(h)) return rc;
   const int blocks = (R + kWave - 1) / kWave;
   hipStream_t s = (hipStream_t)stream;
-  switch (h->n_slots_full) {
-    case 0: hipLaunchKernelGGL((rmp2_fk_kernel<0>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, T, R); break;
-    case 1: hipLaunchKernelGGL((rmp2_fk_kernel<1>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, T, R); break;
-    default: hipLaunchKernelGGL((rmp2_fk_kernel<2>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, T, R); break;
-  }
+  with_slots(h->n_slots_full,
+             [&](auto S) { hipLaunchKernelGGL((rmp2_fk_kernel<S>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, T, R); });
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }
@@ -3371,15 +3340,10 @@ int rmp2_closest_points_links(rmp2_handle* h, const float* q, const rmp2_obstacl
   hipStream_t s = (hipStream_t)stream;
   if (int rc = use_device(h)) return rc;
   // pair layout of the arrays written here: the i-th distance leaf owns pairs [i*K, (i+1)*K)
-  int32_t pb[RMP2_MAX_LEAVES + 1];
-  int acc = 0;
-  for (int l = 0; l <= RMP2_MAX_LEAVES; ++l) {
-    pb[l] = acc;
-    if (l < h->n_leaves && std::find(h->distance_leaves.begin(), h->distance_leaves.end(), l) != h->distance_leaves.end())
-      acc += table->n_spheres;
-  }
-  if (!h->pair_begin_valid || std::memcmp(h->h_pair_begin, pb, sizeof(pb)) != 0) {
-    std::memcpy(h->h_pair_begin, pb, sizeof(pb));
+  rmp2_obstacles lay;
+  explicit_pairs(h->distance_leaves, [table](int) { return table->n_spheres; }, p_link, p_obs, nullptr, lay);
+  if (!h->pair_begin_valid || std::memcmp(h->h_pair_begin, lay.pair_begin, sizeof(h->h_pair_begin)) != 0) {
+    std::memcpy(h->h_pair_begin, lay.pair_begin, sizeof(h->h_pair_begin));
     HIP_TRY(h, hipMemcpyAsync(h->d_pair_begin, h->h_pair_begin, sizeof(h->h_pair_begin), hipMemcpyHostToDevice, s));
     h->pair_begin_valid = true;
   }
@@ -3387,41 +3351,32 @@ int rmp2_closest_points_links(rmp2_handle* h, const float* q, const rmp2_obstacl
   std::memset(&o, 0, sizeof(o));
   o.mode = table->mode;
   o.n_spheres = table->n_spheres;
-  o.n_pairs = acc;
+  o.n_pairs = lay.n_pairs;
   o.capsule = table->primitive != RMP2_PRIM_SPHERE ? 1 : 0;   // (8-float records)
   o.cylinder = table->primitive == RMP2_PRIM_CYLINDER ? 1 : 0;
   o.spheres = table->spheres;
   o.pair_begin = h->d_pair_begin;
-  const int n_dist = acc / table->n_spheres;
+  const int n_dist = (int)h->distance_leaves.size();
   const size_t seg_bytes = sizeof(float4) * 2 * kClosestRobots * n_dist;
   if (seg_bytes <= 64 * 1024 && h->kernel_choice != 1) {  // (more distance leaves than that, or RMP2_KERNEL=lane: a lane per robot)
     const int wblocks = (R + kClosestRobots - 1) / kClosestRobots;
-#define RMP2_CLOSEST_WAVE_(SLOTS_, LINK_, CAPS_)                                                                        \
-    hipLaunchKernelGGL((rmp2_closest_wave_kernel<SLOTS_, LINK_, CAPS_>), dim3(wblocks), dim3(kWave), seg_bytes, s, h->d_prog, q, o, \
+#define RMP2_CLOSEST_WAVE_(LINK_, CAPS_)                                                                                \
+    hipLaunchKernelGGL((rmp2_closest_wave_kernel<S, LINK_, CAPS_>), dim3(wblocks), dim3(kWave), seg_bytes, s, h->d_prog, q, o,   \
                        link_capsules, n_dist, p_link, p_obs, R)
-#define RMP2_CLOSEST_WAVE(SLOTS_)                                                                                       \
-    do {                                                                                                                \
-      if (link_capsules && o.capsule) RMP2_CLOSEST_WAVE_(SLOTS_, true, true);                                           \
-      else if (link_capsules) RMP2_CLOSEST_WAVE_(SLOTS_, true, false);                                                  \
-      else if (o.capsule) RMP2_CLOSEST_WAVE_(SLOTS_, false, true);                                                      \
-      else RMP2_CLOSEST_WAVE_(SLOTS_, false, false);                                                                    \
-    } while (0)
-    switch (h->n_slots) {
-      case 0: RMP2_CLOSEST_WAVE(0); break;
-      case 1: RMP2_CLOSEST_WAVE(1); break;
-      default: RMP2_CLOSEST_WAVE(2); break;
-    }
-#undef RMP2_CLOSEST_WAVE
+    with_slots(h->n_slots, [&](auto S) {
+      if (link_capsules && o.capsule) RMP2_CLOSEST_WAVE_(true, true);
+      else if (link_capsules) RMP2_CLOSEST_WAVE_(true, false);
+      else if (o.capsule) RMP2_CLOSEST_WAVE_(false, true);
+      else RMP2_CLOSEST_WAVE_(false, false);
+    });
 #undef RMP2_CLOSEST_WAVE_
     HIP_TRY(h, hipGetLastError());
     return RMP2_OK;
   }
   const int blocks = (R + kWave - 1) / kWave;
-  switch (h->n_slots) {
-    case 0: hipLaunchKernelGGL((rmp2_closest_kernel<0>), dim3(blocks), dim3(kWave), 0, s, h->d_prog, q, o, link_capsules, p_link, p_obs, R); break;
-    case 1: hipLaunchKernelGGL((rmp2_closest_kernel<1>), dim3(blocks), dim3(kWave), 0, s, h->d_prog, q, o, link_capsules, p_link, p_obs, R); break;
-    default: hipLaunchKernelGGL((rmp2_closest_kernel<2>), dim3(blocks), dim3(kWave), 0, s, h->d_prog, q, o, link_capsules, p_link, p_obs, R); break;
-  }
+  with_slots(h->n_slots, [&](auto S) {
+    hipLaunchKernelGGL((rmp2_closest_kernel<S>), dim3(blocks), dim3(kWave), 0, s, h->d_prog, q, o, link_capsules, p_link, p_obs, R);
+  });
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }
@@ -3453,19 +3408,8 @@ int rmp2_set_self_collision(rmp2_handle* h, int32_t n_pairs, const int32_t* pair
     sp.ord_of_leaf[h->pair_leaves[o]] = o;
     sp.dord[o] = h->pair_leaf_point[o] ? -1 : nd++;
   }
-  std::vector<std::vector<int>> by_leaf(L);   // B frames per ordinal, in the order given
-  for (int k = 0; k < n_pairs; ++k) {
-    const int leaf = pairs[2 * k], b = pairs[2 * k + 1];
-    const int o = (leaf >= 0 && leaf < h->n_leaves) ? sp.ord_of_leaf[leaf] : -1;
-    if (o < 0)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": leaf " + std::to_string(leaf) +
-                                                    " is not a distance or attached-point leaf");
-    if (b < -1 || b >= F)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B " + std::to_string(b) + " out of range");
-    if (b == h->pair_leaf_frame[o])
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B is the leaf's own frame");
-    by_leaf[o].push_back(b);
-  }
+  std::vector<std::vector<int>> by_leaf;
+  if (int rc = group_self_pairs(h, n_pairs, pairs, by_leaf, [](int, int, int) { return RMP2_OK; })) return rc;
   for (int f = 0; f <= F; ++f)
     for (int c = 0; c < 8; ++c)
       if (!std::isfinite(capsules[8 * f + c]) || (c == 3 && capsules[8 * f + c] < 0.f))
@@ -3516,6 +3460,60 @@ int rmp2_self_pairs(rmp2_handle* h, const float* q, float* p_link, float* p_obs,
   return launch_self_stage(h, q, nullptr, p_link, p_obs, dist, h->self_n_pairs, R, (hipStream_t)stream);
 }
 
+// The hull arrays of both hull setters (include/rmp2.h rmp2_set_link_hulls): n entries back to back, each with at most
+// RMP2_MAX_HULL_VERTICES vertices and RMP2_MAX_HULL_FACES face planes -- at least one of each, or (empty_ok) neither --, finite vertices,
+// unit normals and finite offsets.  `what` names the feature in the messages ("link hulls"), `entry` one entry ("link hull").
+static int check_hulls(rmp2_handle* h, const char* what, const char* entry, bool empty_ok, int n, const int32_t* vert_offset,
+                       const float* verts, const int32_t* face_offset, const float* planes) {
+  const std::string w = what;
+  if (!vert_offset || !verts || !face_offset || !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null array");
+  if (vert_offset[0] != 0 || face_offset[0] != 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": offsets must start at 0");
+  for (int e = 0; e < n; ++e) {
+    const int nv = vert_offset[e + 1] - vert_offset[e], nf = face_offset[e + 1] - face_offset[e];
+    if (empty_ok ? (nv < 0 || nf < 0 || (nv == 0) != (nf == 0)) : (nv < 1 || nf < 1))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(entry) + " " + std::to_string(e) +
+                                                    (empty_ok ? ": needs vertices and face planes, or neither"
+                                                              : ": needs at least one vertex and one face plane"));
+    if (nv > RMP2_MAX_HULL_VERTICES || nf > RMP2_MAX_HULL_FACES)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(entry) + " " + std::to_string(e) + ": " + std::to_string(nv) + " vertices / " +
+                                                    std::to_string(nf) + " faces, at most RMP2_MAX_HULL_VERTICES = " +
+                                                    std::to_string(RMP2_MAX_HULL_VERTICES) + " / RMP2_MAX_HULL_FACES = " +
+                                                    std::to_string(RMP2_MAX_HULL_FACES));
+  }
+  for (size_t i = 0; i < (size_t)vert_offset[n]; ++i)
+    if (!std::isfinite(verts[3 * i]) || !std::isfinite(verts[3 * i + 1]) || !std::isfinite(verts[3 * i + 2]))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": vertex " + std::to_string(i) + " is not finite");
+  for (size_t i = 0; i < (size_t)face_offset[n]; ++i) {
+    const float* pl = planes + 4 * i;
+    const double n2 = (double)pl[0] * pl[0] + (double)pl[1] * pl[1] + (double)pl[2] * pl[2];
+    if (!std::isfinite(pl[3]) || !(std::fabs(n2 - 1.0) <= 1e-4))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": plane " + std::to_string(i) + " needs a unit normal and a finite offset");
+  }
+  return RMP2_OK;
+}
+
+// Uploads the handle's hull arrays (rmp2_host.h: one set, for whichever hull geometry is on) and its HullProg.  Synchronous copies:
+// no launch still reads the old hulls.
+static int upload_hulls(rmp2_handle* h, const std::vector<float4>& hv, const std::vector<float4>& hpl, const HullProg& hp) {
+  if (int rc = use_device(h)) return rc;
+  const size_t nv = std::max<size_t>(hv.size(), 1), nf = std::max<size_t>(hpl.size(), 1);
+  if (nv > h->hull_verts_cap) {
+    h->hull_verts_cap = 0;
+    if (int rc = realloc_device(h, &h->d_hull_verts, sizeof(float4) * nv)) return rc;
+    h->hull_verts_cap = nv;
+  }
+  if (nf > h->hull_planes_cap) {
+    h->hull_planes_cap = 0;
+    if (int rc = realloc_device(h, &h->d_hull_planes, sizeof(float4) * nf)) return rc;
+    h->hull_planes_cap = nf;
+  }
+  if (!h->d_hull) HIP_TRY(h, hipMalloc(&h->d_hull, sizeof(HullProg)));
+  if (!hv.empty()) HIP_TRY(h, hipMemcpy(h->d_hull_verts, hv.data(), sizeof(float4) * hv.size(), hipMemcpyHostToDevice));
+  if (!hpl.empty()) HIP_TRY(h, hipMemcpy(h->d_hull_planes, hpl.data(), sizeof(float4) * hpl.size(), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->d_hull, &hp, sizeof(HullProg), hipMemcpyHostToDevice));
+  return RMP2_OK;
+}
+
 int rmp2_set_link_hulls(rmp2_handle* h, int32_t n_hulls, const int32_t* vert_offset, const float* verts, const int32_t* face_offset,
                         const float* planes) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
@@ -3530,57 +3528,19 @@ int rmp2_set_link_hulls(rmp2_handle* h, int32_t n_hulls, const int32_t* vert_off
   if (n_hulls != L)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: one hull per distance / attached-point leaf (" + std::to_string(L) + "), got " +
                                                   std::to_string(n_hulls));
-  if (!vert_offset || !verts || !face_offset || !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: null array");
-  if (vert_offset[0] != 0 || face_offset[0] != 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: offsets must start at 0");
+  if (int rc = check_hulls(h, "link hulls", "link hull", false, L, vert_offset, verts, face_offset, planes)) return rc;
   HullProg hp;
   std::memset(&hp, 0, sizeof(hp));
   hp.n_leaves = L;
   for (int l = 0; l < RMP2_MAX_LEAVES; ++l) hp.ord_of_leaf[l] = -1;
-  for (int o = 0; o < L; ++o) {
-    const int nv = vert_offset[o + 1] - vert_offset[o], nf = face_offset[o + 1] - face_offset[o];
-    if (nv < 1 || nf < 1)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hull " + std::to_string(o) + ": needs at least one vertex and one face plane");
-    if (nv > RMP2_MAX_HULL_VERTICES || nf > RMP2_MAX_HULL_FACES)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hull " + std::to_string(o) + ": " + std::to_string(nv) + " vertices / " +
-                                                    std::to_string(nf) + " faces, at most RMP2_MAX_HULL_VERTICES = " +
-                                                    std::to_string(RMP2_MAX_HULL_VERTICES) + " / RMP2_MAX_HULL_FACES = " +
-                                                    std::to_string(RMP2_MAX_HULL_FACES));
-    hp.ord_of_leaf[h->pair_leaves[o]] = o;
-    hp.is_point[o] = h->pair_leaf_point[o];
+  for (int o = 0; o <= L; ++o) {
+    if (o < L) hp.ord_of_leaf[h->pair_leaves[o]] = o, hp.is_point[o] = h->pair_leaf_point[o];
     hp.vert_off[o] = vert_offset[o], hp.face_off[o] = face_offset[o];
   }
-  hp.vert_off[L] = vert_offset[L], hp.face_off[L] = face_offset[L];
-  const size_t NV = (size_t)vert_offset[L], NF = (size_t)face_offset[L];
-  std::vector<float4> hv(NV), hpl(NF);
-  for (size_t i = 0; i < NV; ++i) {
-    hv[i] = make_float4(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2], 0.f);
-    if (!std::isfinite(hv[i].x) || !std::isfinite(hv[i].y) || !std::isfinite(hv[i].z))
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: vertex " + std::to_string(i) + " is not finite");
-  }
-  for (size_t i = 0; i < NF; ++i) {
-    hpl[i] = make_float4(planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]);
-    const double n2 = (double)hpl[i].x * hpl[i].x + (double)hpl[i].y * hpl[i].y + (double)hpl[i].z * hpl[i].z;
-    if (!std::isfinite(hpl[i].w) || !(std::fabs(n2 - 1.0) <= 1e-4))
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "link hulls: plane " + std::to_string(i) + " needs a unit normal and a finite offset");
-  }
-  if (int rc = use_device(h)) return rc;
-  if (NV > h->hull_verts_cap) {
-    if (h->d_hull_verts) HIP_TRY(h, hipFree(h->d_hull_verts));
-    h->d_hull_verts = nullptr, h->hull_verts_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_hull_verts, sizeof(float4) * NV));
-    h->hull_verts_cap = NV;
-  }
-  if (NF > h->hull_planes_cap) {
-    if (h->d_hull_planes) HIP_TRY(h, hipFree(h->d_hull_planes));
-    h->d_hull_planes = nullptr, h->hull_planes_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_hull_planes, sizeof(float4) * NF));
-    h->hull_planes_cap = NF;
-  }
-  if (!h->d_hull) HIP_TRY(h, hipMalloc(&h->d_hull, sizeof(HullProg)));
-  // (synchronous copies: no launch still reads the old hulls)
-  HIP_TRY(h, hipMemcpy(h->d_hull_verts, hv.data(), sizeof(float4) * NV, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->d_hull_planes, hpl.data(), sizeof(float4) * NF, hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->d_hull, &hp, sizeof(HullProg), hipMemcpyHostToDevice));
+  std::vector<float4> hv(vert_offset[L]), hpl(face_offset[L]);
+  for (size_t i = 0; i < hv.size(); ++i) hv[i] = make_float4(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2], 0.f);
+  for (size_t i = 0; i < hpl.size(); ++i) hpl[i] = make_float4(planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]);
+  if (int rc = upload_hulls(h, hv, hpl, hp)) return rc;
   h->hull_n = L;
   return RMP2_OK;
 }
@@ -3600,50 +3560,17 @@ int rmp2_set_self_collision_hulls(rmp2_handle* h, int32_t n_pairs, const int32_t
   if (n_hulls != F + 1)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: one hull entry per frame and the base (" + std::to_string(F + 1) +
                                                   "), got " + std::to_string(n_hulls));
-  if (!vert_offset || !verts || !face_offset || !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: null array");
-  if (vert_offset[0] != 0 || face_offset[0] != 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: offsets must start at 0");
-  for (int e = 0; e <= F; ++e) {
-    const int nv = vert_offset[e + 1] - vert_offset[e], nf = face_offset[e + 1] - face_offset[e];
-    if (nv < 0 || nf < 0 || (nv == 0) != (nf == 0))
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull entry " + std::to_string(e) + ": needs vertices and face planes, or neither");
-    if (nv > RMP2_MAX_HULL_VERTICES || nf > RMP2_MAX_HULL_FACES)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull entry " + std::to_string(e) + ": " + std::to_string(nv) + " vertices / " +
-                                                    std::to_string(nf) + " faces, at most RMP2_MAX_HULL_VERTICES = " +
-                                                    std::to_string(RMP2_MAX_HULL_VERTICES) + " / RMP2_MAX_HULL_FACES = " +
-                                                    std::to_string(RMP2_MAX_HULL_FACES));
-  }
-  const size_t NV = (size_t)vert_offset[F + 1], NF = (size_t)face_offset[F + 1];
-  for (size_t i = 0; i < NV; ++i)
-    if (!std::isfinite(verts[3 * i]) || !std::isfinite(verts[3 * i + 1]) || !std::isfinite(verts[3 * i + 2]))
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: vertex " + std::to_string(i) + " is not finite");
-  for (size_t i = 0; i < NF; ++i) {
-    const float* pl = planes + 4 * i;
-    const double n2 = (double)pl[0] * pl[0] + (double)pl[1] * pl[1] + (double)pl[2] * pl[2];
-    if (!std::isfinite(pl[3]) || !(std::fabs(n2 - 1.0) <= 1e-4))
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "hull self pairs: plane " + std::to_string(i) + " needs a unit normal and a finite offset");
-  }
-  // the pairs (rmp2_set_self_collision's rule), grouped by ordinal
-  int ord_of_leaf[RMP2_MAX_LEAVES];
-  for (int l = 0; l < RMP2_MAX_LEAVES; ++l) ord_of_leaf[l] = -1;
-  for (int o = 0; o < L; ++o) ord_of_leaf[h->pair_leaves[o]] = o;
-  std::vector<std::vector<int>> by_leaf(L);
+  if (int rc = check_hulls(h, "hull self pairs", "hull entry", true, F + 1, vert_offset, verts, face_offset, planes)) return rc;
+  // the pairs (rmp2_set_self_collision's rule, and no pair on an empty entry), grouped by ordinal
   auto entry_empty = [&](int e) { return vert_offset[e + 1] == vert_offset[e]; };
-  for (int k = 0; k < n_pairs; ++k) {
-    const int leaf = pairs[2 * k], b = pairs[2 * k + 1];
-    const int o = (leaf >= 0 && leaf < h->n_leaves) ? ord_of_leaf[leaf] : -1;
-    if (o < 0)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": leaf " + std::to_string(leaf) +
-                                                    " is not a distance or attached-point leaf");
-    if (b < -1 || b >= F)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B " + std::to_string(b) + " out of range");
-    if (b == h->pair_leaf_frame[o])
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": frame B is the leaf's own frame");
-    if (entry_empty(h->pair_leaf_frame[o]) || entry_empty(b < 0 ? F : b))
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": its hull entry " +
-                                                    std::to_string(entry_empty(h->pair_leaf_frame[o]) ? h->pair_leaf_frame[o] : (b < 0 ? F : b)) +
-                                                    " is empty");
-    by_leaf[o].push_back(b);
-  }
+  std::vector<std::vector<int>> by_leaf;
+  int rc = group_self_pairs(h, n_pairs, pairs, by_leaf, [&](int k, int o, int b) {
+    const int ea = h->pair_leaf_frame[o], eb = b < 0 ? F : b;
+    if (!entry_empty(ea) && !entry_empty(eb)) return RMP2_OK;
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "self pair " + std::to_string(k) + ": its hull entry " +
+                                                  std::to_string(entry_empty(ea) ? ea : eb) + " is empty");
+  });
+  if (rc) return rc;
   // device arrays: the pair leaves' hulls first, in ordinal order (the obstacle half's HullProg), then every other non-empty entry
   HullProg hp;
   std::memset(&hp, 0, sizeof(hp));
@@ -3700,27 +3627,9 @@ int rmp2_set_self_collision_hulls(rmp2_handle* h, int32_t n_pairs, const int32_t
   }
   sp.n_pairs = j;
   hp.n_extra = j;
-  if (int rc = use_device(h)) return rc;
-  const size_t nv_all = hv.size() > 0 ? hv.size() : 1, nf_all = hpl.size() > 0 ? hpl.size() : 1;
-  if (nv_all > h->shull_verts_cap) {
-    if (h->d_shull_verts) HIP_TRY(h, hipFree(h->d_shull_verts));
-    h->d_shull_verts = nullptr, h->shull_verts_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_shull_verts, sizeof(float4) * nv_all));
-    h->shull_verts_cap = nv_all;
-  }
-  if (nf_all > h->shull_planes_cap) {
-    if (h->d_shull_planes) HIP_TRY(h, hipFree(h->d_shull_planes));
-    h->d_shull_planes = nullptr, h->shull_planes_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_shull_planes, sizeof(float4) * nf_all));
-    h->shull_planes_cap = nf_all;
-  }
+  if ((rc = upload_hulls(h, hv, hpl, hp))) return rc;
   if (!h->d_shull) HIP_TRY(h, hipMalloc(&h->d_shull, sizeof(SelfHullProg)));
-  if (!h->d_shull_obs) HIP_TRY(h, hipMalloc(&h->d_shull_obs, sizeof(HullProg)));
-  // (synchronous copies: no launch still reads the old hulls)
-  if (!hv.empty()) HIP_TRY(h, hipMemcpy(h->d_shull_verts, hv.data(), sizeof(float4) * hv.size(), hipMemcpyHostToDevice));
-  if (!hpl.empty()) HIP_TRY(h, hipMemcpy(h->d_shull_planes, hpl.data(), sizeof(float4) * hpl.size(), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->d_shull, &sp, sizeof(SelfHullProg), hipMemcpyHostToDevice));
-  HIP_TRY(h, hipMemcpy(h->d_shull_obs, &hp, sizeof(HullProg), hipMemcpyHostToDevice));
+  HIP_TRY(h, hipMemcpy(h->d_shull, &sp, sizeof(SelfHullProg), hipMemcpyHostToDevice));   // (synchronous: no launch still reads it)
   h->shull_slots = sp.n_slots;
   h->shull_leaf_empty = leaf_empty;
   h->self_counts = counts;
@@ -3752,27 +3661,15 @@ static int differentiate_impl(rmp2_handle* h, const float* q, const float* qd, i
   // The per-robot scratch belongs to the handle: the differentiate entry points are single-stream per handle
   // (include/rmp2.h).  It grows monotonically; hipFree synchronises the device, so no launch still reads the old one.
   if ((size_t)R > h->scratch_robots) {
-    if (h->d_scratch) HIP_TRY(h, hipFree(h->d_scratch));
-    h->d_scratch = nullptr;
     h->scratch_robots = 0;
-    HIP_TRY(h, hipMalloc(&h->d_scratch, sizeof(float) * 6 * RMP2_MAX_DOF * (size_t)R));
+    if (int rc = realloc_device(h, &h->d_scratch, sizeof(float) * 6 * RMP2_MAX_DOF * (size_t)R)) return rc;
     h->scratch_robots = (size_t)R;
   }
   const int blocks = (R + kWave - 1) / kWave;
-  switch (h->n_slots_full) {
-    case 0:
-      hipLaunchKernelGGL((rmp2_diff_kernel<0>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, qd, frame, x, xd, J, c,
-                         h->d_scratch, R, euler);
-      break;
-    case 1:
-      hipLaunchKernelGGL((rmp2_diff_kernel<1>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, qd, frame, x, xd, J, c,
-                         h->d_scratch, R, euler);
-      break;
-    default:
-      hipLaunchKernelGGL((rmp2_diff_kernel<2>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, qd, frame, x, xd, J, c,
-                         h->d_scratch, R, euler);
-      break;
-  }
+  with_slots(h->n_slots_full, [&](auto S) {
+    hipLaunchKernelGGL((rmp2_diff_kernel<S>), dim3(blocks), dim3(kWave), 0, s, h->d_prog_full, q, qd, frame, x, xd, J, c,
+                       h->d_scratch, R, euler);
+  });
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }

@@ -59,8 +59,11 @@ struct rmp2_handle {
   bool pair_begin_valid = false;
   float* d_scratch = nullptr;  // rmp2_differentiate scratch
   size_t scratch_robots = 0;
-  float* d_pairs = nullptr;    // p_link | p_obs of the closest-point stage when a step with link geometry runs as stage + explicit-pair step
-  size_t pairs_floats = 0;     // (floats per array)
+  // The stage buffer of a staged step (rmp2_hip.hip step_impl: link geometry beyond the fused limits, self collision or link hulls),
+  // whose pairs the explicit-pair step then reads.  At most one stage runs per step, so the routes share it; its layout and size
+  // depend on the route in use.  It grows to the largest need seen (a graph captured on a staged step stays valid until it grows).
+  float* d_stage = nullptr;
+  size_t stage_floats = 0;
   double* d_system = nullptr;  // [robots][n_dof * (n_dof + 1)] combined metric and force between the quad step and rmp2_pinv_kernel
   size_t system_robots = 0;
   // self collision (rmp2_set_self_collision): off while self_n_pairs == 0
@@ -71,25 +74,19 @@ struct rmp2_handle {
   std::vector<char> pair_leaf_point;    // 1: FK_POINT
   std::vector<int> self_counts;         // S_l per ordinal
   void* d_self = nullptr;               // SelfProg (rmp2_hip.hip)
-  float* d_self_buf = nullptr;          // p_link | p_obs | dist of the stage when a step runs as self stage + explicit-pair step
-  size_t self_buf_floats = 0;
-  // convex-hull link geometry (rmp2_set_link_hulls): off while hull_n == 0
-  int hull_n = 0;
+  // Convex hulls: one HullProg and one set of vertex / plane arrays, for whichever hull geometry is on -- link hulls
+  // (rmp2_set_link_hulls) or hull self pairs (rmp2_set_self_collision_hulls), which exclude each other.  With hull self pairs the
+  // HullProg covers the pair leaves' hulls (the obstacle half); the arrays hold those first, in ordinal order, then the other entries.
+  int hull_n = 0;                       // link hulls: off while 0
   void* d_hull = nullptr;               // HullProg (rmp2_hip.hip)
   float4* d_hull_verts = nullptr;       // (x, y, z, -) per vertex, hulls back to back
   float4* d_hull_planes = nullptr;      // (n, d) per face
   size_t hull_verts_cap = 0, hull_planes_cap = 0;
-  float* d_hull_buf = nullptr;          // p_link | p_obs | dist of the stage when a step runs as hull stage + explicit-pair step
-  size_t hull_buf_floats = 0;
   // hull self pairs (rmp2_set_self_collision_hulls): the self-collision list above, on hulls while self_hulls is set
   bool self_hulls = false;
   bool shull_leaf_empty = false;        // some pair leaf has no hull: no obstacle pairs on such a handle
   int shull_slots = 0;                  // frame slots of the stage's LDS
   void* d_shull = nullptr;              // SelfHullProg (rmp2_hip.hip)
-  void* d_shull_obs = nullptr;          // HullProg of the pair leaves' hulls (the obstacle half)
-  float4* d_shull_verts = nullptr;      // the pair leaves' hulls first (ordinal order), then the other entries
-  float4* d_shull_planes = nullptr;
-  size_t shull_verts_cap = 0, shull_planes_cap = 0;
   // inverse dynamics (rmp2_set_inertials): off while inert_n == 0
   int inert_n = 0;
   float* d_inert = nullptr;             // [n_frames][10] inertial records

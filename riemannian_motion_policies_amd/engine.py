@@ -34,6 +34,19 @@ def _require_resident(device, **tensors) -> None:
                              "launch, later in-place writes to the original would never be seen")
 
 
+def _hull_arrays(hulls, what: str, entries: str, n: int):
+    """(vert_offset, verts, face_offset, planes) of `hulls` -- a urdf hull set or that tuple -- as int32 / float32 arrays of n entries;
+    `what` names the feature and `entries` says what the n entries are in the messages."""
+    vo, v, fo, p = (hulls.vert_offset, hulls.verts, hulls.face_offset, hulls.planes) if hasattr(hulls, "planes") else hulls
+    vo, fo = np.ascontiguousarray(vo, dtype=np.int32), np.ascontiguousarray(fo, dtype=np.int32)
+    v, p = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4)
+    if vo.shape != (n + 1,) or fo.shape != (n + 1,):
+        raise ValueError(f"{what}: {entries} ({n}), offsets [{n + 1}]")
+    if vo[-1] != len(v) or fo[-1] != len(p):
+        raise ValueError(f"{what}: the offsets must end at the number of vertices / planes")
+    return vo, v, fo, p
+
+
 class Engine:
     def __init__(self, desc: D.Desc, device: int | torch.device = 0):
         if not torch.cuda.is_available():
@@ -50,6 +63,7 @@ class Engine:
         _native.check(self._lib.rmp2_create(C.byref(desc), self.device.index or 0, C.byref(self._h)))
         self._dist_leaves = D.distance_leaf_indices(desc)
         self._self_counts = None   # self pairs per pair leaf (set_self_collision), None = off
+        self._self_key = None      # the self-pair list and geometry the handle holds (set_self_collision / _hulls), None = off
         self._hulls_key = None     # the link hulls the handle holds (set_link_hulls), None = off
         self._inertials_key = None  # the inertial table and gravity the handle holds (set_inertials), None = off
 
@@ -357,14 +371,8 @@ class Engine:
                 _native.check(self._lib.rmp2_set_link_hulls(self._h, 0, None, None, None, None), self._h)
             self._hulls_key = None
             return
-        vo, v, fo, p = (hulls.vert_offset, hulls.verts, hulls.face_offset, hulls.planes) if hasattr(hulls, "planes") else hulls
-        vo, fo = np.ascontiguousarray(vo, dtype=np.int32), np.ascontiguousarray(fo, dtype=np.int32)
-        v, p = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4)
         n = len(self._dist_leaves)
-        if vo.shape != (n + 1,) or fo.shape != (n + 1,):
-            raise ValueError(f"link hulls: one hull per distance / attached-point leaf ({n}), offsets [{n + 1}]")
-        if vo[-1] != len(v) or fo[-1] != len(p):
-            raise ValueError("link hulls: the offsets must end at the number of vertices / planes")
+        vo, v, fo, p = _hull_arrays(hulls, "link hulls", "one hull per distance / attached-point leaf", n)
         key = (vo.tobytes(), v.tobytes(), fo.tobytes(), p.tobytes())
         if key == self._hulls_key:
             return   # (the same hulls: nothing to upload)
@@ -402,21 +410,14 @@ class Engine:
                 _native.check(self._lib.rmp2_set_self_collision(self._h, 0, None, None), self._h)
             self._self_counts, self._self_key = None, None
             return
-        dl = self._dist_leaves
-        if any(not 0 <= a < len(dl) for a, _ in pairs):
-            raise ValueError(f"leaf ordinals must lie in [0, {len(dl)})")
+        arr, counts = self._self_rows(pairs)
         caps = np.ascontiguousarray(capsules, dtype=np.float32)
         if caps.shape != (self.n_frames + 1, 8):
             raise ValueError(f"capsules must be [{self.n_frames + 1}, 8] (one per frame, then the base link)")
         key = (tuple(pairs), caps.tobytes())
-        if self._self_counts is not None and getattr(self, "_self_key", None) == key:
+        if self._self_counts is not None and self._self_key == key:
             return   # (the same list: nothing to upload)
-        arr = np.ascontiguousarray([(dl[a], b) for a, b in pairs], dtype=np.int32)
         _native.check(self._lib.rmp2_set_self_collision(self._h, len(pairs), arr.ctypes.data, caps.ctypes.data), self._h)
-        counts = [0] * len(dl)
-        for a, _ in pairs:
-            counts[a] += 1
-        # (the library keeps each leaf's pairs in the order given, leaves in leaf order)
         self._self_counts, self._self_key = counts, key
 
     def set_self_collision_hulls(self, pairs, hulls) -> None:
@@ -428,34 +429,31 @@ class Engine:
         if not pairs:
             self.set_self_collision([], None)
             return
+        arr, counts = self._self_rows(pairs)
+        n = self.n_frames + 1
+        vo, v, fo, p = _hull_arrays(hulls, "hull self pairs", "one hull entry per frame and the base", n)
+        key = ("hulls", tuple(pairs), vo.tobytes(), v.tobytes(), fo.tobytes(), p.tobytes())
+        if self._self_counts is not None and self._self_key == key:
+            return   # (the same list: nothing to upload)
+        _native.check(self._lib.rmp2_set_self_collision_hulls(self._h, len(pairs), arr.ctypes.data, n, vo.ctypes.data, v.ctypes.data,
+                                                              fo.ctypes.data, p.ctypes.data), self._h)
+        self._self_counts, self._self_key = counts, key
+
+    def _self_rows(self, pairs):
+        """The (leaf ordinal, frame B) list of the self-collision setters as the library's int32 (leaf, B) rows, and the pairs per
+        leaf ordinal (the library keeps each leaf's pairs in the order given, leaves in leaf order)."""
         dl = self._dist_leaves
         if any(not 0 <= a < len(dl) for a, _ in pairs):
             raise ValueError(f"leaf ordinals must lie in [0, {len(dl)})")
-        vo, v, fo, p = (hulls.vert_offset, hulls.verts, hulls.face_offset, hulls.planes) if hasattr(hulls, "planes") else hulls
-        vo, fo = np.ascontiguousarray(vo, dtype=np.int32), np.ascontiguousarray(fo, dtype=np.int32)
-        v, p = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3), np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4)
-        n = len(vo) - 1
-        if n != self.n_frames + 1 or len(fo) != n + 1:
-            raise ValueError(f"hull self pairs: one hull entry per frame and the base ({self.n_frames + 1}), offsets "
-                             f"[{self.n_frames + 2}]")
-        if vo[-1] != len(v) or fo[-1] != len(p):
-            raise ValueError("hull self pairs: the offsets must end at the number of vertices / planes")
-        key = ("hulls", tuple(pairs), vo.tobytes(), v.tobytes(), fo.tobytes(), p.tobytes())
-        if self._self_counts is not None and getattr(self, "_self_key", None) == key:
-            return   # (the same list: nothing to upload)
-        arr = np.ascontiguousarray([(dl[a], b) for a, b in pairs], dtype=np.int32)
-        _native.check(self._lib.rmp2_set_self_collision_hulls(self._h, len(pairs), arr.ctypes.data, n, vo.ctypes.data, v.ctypes.data,
-                                                              fo.ctypes.data, p.ctypes.data), self._h)
         counts = [0] * len(dl)
         for a, _ in pairs:
             counts[a] += 1
-        self._self_counts, self._self_key = counts, key
+        return np.ascontiguousarray([(dl[a], b) for a, b in pairs], dtype=np.int32), counts
 
     @property
     def has_self_hulls(self) -> bool:
         """True while the self pairs are on hulls (set_self_collision_hulls)."""
-        key = getattr(self, "_self_key", None)
-        return self._self_counts is not None and key is not None and key[0] == "hulls"
+        return self._self_counts is not None and self._self_key is not None and self._self_key[0] == "hulls"
 
     @property
     def self_counts(self):

@@ -1,6 +1,7 @@
 """Hull-versus-hull self pairs on the GPU (include/rmp2.h rmp2_set_self_collision_hulls): the stage against the fp64 brute-force
 restatement (tests/hull_pair_reference.py), the finger pairs' symmetry, the bound by the capsules, the staged step against the CPU
-oracle, bit-exact composition with the hull obstacle stage, switching, the refusals and the class surface."""
+oracle, bit-exact composition with the hull obstacle stage, switching, the staged routes sharing one handle, the refusals and the class
+surface."""
 import ctypes as C
 import os
 
@@ -327,6 +328,40 @@ def test_switching(torch_mod, golden_dir):
     assert not torch.equal(want_hulls, want_fresh) and not torch.equal(want_hulls, want_caps)
     with pytest.raises(ValueError):
         eng.step(q, qd, goal)        # distance leaves and no obstacles: refused again once the self pairs are off
+
+
+def test_staged_routes_share_the_handle(torch_mod, golden_dir):
+    """One handle through every staged route in turn: its one stage buffer grows and is reused, and its one set of hull arrays is
+    overwritten, across routes.  Each step is bit-equal to a fresh handle set up for that route alone."""
+    torch = torch_mod
+    from riemannian_motion_policies_amd import configs as Cf, urdf as U
+    table, desc, pairs, caps = _setup("config3")
+    hulls = _hulls(golden_dir)
+    rng = np.random.default_rng(31)
+    s = Cf.sample_panda_states(rng, 3000)
+    q, qd, goal = (torch.from_numpy(s[k]).cuda() for k in ("q", "qd", "goal"))
+    sp = torch.from_numpy(Cf.sample_spheres(rng, 32)).cuda()
+    cyl = torch.from_numpy(Cf.sample_cylinders(rng, 16)).cuda()
+    lc = torch.from_numpy(U.link_capsules(U.PANDA_URDF, table, Cf.CONTROL_POINT_FRAMES)).cuda()
+    routes = [   # (route, setup of the handle, its obstacles, robots)
+        ("link hulls", lambda e: e.set_link_hulls(_leaf_hulls(desc, hulls)), lambda e: e.obstacles(spheres=sp), 3000),
+        ("self collision on capsules", lambda e: e.set_self_collision(pairs, caps), lambda e: e.obstacles(spheres=sp), 3000),
+        ("hull self pairs", lambda e: e.set_self_collision_hulls(pairs, hulls), lambda e: e.obstacles(spheres=sp), 3000),
+        ("staged link capsules", lambda e: None,
+         lambda e: e.obstacles(spheres=cyl, primitive="cylinder", link_capsules=lc), 3000),
+        ("link hulls, smaller fleet", lambda e: e.set_link_hulls(_leaf_hulls(desc, hulls)), lambda e: e.obstacles(spheres=sp), 1000),
+    ]
+    eng = _engine(desc)
+    for name, setup, obstacles, R in routes:
+        eng.set_link_hulls(None)
+        eng.set_self_collision([], None)
+        setup(eng)
+        got = eng.step(q[:R], qd[:R], goal[:R], obstacles=obstacles(eng))
+        fresh = _engine(desc)
+        setup(fresh)
+        want = fresh.step(q[:R], qd[:R], goal[:R], obstacles=obstacles(fresh))
+        torch.cuda.synchronize()
+        assert torch.equal(got, want), (name, (got - want).abs().max().item())
 
 
 def test_refusals(torch_mod, golden_dir):
