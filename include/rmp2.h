@@ -259,6 +259,14 @@ int rmp2_leaf_evaluate(int device, const rmp2_leaf *leaf, int32_t k, const float
  * (and the sanitizer build, tools/asan_compile_program.sh) can exercise without a GPU. */
 int rmp2_validate(const rmp2_desc *desc);
 
+/* Host-side view of what the program compiler prepares for the quad mapping's structured identity-leaf loop: when EVERY
+ * identity-map leaf of the set is JointDamping, CSpaceBiasing, configuration-space biasing or JointVelocityCap, one 32-word
+ * record per such leaf, in execution order, is written to `records` (at most `capacity` of them) --
+ *   word 0 kind (int32) | 1 P[0] - P[1] | 2 P[1] - 1e-6f | 3 P[0] + P[4] (fp32, rounded once) | 4..15 P[0..11] | 16..31 vec_a[0..15]
+ * -- and their number is returned; 0 when the set has no identity leaf or a dense one (JointLimitAvoidance, TargetPolicy on
+ * the identity map: such a set keeps the general loop), a negative RMP2_ERR_* code as rmp2_validate.  Needs no HIP device. */
+int rmp2_identity_records(const rmp2_desc *desc, void *records, int32_t capacity);
+
 /* Environment variables read by rmp2_create (and by nothing else).  They are DIAGNOSTIC overrides of the per-call kernel
  * dispatch, used by the parity tests and the profiling tools to force every mapping over the same inputs; all choices
  * produce the same numbers to fp32 rounding, none is needed for correctness, and an unset variable means "by fleet size":

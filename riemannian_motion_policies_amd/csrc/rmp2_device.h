@@ -64,6 +64,29 @@ struct OpCtl {
   int32_t leaf_begin, leaf_count;
 };
 static_assert(sizeof(DevOp) % 16 == 0 && sizeof(DevLeaf) % 16 == 0, "program records must be 16-byte multiples");
+// The record of a STRUCTURED identity-map leaf (JointDamping, CSpaceBiasing, configuration-space biasing: metric m * I;
+// JointVelocityCap: a constant plus a diagonal) for the quad kernel's structured identity-leaf loop: fixed layout, one
+// cache-line-aligned 64-byte head (one scalar load) followed by the leaf's per-dof vector.  The head carries the wave-uniform
+// fp32 values the general loop derives from the parameters every step; they are formed on the host in float, so the bits are
+// the ones the kernel would form.
+struct alignas(64) IdLeafRec {
+  int32_t kind;
+  float cutoff;   // P[0] - P[1]     (JointVelocityCap: velocity beyond which the cap acts)
+  float rlimit;   // P[1] - 1e-6f    (JointVelocityCap: clamp of the ratio's numerator)
+  float msum;     // P[0] + P[4]     (CSpaceBiasing: the metric scalar)
+  float P[RMP2_MAX_PARAMS];
+  float va[RMP2_MAX_DOF];
+};
+struct IdLeafHead {
+  int32_t kind;
+  float cutoff, rlimit, msum;
+  float P[RMP2_MAX_PARAMS];
+};
+static_assert(sizeof(IdLeafRec) == 128 && sizeof(IdLeafHead) == 64 && offsetof(IdLeafRec, va) == 64, "IdLeafRec: 64-byte head, then va");
+__host__ __device__ inline bool id_leaf_structured(int kind) {
+  return kind == RMP2_LEAF_JOINT_DAMPING || kind == RMP2_LEAF_CSPACE_BIASING || kind == RMP2_LEAF_CONFIG_SPACE_BIASING ||
+         kind == RMP2_LEAF_JOINT_VELOCITY_CAP;
+}
 
 struct DevProgram {
   int32_t n_ops, n_dof, n_frames, n_leaves;
@@ -94,6 +117,10 @@ struct DevProgram {
     int32_t leaf_begin, leaf_count;  // range in exec_leaves
   } leaf_frames[kMaxOps];
   DevLeaf exec_leaves[RMP2_MAX_LEAVES];
+  // Identity-map leaves in execution order as IdLeafRec, filled when EVERY identity leaf of the set is structured
+  // (id_structured = 1; else 0 and the records are zero: a set with a dense identity leaf keeps the general loop).
+  int32_t id_structured;
+  IdLeafRec id_recs[RMP2_MAX_LEAVES];
 };
 
 // Local transform of one frame as an affine function of (cos q, sin q, q), precomputed on the host in fp64:

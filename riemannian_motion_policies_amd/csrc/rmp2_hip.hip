@@ -2037,6 +2037,21 @@ int compile_program(const rmp2_desc& d, DevProgram& P, int& n_slots, std::string
       last = i;
     }
   for (int i = 0; i < nid; ++i) P.exec_leaves[nfk + i] = P.leaves[P.id_leaves[i]];  // (nfk + nid = n_leaves <= RMP2_MAX_LEAVES)
+  // the structured identity-leaf records of the quad kernel (rmp2_device.h IdLeafRec): all of them or none
+  P.id_structured = nid > 0 ? 1 : 0;
+  for (int i = 0; i < nid; ++i)
+    if (!id_leaf_structured(P.leaves[P.id_leaves[i]].kind)) P.id_structured = 0;
+  std::memset(P.id_recs, 0, sizeof(P.id_recs));
+  for (int i = 0; i < nid && P.id_structured; ++i) {
+    const DevLeaf& lf = P.leaves[P.id_leaves[i]];
+    IdLeafRec& r = P.id_recs[i];
+    r.kind = lf.kind;
+    // (volatile: the three values are rounded to float one operation at a time, as the kernel forms them)
+    volatile float cutoff = lf.P[0] - lf.P[1], rlimit = lf.P[1] - 1e-6f, msum = lf.P[0] + lf.P[4];
+    r.cutoff = cutoff, r.rlimit = rlimit, r.msum = msum;
+    for (int c = 0; c < RMP2_MAX_PARAMS; ++c) r.P[c] = lf.P[c];
+    for (int c = 0; c < RMP2_MAX_DOF; ++c) r.va[c] = lf.va[c];
+  }
   for (int k = 0; k < F; ++k) {
     const DevOp& o = P.ops[k];
     P.ops[k].ctl = (o.restore + 2) | ((o.save + 1) << 2) | (o.jtype << 4) | ((o.qidx + 1) << 6) | ((o.leaf_count > 0 ? 1 : 0) << 11);
@@ -2398,6 +2413,20 @@ int rmp2_validate(const rmp2_desc* desc) {
   return compile_desc(*desc, P[0], n_slots, P[1], n_slots_full, hops);
 }
 
+int rmp2_identity_records(const rmp2_desc* desc, void* records, int32_t capacity) {
+  if (!desc || (capacity > 0 && !records)) return fail(nullptr, RMP2_ERR_INVALID_ARGUMENT, "null argument");
+  if (desc->abi_version != RMP2_ABI_VERSION)
+    return fail(nullptr, RMP2_ERR_ABI_MISMATCH, "rmp2_desc.abi_version does not match the library");
+  std::vector<DevProgram> P(2);
+  int n_slots = 0, n_slots_full = 0;
+  std::vector<HexOp> hops;
+  if (int rc = compile_desc(*desc, P[0], n_slots, P[1], n_slots_full, hops)) return rc;
+  if (!P[0].id_structured) return 0;
+  const int n = P[0].n_id_leaves;
+  std::memcpy(records, P[0].id_recs, sizeof(IdLeafRec) * (size_t)std::max(0, std::min(n, (int)capacity)));
+  return n;
+}
+
 int rmp2_create(const rmp2_desc* desc, int device, rmp2_handle** out) {
   if (!desc || !out) return fail(nullptr, RMP2_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
@@ -2423,6 +2452,7 @@ int rmp2_create(const rmp2_desc* desc, int device, rmp2_handle** out) {
   h->n_template = h->n_dof <= 2 ? 2 : (h->n_dof <= 9 ? 9 : 16);
   h->strict = desc->solve_mode == RMP2_SOLVE_PINV;
   h->n_id_leaves = P.n_id_leaves;
+  h->id_structured = P.id_structured != 0;
   h->likely_singular = true;
   for (int l = 0; l < desc->n_leaves; ++l) {
     const rmp2_leaf& lf = desc->leaves[l];

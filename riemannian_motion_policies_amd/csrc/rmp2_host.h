@@ -26,6 +26,7 @@ struct rmp2_handle {
   bool has_distance = false;
   bool has_point = false;  // attached-point leaves (CollisionAvoidance): hex and lane-per-robot kernels
   int n_id_leaves = 0;
+  bool id_structured = false;  // every identity leaf is m * I or the velocity cap: the quad kernel's structured identity-leaf loop
   int n_leaf_ops = 0;
   uint32_t rev_mask = 0;
   float cull_c0 = 0.f;  // max over the distance leaves of (metric_modulation_radius + margin): beyond it a pair is culled
@@ -92,6 +93,8 @@ struct rmp2_handle {
   float* d_inert = nullptr;             // [n_frames][10] inertial records
   float base_acc[3] = {0.f, 0.f, 9.81f};  // -g
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
+  mutable bool quad_id_lean = false;       // the last quad launch ran the structured identity-leaf loop (launch_quad)
+  mutable std::string last_kernel_text;    // last_kernel with that loop named
   mutable const char* last_kernel = "none";  // mapping the last control step / rollout was launched with (rmp2_last_kernel)
   std::string error;
 };
@@ -136,7 +139,7 @@ inline QuadHdr make_quad_hdr(const rmp2_handle* h) {
   return QuadHdr{h->n_ops_step, h->n_dof, h->n_id_leaves, h->n_leaves, h->goal_floats, h->n_leaf_ops, h->rev_mask,
                  h->hex_levels, h->n_fk_leaves, h->hex_is_chain, {h->dof_ops[0], h->dof_ops[1], h->dof_ops[2]}, h->cull_c0, h->strict ? 1 : 0,
                  h->prio_tail >= 0 ? h->prio_tail : 0, h->quad_skip_resolve ? 1 : 0, h->has_point ? 1 : 0, h->likely_singular ? 1 : 0,
-                 h->stream_stagger};
+                 h->stream_stagger, h->id_structured ? 1 : 0};
 }
 // rmp2_hex_tu.hip (false: the working set does not fit the CU's LDS -- the caller falls back to the quad mapping)
 bool launch_hex_n2(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs, const ObsArgs& o,

@@ -1209,6 +1209,8 @@ struct QuadHdr {
                         // rank-one form (rmp2_device.h rank_one_of)
   int32_t stagger;      // streamed explicit pairs (kObsExplicitStream): the wave in slot s of its SIMD starts (s & 3) * stagger * 3.4 us
                         // late (s_sleep), so that the four waves of a SIMD are not all in their streaming phase at once
+  int32_t id_lean;      // every identity leaf of the set is structured (m * I, velocity cap) and DevProgram::id_recs is filled: the
+                        // builds that carry the structured identity-leaf loop (kLeanId) take it for a full-width robot (rmp2_quad.h only)
 };
 
 __device__ __forceinline__ int gi_loc(int g, int n_ops) { return g * kSlot * quad_slots(n_ops); }
@@ -1742,6 +1744,148 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
         }
       }
   };
+  // ---- the same, for sets whose identity leaves are ALL structured (hdr.id_lean; config 3: damping, c-space biasing, velocity
+  // cap) on a robot that uses every dof of the template (n_dof == N, the Panda): a loop whose body holds those kinds only.  In
+  // the general loop above every kind shares one body -- the dense kinds' column ladders and full-precision log / exp sequences
+  // are most of its code and shape the registers of the part such a set executes.  Same expressions in the same order as above
+  // (every result bit is the general loop's); what differs:
+  //  * the leaf comes as an IdLeafRec (rmp2_device.h), fetched in one burst at the top of its trip, with the wave-uniform values
+  //    P[0] - P[1], P[1] - 1e-6f, P[0] + P[4] formed on the host;
+  //  * the row and column tests against n_dof are compile-time facts (rows 9 .. 11 of the last row block remain padding);
+  //  * the lane-selected diagonal addends (sub == c ? m : 0) of the m * I kinds are formed once per leaf for the four c.
+  // Compiled into the symmetric plain-step and plain-rollout builds of the 3..9-dof template; every other build, a robot with
+  // fewer dofs than the template and a set with a dense identity leaf keep the general loop.
+  constexpr bool kLeanId = N == 9 && !STAGE && SYM && LEAN;
+  auto identity_leaves_lean = [&]() __attribute__((always_inline)) {
+    int sd = sub;  // (opaque copy: the four lane predicates below live in this phase only)
+    if (MINW >= 3) asm volatile("" : "+v"(sd));
+    for (int li = 0; li < n_id; ++li) {
+      // the whole record in one burst: the 32 bytes of the head that the loop reads and the leaf's per-dof vector
+      // (va[0 .. 11]: a lane's rows are 4 m + sub), pinned here so that no scalar fetch waits behind a branch on the kind
+      const IdLeafRec& rec = prog->id_recs[li];
+      struct Head8 { int32_t kind; float cutoff, rlimit, msum, P[4]; };
+      struct Va12 { float v[12]; };
+      const Head8 ih = *reinterpret_cast<const Head8*>(&rec);
+      const Va12 vv = *reinterpret_cast<const Va12*>(rec.va);
+      asm volatile("" ::"s"(ih.kind), "s"(ih.cutoff), "s"(ih.rlimit), "s"(ih.msum), "s"(ih.P[0]), "s"(ih.P[1]), "s"(ih.P[2]), "s"(ih.P[3]),
+                   "s"(vv.v[0]), "s"(vv.v[1]), "s"(vv.v[2]), "s"(vv.v[3]), "s"(vv.v[4]), "s"(vv.v[5]), "s"(vv.v[6]), "s"(vv.v[7]),
+                   "s"(vv.v[8]), "s"(vv.v[9]), "s"(vv.v[10]), "s"(vv.v[11]));
+      const float* P = ih.P;
+      const float* va = vv.v;
+      // my rows' entries of va (padding rows of the last block read what pick4 reads: va[4 m + sub]); the four candidates
+      // as vector registers, so that the choice is three selects and not control flow
+      auto va_row = [&](int m) __attribute__((always_inline)) {
+        float a0 = va[4 * m], a1 = va[4 * m + 1], a2 = va[4 * m + 2], a3 = va[4 * m + 3];
+        asm volatile("" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
+        float r = a3;
+        r = sd == 2 ? a2 : r;
+        r = sd == 1 ? a1 : r;
+        r = sd == 0 ? a0 : r;
+        return r;
+      };
+      // diagonal metrics m * I:  A_ii += m (column j's diagonal lives in local row j >> 2 of lane sub == (j & 3)), f_i += m * xdd_i
+      auto add_diag = [&](float mdiag) __attribute__((always_inline)) {
+        const double dm = (double)mdiag;
+        double dsel[kQuad];
+#pragma unroll
+        for (int c = 0; c < kQuad; ++c) dsel[c] = (sd == c) ? dm : 0.0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) A[j >> 2][j] += dsel[j & 3];
+      };
+      if (ih.kind == RMP2_LEAF_JOINT_DAMPING) {  // rmp2.py:127-137
+        float s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) s2 += my_qd[j] * my_qd[j];
+        const float nrm = s2 > 0.f ? s2 * rsq1(s2) : 0.f;
+        const float mdiag = P[1] * nrm + P[2];
+#pragma unroll
+        for (int m = 0; m < ROWS; ++m) {
+          const int i = sub + kQuad * m;
+          const float qdi = my_qd[i < N ? i : 0];
+          const float acc = -(P[0] * nrm) * qdi;
+          fv[m] += (double)(mdiag * acc);
+        }
+        add_diag(mdiag);
+      } else if (ih.kind == RMP2_LEAF_CSPACE_BIASING) {  // rmp2.py:212-226
+        float s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          const float e = my_q[j] - va[j];
+          s2 += e * e;
+        }
+        const float nrm = sqrtf(s2);
+        const float mdiag = ih.msum;
+#pragma unroll
+        for (int m = 0; m < ROWS; ++m) {
+          const int i = sub + kQuad * m;
+          const int ii = i < N ? i : 0;
+          const float qi_ = my_q[ii], qdi = my_qd[ii];
+          const float e = qi_ - va_row(m);
+          const float pos = (nrm < P[3]) ? (-e * P[1]) : (-P[3] * (e / nrm) * P[1]);
+          const float acc = pos + (-P[2] * qdi);
+          fv[m] += (double)(mdiag * acc);
+        }
+        add_diag(mdiag);
+      } else if (ih.kind == RMP2_LEAF_CONFIG_SPACE_BIASING) {  // rmp.py:330-347
+        const float mdiag = P[2];
+#pragma unroll
+        for (int m = 0; m < ROWS; ++m) {
+          const int i = sub + kQuad * m;
+          const int ii = i < N ? i : 0;
+          const float qi_ = my_q[ii], qdi = my_qd[ii];
+          const float acc = P[0] * (va_row(m) - qi_) - P[1] * qdi;
+          fv[m] += (double)(mdiag * acc);
+        }
+        add_diag(mdiag);
+      } else {
+        // rmp2.py:100-112 (quirk Q4), as above:  A_ij += w ,  A_ii += d_i - w ,  f_i += w sum_j xdd_j + (d_i - w) xdd_i
+        const float cutoff = ih.cutoff;
+        const float w = P[3] / 1.0f;
+        float xo[ROWS], dg[ROWS], sx = 0.f;
+        bool row_in[ROWS];
+#pragma unroll
+        for (int m = 0; m < ROWS; ++m) {
+          const int i = sub + kQuad * m;
+          row_in[m] = kQuad * m + kQuad <= N || i < N;  // (i < n_dof with n_dof == N)
+          const float qdj = my_qd[i < N ? i : 0];
+          const float dv = fabsf(qdj) - cutoff;
+          const float sgn = (qdj > 0.f) ? 1.f : (qdj < 0.f ? -1.f : 0.f);
+          const float acc = -fabsf(P[2] * dv) * sgn;
+          xo[m] = (row_in[m] && !(fabsf(qdj) < cutoff)) ? acc : 0.f;
+          const float ratio = fminf(dv, ih.rlimit) / P[1];
+          dg[m] = P[3] / (1.0f - ratio * ratio);
+          sx += xo[m];
+        }
+        sx = quad_sum(sx);
+        const double wd = (double)w;
+#pragma unroll
+        for (int m = 0; m < ROWS; ++m) {
+          const bool row_ok = row_in[m];
+          const double wr = row_ok ? wd : 0.0;
+          const double dd = row_ok ? (double)dg[m] - wd : 0.0;  // exact: A_ii = w + (d_i - w) = d_i
+#pragma unroll
+          for (int j = 0; j < N; ++j)
+            if (j >= kQuad * m || !sym) A[m][j] += wr;  // (sym: the blocks below the diagonal are not kept)
+#pragma unroll
+          for (int c = 0; c < kQuad; ++c)
+            if (kQuad * m + c < N) A[m][kQuad * m + c] += (sd == c) ? dd : 0.0;
+          fv[m] += (double)(row_ok ? fmaf(w, sx, (dg[m] - w) * xo[m]) : 0.f);
+        }
+      }
+    }
+  };
+  // the identity-leaf phase of the fast pass (the careful second pass is cold code: it keeps the general loop)
+  auto identity_phase = [&]() __attribute__((always_inline)) {
+    if constexpr (kLeanId) {
+      // (wave-uniform; marked as the expected side: the builds that carry the loop exist for such fleets, and with the general
+      // loop laid out as the cold side the 128-register build keeps every spill in the careful pass, as before the loop existed)
+      if (__builtin_expect(hdr.id_lean && n_dof == N, 1)) {
+        identity_leaves_lean();
+        return;
+      }
+    }
+    identity_leaves();
+  };
   // Phase order per wave.  The four waves of a SIMD start together and would walk their kinematic trees together -- the
   // one phase that is a dependent chain (latency bound, the SIMD issues next to nothing) -- and then crowd the issue-bound
   // leaf phases together.  The identity-map leaves depend on nothing the walk produces, so the waves in the ODD wave slots
@@ -1751,7 +1895,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   const bool ident_first = kIdentFirst && ((__builtin_amdgcn_s_getreg(0x1804) & 1) != 0);  // HW_ID[3:0] = wave slot in its SIMD
   if (ident_first) {
     zero_system();
-    identity_leaves();
+    identity_phase();
   }
 
   // ---- phase 2: serial tree walk (component layout), ONCE per step ------------------------------
@@ -2393,7 +2537,11 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
     }
     RMP2_STAMP();  // 3: FK leaves done
     // ---- identity-task-map leaves (row layout) -------------------------------------------------
-    if (!(ident_first && pass == 0)) identity_leaves();
+    if (pass == 0) {
+      if (!ident_first) identity_phase();
+    } else {
+      identity_leaves();
+    }
 
     RMP2_STAMP();  // 4: identity leaves done
     // A robot whose state is not finite resolves to NaN (status NONFINITE) whatever its leaves see of it.  The reference gets

@@ -36,6 +36,11 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
   //   4 waves  41.8  47.7  52.5  57.3  88.5  103.4  193.8
   const bool latency = blocks <= h->quad_latency_blocks && h->goal_floats <= 16;
   const bool symk = h->symmetric && N == 9;
+  // does the launched build run the structured identity-leaf loop (rmp2_quad.h kLeanId)?  Named in rmp2_last_kernel.  It is
+  // compiled into the symmetric plain-step and plain-rollout builds (lean_flavor below) and taken by a set whose identity leaves
+  // are all structured, on a robot that uses every dof of the template.
+  h->quad_id_lean = false;
+  auto lean_flavor = [&]() { h->quad_id_lean = N == 9 && !latency && symk && hdr.id_lean && h->n_dof == N; };
   int minw = h->quad_minw;
   if (minw == 0) {
     const int bc = (blocks + h->n_simd - 1) / h->n_simd;  // ceil(b)
@@ -113,6 +118,7 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
   } while (0)
   const bool lean_rollout = !plain && !out.M && !out.f && !o.capsule && o.mode != RMP2_OBS_EXPLICIT_PAIRS && !latency && !with_records;
   if (lean_rollout) {
+    lean_flavor();
     if (minw == 3) minw = 2;  // (the lean rollout exists at two and four waves per SIMD)
     if (minw == 4) {
       if (symk) RMP2_QUAD_ROLL_SYM(4, (N == 9)); else RMP2_QUAD_ROLL_SYM(4, false);
@@ -130,6 +136,7 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
     if (o.link_caps && !h->has_point && !h->likely_singular && h->link_rows_ok && o.mode == RMP2_OBS_SHARED_SPHERES && !latency && ro.n_iters == 1 &&
         ro.substeps == 0 && !ro.q_out && !out.M && !out.f) {
       bytes = lds_bytes + sizeof(float) * kLinkSeg * kRobotsPerWave * h->n_leaf_ops;
+      lean_flavor();
       const int lw = h->quad_minw == 2 ? 2 : 3;
 #define RMP2_QUAD_LINK(MINW, CAP, SYM)                                                                                   \
       do {                                                                                                              \
@@ -169,6 +176,7 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
     for (int l : h->distance_leaves)
       stream = stream && (h->h_pair_begin[l] % 4) == 0 && h->h_pair_begin[l + 1] - h->h_pair_begin[l] == 32;
     if (stream) {
+      lean_flavor();
       if (symk) RMP2_STEP_LAUNCH(h, (rmp2_step_quad_kernel<N, SLOTS, 4, false, false, true, kObsExplicitStream, kPlainStep>), dim3(blocks),
                                  dim3(kWave), lds_bytes, s, h->d_prog, hdr, q, qd, goal, gs, o, out, ro, R);
       else RMP2_STEP_LAUNCH(h, (rmp2_step_quad_kernel<N, SLOTS, 4, false, false, false, kObsExplicitStream, kPlainStep>), dim3(blocks),
@@ -205,6 +213,7 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
 #undef RMP2_QUAD_PT
     return;
   }
+  if (!latency && plain) lean_flavor();
   if (latency) RMP2_QUAD_BY_CAP(1, true);
   else if (plain && minw == 4) RMP2_QUAD_PLAIN(4);
   else if (plain && minw == 3) RMP2_QUAD_PLAIN(3);
@@ -225,6 +234,10 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
 bool RMP2_CAT(launch_quad_n, RMP2_TU_N, _s, RMP2_TU_SLOTS)(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs,
                                                             const ObsArgs& o, const OutArgs& out, const RolloutArgs& ro, int R, hipStream_t s) {
   launch_quad<RMP2_TU_N, RMP2_TU_SLOTS>(h, q, qd, goal, gs, o, out, ro, R, s);
+  if (h->quad_id_lean) {
+    h->last_kernel_text = std::string(h->last_kernel) + " [identity leaves: structured loop, full width]";
+    h->last_kernel = h->last_kernel_text.c_str();
+  }
   return true;
 }
 
