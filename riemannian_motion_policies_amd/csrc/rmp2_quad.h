@@ -147,9 +147,9 @@ __device__ __forceinline__ double rcpd(double x) {
 // (formed in fp64, rounded once): exp(-x/rstd) = exp2(-x * IP[1]) costs one multiply + v_exp_f32 and
 // rounds the argument once, like the reference's own x / rstd.
 __device__ __forceinline__ void obstacle_pair(const float* P, const float* IP, float x, float xd, float& accel,
-                                              float& metric) {
+                                              float& metric, float p10, float p3) {
   x = fmaxf(x - P[0], 0.0f);
-  const float base = P[8] * rcp0(fmaf(x, IP[0], P[10]));
+  const float base = P[8] * rcp0(fmaf(x, IP[0], p10));
   const float gate = fmaf(x * x, IP[4], fmaf(-x, IP[5], 1.0f));
   const float repel = P[5] * __builtin_amdgcn_exp2f(-(x * IP[1]));
   // 1 - sigmoid(z), z = xd / gate_len, as e^-|z| / (1 + e^-|z|) for z > 0 and 1 / (1 + e^-|z|) otherwise: the reference's
@@ -163,9 +163,17 @@ __device__ __forceinline__ void obstacle_pair(const float* P, const float* IP, f
   const float ez = __builtin_amdgcn_exp2f(-fabsf(z2));
   const float rz = rcp0(1.0f + ez);
   const float oms = (z2 > 0.0f ? (z2 > 25.0f ? 0.0f : ez) : 1.0f) * rz;
-  const float damp = -oms * P[1] * xd * rcp0(fmaf(x, IP[2], P[3]));
+  const float damp = -oms * P[1] * xd * rcp0(fmaf(x, IP[2], p3));
   accel = repel + damp;
   metric = (x > P[7]) ? 0.0f : oms * (base * gate);
+}
+
+// (P[10] and P[3] taken from P: what every caller but pair_loop_culled uses.  Each of the two fma above has a second scalar source in
+//  them, which costs a v_mov per trip; pair_loop_culled pins the two in vector registers across its trips (see there); the other
+//  loops were not checked for the room and keep the moves.)
+__device__ __forceinline__ void obstacle_pair(const float* P, const float* IP, float x, float xd, float& accel,
+                                              float& metric) {
+  obstacle_pair(P, IP, x, xd, accel, metric, P[10], P[3]);
 }
 
 // rmp2.py:52-83 with refined hardware reciprocals / exp
@@ -392,6 +400,12 @@ __device__ __forceinline__ void pair_loop_culled(const float* tab, int n_tab, co
   const float vv = dot3(V3, V3);
   const float npp = -dot3(P3, P3);
   constexpr int kTests = 32 / W;
+  // (P[10], P[3] of the distance leaf held in two vector registers across the trips: each is the second scalar source of an fma in
+  //  obstacle_pair and would cost a v_mov per trip.  The pin holds in EVERY instantiation of this template; room for it was checked on
+  //  the compiler's output of the 128-register sphere builds (OBS = 2, 3: 128 registers, no scratch access in the fast pass).  The
+  //  capsule and 16-lane builds were only checked to keep their occupancy -- their register counts move by -2 ... +2 with it.)
+  float p10 = P[10], p3 = P[3];
+  asm volatile("" : "+v"(p10), "+v"(p3));
   for (int base = 0; base < max_count; base += 32) {  // wave-uniform
     // ---- pass 1: in-range mask of this robot's chunk ----
     uint32_t m = 0u;
@@ -463,33 +477,31 @@ __device__ __forceinline__ void pair_loop_culled(const float* tab, int n_tab, co
     };
     // (sphere tables, kTripAhead -- off, measured no gain --: the staged record {-2c, w} and the radius of the NEXT trip are read from
     //  LDS before this trip's chain starts; capsule records, which come from global memory, are always fetched a trip ahead)
-    bool on_n = false;
-    int sidx_n = 0;
-    float4 ca_n = make_float4(0.f, 0.f, 0.f, 0.f), cb_n = ca_n;
+    // The loop is tested at the BOTTOM: the first pair is taken (and the wave asked whether any lane has one) in front of it, the
+    // next trip's (on, index) at the end of a trip.  With the test at the top the sums S, h were live out of the loop from the middle
+    // of its block, and the compiler kept them in two register sets with nine copies per trip between them; tested at the bottom the
+    // nine fused multiply-adds accumulate in place.  Only the two integers travel ahead, not the records (kTripAhead stays off).
+    bool on;
+    int sidx;
+    float4 ca = make_float4(0.f, 0.f, 0.f, 0.f), cb = ca;
+    take(on, sidx);
     if (CAPS) {
-      take(on_n, sidx_n);
-      ca_n = reinterpret_cast<const float4*>(caps)[2 * sidx_n];
-      cb_n = reinterpret_cast<const float4*>(caps)[2 * sidx_n + 1];
+      ca = reinterpret_cast<const float4*>(caps)[2 * sidx];
+      cb = reinterpret_cast<const float4*>(caps)[2 * sidx + 1];
     } else if (kTripAhead) {
-      take(on_n, sidx_n);
-      ca_n = aux[sidx_n];
-      cb_n.x = rad[sidx_n];
+      ca = aux[sidx];
+      cb.x = rad[sidx];
     }
-    while (true) {
-      bool on;
-      int sidx;
-      float4 ca, cb;
-      if (CAPS || kTripAhead) {
-        on = on_n, sidx = sidx_n, ca = ca_n, cb = cb_n;
-      } else {
-        take(on, sidx);
-      }
-      if (!__any(on)) break;
+    if (!__any(on)) continue;  // (wave-uniform) no pair of this chunk is in range of a robot of the wave
+    do {
 #ifdef RMP2_STAMPS
       if (dbg) dbg[0] += 1ull;  // trips of the wave
 #endif
       float diff[3], r;
       float d_cyl = 0.f, n_cyl[3] = {0.f, 0.f, 0.f};
+      bool on_n = false;
+      int sidx_n = 0;
+      float4 ca_n = ca, cb_n = cb;
       if (!CAPS && kTripAhead) {
         take(on_n, sidx_n);
         ca_n = aux[sidx_n];
@@ -507,8 +519,12 @@ __device__ __forceinline__ void pair_loop_culled(const float* tab, int n_tab, co
         // un-culled loop above)
         const float u[3] = {cb.x - ca.x, cb.y - ca.y, cb.z - ca.z};
         const float w[3] = {P3[0] - ca.x, P3[1] - ca.y, P3[2] - ca.z};
-        const float uu = dot3(u, u);
-        float t = uu > 0.f ? dot3(w, u) * rcp1(uu) : 0.f;
+        // (the two dot products in the fused form the compiler gives dot3() everywhere else -- fma(z, z, fma(x, x, y * y)) --, written
+        //  out: left to contraction, this loop shape fused them in another order and moved the capsule results by an ulp.  dot3 itself
+        //  (rmp2_device.h) is a plain sum of products whose fusing is the compiler's choice: "the same arithmetic as the un-culled loop"
+        //  holds bit for bit only while the compiler contracts dot3 there in this order; to rounding the two loops agree in any case)
+        const float uu = fmaf(u[2], u[2], fmaf(u[0], u[0], u[1] * u[1]));
+        float t = uu > 0.f ? fmaf(w[2], u[2], fmaf(w[0], u[0], w[1] * u[1])) * rcp1(uu) : 0.f;
         t = fminf(fmaxf(t, 0.f), 1.f);
         const float ctr[3] = {fmaf(t, u[0], ca.x), fmaf(t, u[1], ca.y), fmaf(t, u[2], ca.z)};
         diff[0] = P3[0] - ctr[0], diff[1] = P3[1] - ctr[1], diff[2] = P3[2] - ctr[2];
@@ -527,7 +543,7 @@ __device__ __forceinline__ void pair_loop_culled(const float* tab, int n_tab, co
       const float xdot = dot3(nh, V3);
       const float cd = fmaf(-xdot, xdot, vv) * rcp0(d) + dot3(nh, A3);  // c2 + J2 c1 (taskmap.py:159)
       float acc, met;
-      obstacle_pair(P, IP, d, xdot, acc, met);
+      obstacle_pair(P, IP, d, xdot, acc, met, p10, p3);
       if (!on) met = 0.f;
       const float wgt = met * (acc - cd);
       const float mn[3] = {met * nh[0], met * nh[1], met * nh[2]};
@@ -540,7 +556,12 @@ __device__ __forceinline__ void pair_loop_culled(const float* tab, int n_tab, co
       h[0] = fmaf(wgt, nh[0], h[0]);
       h[1] = fmaf(wgt, nh[1], h[1]);
       h[2] = fmaf(wgt, nh[2], h[2]);
-    }
+      if (CAPS || kTripAhead) {
+        on = on_n, sidx = sidx_n, ca = ca_n, cb = cb_n;
+      } else {
+        take(on, sidx);
+      }
+    } while (__any(on));
   }
 }
 
@@ -631,29 +652,24 @@ __device__ __forceinline__ void pair_loop_link(const float* tab, int n_tab, int 
       for (int u = 0; u < 4; ++u) rem &= rem - 1u;
       sidx_ = on_ ? base + j : 0;
     };
-    bool on_n = false;
-    int sidx_n = 0;
-    float4 ca_n = make_float4(0.f, 0.f, 0.f, 0.f), cb_n = ca_n;
+    // (tested at the bottom, as pair_loop_culled's loop and for its reason: S and h accumulate in place)
+    bool on;
+    int sidx;
+    float4 ca = make_float4(0.f, 0.f, 0.f, 0.f), cb = ca;
+    take(on, sidx);
     if (CAPS) {
-      take(on_n, sidx_n);
-      ca_n = reinterpret_cast<const float4*>(caps)[2 * sidx_n];
-      cb_n = reinterpret_cast<const float4*>(caps)[2 * sidx_n + 1];
+      ca = reinterpret_cast<const float4*>(caps)[2 * sidx];
+      cb = reinterpret_cast<const float4*>(caps)[2 * sidx + 1];
     } else if (kLinkTripAhead) {  // (sphere tables: the staged record and radius of the next trip, read from LDS a trip ahead)
-      take(on_n, sidx_n);
-      ca_n = aux[sidx_n];
-      cb_n.x = rad[sidx_n];
+      ca = aux[sidx];
+      cb.x = rad[sidx];
     }
-    while (true) {
-      bool on;
-      int sidx;
-      float4 ca, cb;
-      if (CAPS || kLinkTripAhead) {
-        on = on_n, sidx = sidx_n, ca = ca_n, cb = cb_n;
-      } else {
-        take(on, sidx);
-      }
-      if (!__any(on)) break;
+    if (!__any(on)) continue;  // (wave-uniform)
+    do {
       float X[3], Y[3], r;
+      bool on_n = false;
+      int sidx_n = 0;
+      float4 ca_n = ca, cb_n = cb;
       if (!CAPS && kLinkTripAhead) {
         take(on_n, sidx_n);
         ca_n = aux[sidx_n];
@@ -715,7 +731,12 @@ __device__ __forceinline__ void pair_loop_link(const float* tab, int n_tab, int 
       h[0] = fmaf(wgt, nh[0], h[0]);
       h[1] = fmaf(wgt, nh[1], h[1]);
       h[2] = fmaf(wgt, nh[2], h[2]);
-    }
+      if (CAPS || kLinkTripAhead) {
+        on = on_n, sidx = sidx_n, ca = ca_n, cb = cb_n;
+      } else {
+        take(on, sidx);
+      }
+    } while (__any(on));
   }
 }
 
