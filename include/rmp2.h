@@ -579,6 +579,51 @@ int rmp2_set_self_collision_hulls(rmp2_handle *h, int32_t n_pairs, const int32_t
 int rmp2_set_inertials(rmp2_handle *h, int32_t n_frames, const float *inertials, const float *gravity);
 int rmp2_inverse_dynamics(rmp2_handle *h, const float *q, const float *qd, const float *qdd, float *tau, int32_t R, void *stream);
 
+/* ---- forward dynamics: the plant that answers the torques --------------------------------------------------------------------
+ * After the torques the reference calls p.stepSimulation: the robot's own equations of motion answer them.  These three entry
+ * points are that half for a fleet, on the model of rmp2_inverse_dynamics: the rigid bodies of the inertial table, a fixed base,
+ * the gravity of rmp2_set_inertials; no damping, friction, rotor inertia, joint limits or contacts.  With
+ * tau_id(a) = M(q) a + C(q, qd) qd + G(q), one routine serves both drives:
+ *     qdd = qdd_in + M(q)^-1 (tau_applied - tau_id(qdd_in))
+ *   torque drive:        qdd_in = 0, tau_applied = the caller's tau:  qdd = M^-1 (tau - C qd - G);
+ *   acceleration drive:  qdd_in = qdd_des, tau_applied = clamp(tau_id(qdd_des), +-tau_limit) (what simulation.step does).  With
+ *                        no limit, or where no joint of a robot saturates, tau_applied - tau_id is exactly zero, the solve is
+ *                        skipped and the robot's qdd is qdd_des bit for bit.
+ *
+ * rmp2_mass_matrix: q device [R][n_dof]; M device [R][n_dof][n_dof], symmetric, both triangles written from one computed
+ * triangle (the counterpart of p.calculateMassMatrix).  rmp2_forward_dynamics: q, qd, tau device [R][n_dof] -> qdd.
+ * rmp2_dynamics_step: the plant's step, in place:  repeat substeps times:
+ *     qdd = the solve above;  qd += dt * qdd;  q += dt * qd;          (the integrator of rmp2_rollout)
+ *   drive = RMP2_DRIVE_TORQUE: u = tau, held over the substeps, clamped by tau_limit if given;
+ *   drive = RMP2_DRIVE_ACCEL : u = qdd_des, held over the substeps; tau recomputed at every substep's state
+ *                              (simulation.py:369-381).
+ *   tau_limit: device [n_dof], >= 0 (+inf = no limit on that joint), shared by the fleet, or NULL.
+ *   qdd_out / tau_out: device [R][n_dof] or NULL, the last substep's qdd and applied tau.
+ * All three are stream-ordered, without host synchronisation or allocation (they can be captured in a graph); R == 0 is a
+ * no-op.  RMP2_ERR_INVALID_ARGUMENT with a message: a null array, R < 0, substeps < 1, a dt that is not finite or not > 0, an
+ * unknown drive, and a handle without inertials (the message names rmp2_set_inertials).
+ *
+ * Edge behaviour:
+ *   - a dof that no joint of the program owns takes no part in the system: its row of M is e_j and its qdd is 0 (in either
+ *     drive; its entry of u is ignored);
+ *   - a movable joint missing from the joint order is held at 0, as in the FK and the inverse dynamics;
+ *   - M not numerically positive definite -- a Cholesky pivot <= 0 or not finite, e.g. a moving joint whose whole subtree is
+ *     massless: every entry of that robot's qdd is NaN, and in rmp2_dynamics_step so are its q and qd; the other robots are
+ *     unaffected; rmp2_mass_matrix still returns that robot's M.  (An acceleration drive in which nothing saturates never
+ *     factors M and returns qdd_des.)
+ *   - a non-finite value anywhere in a robot's input rows (q, qd, tau / u) makes every output of that robot NaN and leaves the
+ *     others unaffected.
+ * fp32 throughout: one forward walk per robot that sums tau_id and M together, then a Cholesky factorisation and two
+ * triangular solves (csrc/rmp2_forward_dynamics.h).  rmp2_step, rmp2_forward_kinematics, rmp2_rollout and
+ * rmp2_inverse_dynamics are untouched.  Parity with PyBullet's stepSimulation is UNPINNED, as for the inverse dynamics (PyBullet
+ * replaces the file's inertia and adds default link damping); the tests pin these against fp64 restatements. */
+#define RMP2_DRIVE_TORQUE 0
+#define RMP2_DRIVE_ACCEL 1
+int rmp2_mass_matrix(rmp2_handle *h, const float *q, float *M /* [R][n_dof][n_dof], symmetric, both triangles */, int32_t R, void *stream);
+int rmp2_forward_dynamics(rmp2_handle *h, const float *q, const float *qd, const float *tau, float *qdd, int32_t R, void *stream);
+int rmp2_dynamics_step(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
+                       float dt, int32_t substeps, float *qdd_out, float *tau_out, int32_t R, void *stream);
+
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,
  * plain steps on shared or ragged sphere tables, both fleets beyond 8 192 robots -- the two steps are ONE grid (the first

@@ -28,6 +28,7 @@
 #include "rmp2_host.h"
 #include "rmp2_hull.h"
 #include "rmp2_dynamics.h"
+#include "rmp2_forward_dynamics.h"
 
 using namespace rmp2;
 
@@ -2298,6 +2299,77 @@ void launch_inverse_dynamics(const rmp2_handle* h, const float* q, const float* 
 }  // namespace
 
 // =========================================================================================
+// device: the plant (rmp2_mass_matrix / rmp2_forward_dynamics / rmp2_dynamics_step; the routines are rmp2_forward_dynamics.h)
+// =========================================================================================
+namespace {
+
+// As the inverse dynamics: one lane per robot over the unpruned program, ops and inertial records at wave-uniform addresses.
+template <int N, int SLOTS>
+__global__ void __launch_bounds__(kWave)
+rmp2_mass_matrix_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, const float* __restrict__ q,
+                        float* __restrict__ M, int R) {
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  mass_matrix_robot<N, SLOTS>(prog->ops, prog->n_ops, n_dof, inert, q + (size_t)robot * n_dof, M + (size_t)robot * n_dof * n_dof);
+}
+
+// rmp2_forward_dynamics (integrate = 0: one evaluation, q and qd only read) and rmp2_dynamics_step (the substep loop with the
+// state in registers) in one kernel.
+template <int N, int SLOTS>
+__global__ void __launch_bounds__(kWave)
+rmp2_dynamics_step_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay, float az,
+                          float* q, float* qd, const float* __restrict__ u, int accel, const float* __restrict__ lim, float dt,
+                          int substeps, int integrate, float* __restrict__ qdd_out, float* __restrict__ tau_out, int R) {
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const float base_acc[3] = {ax, ay, az};
+  dynamics_step_robot<N, SLOTS>(prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim, dt,
+                                substeps, integrate != 0, qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr);
+}
+
+template <int N>
+void launch_mass_matrix(const rmp2_handle* h, const float* q, float* M, int R, hipStream_t s) {
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  with_slots(h->n_slots_full, [&](auto S) {
+    hipLaunchKernelGGL((rmp2_mass_matrix_kernel<N, S>), grid, block, 0, s, h->d_prog_full, h->d_inert, q, M, R);
+  });
+}
+
+template <int N>
+void launch_dynamics_step(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, float dt,
+                          int substeps, int integrate, float* qdd_out, float* tau_out, int R, hipStream_t s) {
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  with_slots(h->n_slots_full, [&](auto S) {
+    hipLaunchKernelGGL((rmp2_dynamics_step_kernel<N, S>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd, u,
+                       accel, lim, dt, substeps, integrate, qdd_out, tau_out, R);
+  });
+}
+
+int dynamics_step_impl(rmp2_handle* h, const char* what, float* q, float* qd, const float* u, int accel, const float* lim, float dt,
+                       int substeps, int integrate, float* qdd_out, float* tau_out, int R, void* stream) {
+  if (R < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": R < 0");
+  if (h->inert_n == 0)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no inertial table on this handle (call rmp2_set_inertials first)");
+  if (R == 0) return RMP2_OK;
+  if (!q || !qd || !u || (!integrate && !qdd_out)) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": null array");
+  if (int rc = use_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  switch (h->n_template) {
+    case 2: launch_dynamics_step<2>(h, q, qd, u, accel, lim, dt, substeps, integrate, qdd_out, tau_out, R, s); break;
+    case 9: launch_dynamics_step<9>(h, q, qd, u, accel, lim, dt, substeps, integrate, qdd_out, tau_out, R, s); break;
+    default: launch_dynamics_step<16>(h, q, qd, u, accel, lim, dt, substeps, integrate, qdd_out, tau_out, R, s); break;
+  }
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
+}  // namespace
+
+// =========================================================================================
 // C ABI
 // =========================================================================================
 extern "C" {
@@ -3768,6 +3840,42 @@ int rmp2_inverse_dynamics(rmp2_handle* h, const float* q, const float* qd, const
   }
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
+}
+
+int rmp2_mass_matrix(rmp2_handle* h, const float* q, float* M, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (R < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "mass matrix: R < 0");
+  if (h->inert_n == 0)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "mass matrix: no inertial table on this handle (call rmp2_set_inertials first)");
+  if (R == 0) return RMP2_OK;
+  if (!q || !M) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "mass matrix: null array");
+  if (int rc = use_device(h)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  switch (h->n_template) {
+    case 2: launch_mass_matrix<2>(h, q, M, R, s); break;
+    case 9: launch_mass_matrix<9>(h, q, M, R, s); break;
+    default: launch_mass_matrix<16>(h, q, M, R, s); break;
+  }
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
+int rmp2_forward_dynamics(rmp2_handle* h, const float* q, const float* qd, const float* tau, float* qdd, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  // (one evaluation of the step's kernel in the torque drive; q and qd are only read)
+  return dynamics_step_impl(h, "forward dynamics", const_cast<float*>(q), const_cast<float*>(qd), tau, 0, nullptr, 0.f, 1, 0, qdd,
+                            nullptr, R, stream);
+}
+
+int rmp2_dynamics_step(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit, float dt,
+                       int32_t substeps, float* qdd_out, float* tau_out, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (drive != RMP2_DRIVE_TORQUE && drive != RMP2_DRIVE_ACCEL)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "dynamics step: unknown drive " + std::to_string(drive));
+  if (substeps < 1) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "dynamics step: substeps < 1");
+  if (!std::isfinite(dt) || !(dt > 0.f)) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "dynamics step: dt must be finite and > 0");
+  return dynamics_step_impl(h, "dynamics step", q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, dt, substeps, 1, qdd_out, tau_out, R,
+                            stream);
 }
 
 }  // extern "C"

@@ -66,6 +66,7 @@ class Engine:
         self._self_key = None      # the self-pair list and geometry the handle holds (set_self_collision / _hulls), None = off
         self._hulls_key = None     # the link hulls the handle holds (set_link_hulls), None = off
         self._inertials_key = None  # the inertial table and gravity the handle holds (set_inertials), None = off
+        self._tau_limit = None     # (bytes, device tensor) of the last host tau_limit of dynamics_step: uploaded once per value
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -519,6 +520,82 @@ class Engine:
         _native.check(self._lib.rmp2_inverse_dynamics(self._h, q.data_ptr(), qd.data_ptr(), qdd.data_ptr(), out.data_ptr(), R, s),
                       self._h)
         return out
+
+    def _dynamics_rows(self, names: str, *rows):
+        rows = tuple(_f32(x, self.device) for x in rows)
+        q = rows[0]
+        if q.dim() != 2 or q.shape[1] != self.n_dof or any(x.shape != q.shape for x in rows[1:]):
+            raise ValueError(f"{names} must all be [R, {self.n_dof}], got " + ", ".join(str(list(x.shape)) for x in rows))
+        return rows
+
+    def _dynamics_out(self, name: str, out, shape):
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        _require_resident(self.device, **{name: out})
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {list(shape)}")
+        return out
+
+    def mass_matrix(self, q: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Joint-space mass matrix M(q) [R, n, n] (include/rmp2.h rmp2_mass_matrix: symmetric, both triangles) on the current
+        stream; q [R, n] on the engine's device.  Needs set_inertials."""
+        (q,) = self._dynamics_rows("q", q)
+        R = q.shape[0]
+        out = self._dynamics_out("out", out, (R, self.n_dof, self.n_dof))
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        _native.check(self._lib.rmp2_mass_matrix(self._h, q.data_ptr(), out.data_ptr(), R, s), self._h)
+        return out
+
+    def forward_dynamics(self, q: torch.Tensor, qd: torch.Tensor, tau: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Accelerations qdd [R, n] = M(q)^-1 (tau - C(q, qd) qd - G(q)) (include/rmp2.h rmp2_forward_dynamics) on the current
+        stream; q, qd, tau [R, n] on the engine's device.  Needs set_inertials."""
+        q, qd, tau = self._dynamics_rows("q, qd, tau", q, qd, tau)
+        R = q.shape[0]
+        out = self._dynamics_out("out", out, (R, self.n_dof))
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        _native.check(self._lib.rmp2_forward_dynamics(self._h, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), out.data_ptr(), R, s),
+                      self._h)
+        return out
+
+    def _tau_limit_device(self, tau_limit):
+        if tau_limit is None:
+            return None
+        if isinstance(tau_limit, torch.Tensor) and tau_limit.is_cuda:
+            _require_resident(self.device, tau_limit=tau_limit)
+            if tuple(tau_limit.shape) != (self.n_dof,):
+                raise ValueError(f"tau_limit must be [{self.n_dof}], got {list(tau_limit.shape)}")
+            return tau_limit
+        t = np.ascontiguousarray(tau_limit.detach().cpu() if isinstance(tau_limit, torch.Tensor) else tau_limit, dtype=np.float32)
+        if t.shape != (self.n_dof,):
+            raise ValueError(f"tau_limit must be [{self.n_dof}], got {list(t.shape)}")
+        if not (t >= 0).all():   # (false for a NaN as well; +inf = no limit on that joint)
+            raise ValueError("tau_limit must be >= 0 (inf where a joint has no limit)")
+        key = t.tobytes()
+        if self._tau_limit is None or self._tau_limit[0] != key:   # (the same values again upload nothing)
+            self._tau_limit = (key, torch.from_numpy(t).to(self.device))
+        return self._tau_limit[1]
+
+    def dynamics_step(self, q: torch.Tensor, qd: torch.Tensor, u: torch.Tensor, dt: float, substeps: int = 1, drive: str = "accel",
+                      tau_limit=None, qdd_out: Optional[torch.Tensor] = None, tau_out: Optional[torch.Tensor] = None) -> None:
+        """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
+        fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
+        policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
+        drive="torque": u is the torque, held and clamped.  tau_limit: [n] host array (uploaded once per value) or device tensor,
+        or None.  qdd_out / tau_out [R, n]: the last substep's qdd and applied torque.  Needs set_inertials."""
+        _require_resident(self.device, q=q, qd=qd)
+        drives = {"torque": 0, "accel": 1}
+        if drive not in drives:
+            raise ValueError(f"drive must be 'accel' or 'torque', got {drive!r}")
+        q, qd, u = self._dynamics_rows("q, qd, u", q, qd, u)
+        R = q.shape[0]
+        for name, o in (("qdd_out", qdd_out), ("tau_out", tau_out)):
+            if o is not None:
+                self._dynamics_out(name, o, (R, self.n_dof))
+        lim = self._tau_limit_device(tau_limit)
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _native.check(self._lib.rmp2_dynamics_step(self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim),
+                                                   float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), R, s), self._h)
 
     def differentiate(self, q: torch.Tensor, qd: torch.Tensor, frame: int):
         q, qd = _f32(q, self.device), _f32(qd, self.device)

@@ -177,12 +177,9 @@ class UrdfForwardKinematic:
         out = self._fk_engine().differentiate_euler(q2, qd2, self.table.frame_index(_to_str(frame)))
         return tuple(o.cpu().numpy() for o in out) if as_np else out
 
-    def inverse_dynamics(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), inertials=None):
-        """Joint torques tau = M(q) qdd + C(q, qd) qd + G(q) of the robot for the accelerations qdd (what the reference's
-        simulation.step asks p.calculateInverseDynamics for, simulation.py:369-386), on the GPU (rmp2_inverse_dynamics).
-        q, qd, qdd [n] or [R, n]; host inputs give host outputs, CUDA tensors give a CUDA tensor.  `inertials`: a dict as
-        urdf.read_inertials returns it, or an [n_frames, 10] table (urdf.inertial_table); by default the <inertial> elements of
-        this object's URDF (an error when it has none).  `gravity` in the base frame."""
+    def _dynamics_engine(self, gravity, inertials):
+        """The FK engine with the inertial table set: `inertials` a dict as urdf.read_inertials returns it, an [n_frames, 10] table
+        (urdf.inertial_table), or None for the <inertial> elements of this object's URDF (an error when it has none)."""
         if inertials is None:
             if self._inertials is None:
                 self._inertials = read_inertials(self.filepath)
@@ -193,13 +190,48 @@ class UrdfForwardKinematic:
         table = inertial_table(self.table, inertials) if isinstance(inertials, dict) else inertials
         eng = self._fk_engine()
         eng.set_inertials(table, gravity)
-        as_np = not isinstance(q, torch.Tensor)
-        one = (np.ndim(q) if as_np else q.dim()) == 1
+        return eng
+
+    @staticmethod
+    def _rows(*xs):
+        """(as_np, one, rows): host inputs give host outputs, [n] inputs give [n] outputs."""
+        as_np = not isinstance(xs[0], torch.Tensor)
+        one = (np.ndim(xs[0]) if as_np else xs[0].dim()) == 1
         if as_np:
-            q2, qd2, qdd2 = (np.atleast_2d(np.asarray(x, dtype=np.float32)) for x in (q, qd, qdd))
+            rows = tuple(np.atleast_2d(np.asarray(x, dtype=np.float32)) for x in xs)
         else:
-            q2, qd2, qdd2 = (x.reshape(1, -1) if one else x for x in (q, qd, qdd))
+            rows = tuple(x.reshape(1, -1) if one else x for x in xs)
+        return as_np, one, rows
+
+    def inverse_dynamics(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), inertials=None):
+        """Joint torques tau = M(q) qdd + C(q, qd) qd + G(q) of the robot for the accelerations qdd (what the reference's
+        simulation.step asks p.calculateInverseDynamics for, simulation.py:369-386), on the GPU (rmp2_inverse_dynamics).
+        q, qd, qdd [n] or [R, n]; host inputs give host outputs, CUDA tensors give a CUDA tensor.  `inertials`: a dict as
+        urdf.read_inertials returns it, or an [n_frames, 10] table (urdf.inertial_table); by default the <inertial> elements of
+        this object's URDF (an error when it has none).  `gravity` in the base frame."""
+        eng = self._dynamics_engine(gravity, inertials)
+        as_np, one, (q2, qd2, qdd2) = self._rows(q, qd, qdd)
         tau = eng.inverse_dynamics(q2, qd2, qdd2)
         if one:
             tau = tau[0]
         return tau.cpu().numpy() if as_np else tau
+
+    def forward_dynamics(self, q, qd, tau, gravity=(0.0, 0.0, -9.81), inertials=None):
+        """Accelerations qdd = M(q)^-1 (tau - C(q, qd) qd - G(q)) of the robot under the joint torques tau (the plant that
+        p.stepSimulation integrates), on the GPU (rmp2_forward_dynamics).  Arguments and conventions as inverse_dynamics."""
+        eng = self._dynamics_engine(gravity, inertials)
+        as_np, one, (q2, qd2, tau2) = self._rows(q, qd, tau)
+        qdd = eng.forward_dynamics(q2, qd2, tau2)
+        if one:
+            qdd = qdd[0]
+        return qdd.cpu().numpy() if as_np else qdd
+
+    def mass_matrix(self, q, inertials=None):
+        """Joint-space mass matrix M(q) [n, n] or [R, n, n] (p.calculateMassMatrix's counterpart), on the GPU (rmp2_mass_matrix).
+        q [n] or [R, n]; conventions as inverse_dynamics."""
+        eng = self._dynamics_engine((0.0, 0.0, -9.81), inertials)
+        as_np, one, (q2,) = self._rows(q)
+        M = eng.mass_matrix(q2)
+        if one:
+            M = M[0]
+        return M.cpu().numpy() if as_np else M

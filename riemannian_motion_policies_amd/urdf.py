@@ -585,6 +585,21 @@ def read_inertials(urdf_filepath: str) -> dict:
     return out
 
 
+def read_effort_limits(urdf_filepath: str, order: Sequence[str]) -> np.ndarray:
+    """float32 [n]: the <limit effort=> of the joints in `order` (N m, or N for a prismatic joint), inf where the joint has no
+    <limit> or the attribute is absent: the tau_limit of Engine.dynamics_step."""
+    root = ElementTree.parse(urdf_filepath).getroot()
+    joints = {j.attrib["name"]: j for j in root.findall("joint")}
+    out = np.full(len(order), np.inf, dtype=np.float32)
+    for i, name in enumerate(order):
+        if name not in joints:
+            raise ValueError(f"{urdf_filepath}: no joint named {name!r}")
+        lim = joints[name].find("limit")
+        if lim is not None and "effort" in lim.attrib:
+            out[i] = float(lim.attrib["effort"])
+    return out
+
+
 def inertial_table(table: KinematicTable, inertials: dict) -> np.ndarray:
     """float32 [n_frames, 10] for rmp2_set_inertials: frame f's record describes its child link (table.link_names[f]) in FRAME
     coordinates, (m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz) -- c the centre of mass, the tensor about c in frame axes.
