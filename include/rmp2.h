@@ -195,6 +195,9 @@ typedef struct rmp2_obstacles {
                                               the nearest point of the LINK's capsule to the obstacle -- the values of
                                               rmp2_closest_points_links + EXPLICIT_PAIRS (d = |p_link - p_obs| and unit normal; as
                                               there, the derivative moves the point with the frame origin, taskmap.py:124-129).
+                                              Where the two axes INTERSECT (a sphere centred on the link's axis, crossing segments)
+                                              there is no common normal: every route takes the fixed direction +z, so the shapes
+                                              overlap by the sum of their radii along it and the pair's normal is -z.
                                               FUSED into the step for tables of at most 256 spheres / capsules, robots with at
                                               most 9 dofs and an inertia leaf, solve = AUTO or a certifying PINV, and 2-dof robots
                                               with either resolve (their closed-form 2 x 2 resolve is the pseudo-inverse) -- shared

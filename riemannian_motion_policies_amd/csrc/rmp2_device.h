@@ -245,7 +245,7 @@ __device__ __forceinline__ void capsule_centre(const float4 ra, const float4 rb,
 // points c1 = p1 + s (q1 - p1), c2 = p2 + t (q2 - p2).  The standard clamped solution of the 2 x 2 normal equations
 // (degenerate segments -- points -- included); the link-capsule case of the reference's closest-point stage, which
 // PyBullet answers for the link's collision shape (simulation.py:462-484).
-__device__ __forceinline__ void segment_segment(const float p1[3], const float q1[3], const float p2[3], const float q2[3],
+__host__ __device__ __forceinline__ void segment_segment(const float p1[3], const float q1[3], const float p2[3], const float q2[3],
                                                 float& s, float& t) {
   const float d1[3] = {q1[0] - p1[0], q1[1] - p1[1], q1[2] - p1[2]};
   const float d2[3] = {q2[0] - p2[0], q2[1] - p2[1], q2[2] - p2[2]};
@@ -311,7 +311,7 @@ __device__ __forceinline__ void cross3(const float a[3], const float b[3], float
   o[1] = a[2] * b[0] - a[0] * b[2];
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
-__device__ __forceinline__ float dot3(const float a[3], const float b[3]) {
+__host__ __device__ __forceinline__ float dot3(const float a[3], const float b[3]) {
   return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
 }
 
@@ -536,6 +536,18 @@ __device__ __forceinline__ void leaf_collision_avoidance(const float* P, float d
   wgt = d > r ? 0.f : spline;
 }
 
+// The length to normalise n = X - Y by, X and Y the nearest points of a link's axis and a primitive's axis: |n|.  Where the axes
+// INTERSECT (|n| == 0) there is no common normal: n becomes the fixed direction +z and the length 1, link_pair_fields' convention
+// below (and configs.pairs_from_link_capsules'), so that the surface points X - r_link n / len and Y + r_obs n / len stay finite:
+// they lie r_link + r_obs apart along -z, an overlap like any other.  A NaN length is not this case and propagates.  The closest-point
+// stage kernels of rmp2_hip.hip normalise by it; tests/test_link_pairs_host.py runs it on the CPU.
+__host__ __device__ __forceinline__ float link_normal_length(float n[3]) {
+  const float dn = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  const bool crossing = dn == 0.f;
+  n[2] = crossing ? 1.f : n[2];
+  return crossing ? 1.f : dn;
+}
+
 // Datamanager fields of ONE (link capsule, primitive) pair for the attached-point leaves, formed on the device (the reference
 // takes them from PyBullet's closest points every control step, simulation.py:462-484 / data_management.py:22-53): world link
 // axis LA + s LD (laa = |LD|^2, inv_laa its reciprocal or 0, radius lrad), primitive record ca (a.xyz, radius) and cb (b.xyz;
@@ -543,7 +555,7 @@ __device__ __forceinline__ void leaf_collision_avoidance(const float* P, float d
 // branch-free); p_link = X - lrad n, p_obs = Y + r n with n = (X - Y) / |X - Y|; out:
 //   dd = |p_link - p_obs|, nv = (p_link - p_obs) / dd, r = p_link - P3 (= R relative_position, the attached point's lever arm).
 // Overlapping shapes: the points have crossed, the distance reads positive and the normal flips (as the explicit arrays would).
-__device__ __forceinline__ void link_pair_fields(const float LA[3], const float LD[3], float laa, float inv_laa, float lrad,
+__host__ __device__ __forceinline__ void link_pair_fields(const float LA[3], const float LD[3], float laa, float inv_laa, float lrad,
                                                  const float4 ca, const float4 cb, const float P3[3], float r[3], float nv[3],
                                                  float& dd) {
   const float d2v[3] = {cb.x - ca.x, cb.y - ca.y, cb.z - ca.z};

@@ -743,7 +743,7 @@ rmp2_closest_kernel(const DevProgram* __restrict__ prog, const float* __restrict
             Y[c] = C[c] + to * (D[c] - C[c]);
             n[c] = X[c] - Y[c];
           }
-          const float dn = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+          const float dn = link_normal_length(n);  // (intersecting axes: n = +z, dn = 1)
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
             const float u = n[c] / dn;
@@ -902,8 +902,9 @@ rmp2_closest_wave_kernel(const DevProgram* __restrict__ prog, const float* __res
       } else if (CAPS) {
         capsule_centre(ca, cb, X, Y);
       }
-      const float n[3] = {X[0] - Y[0], X[1] - Y[1], X[2] - Y[2]};
-      const float inv = 1.0f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+      float n[3] = {X[0] - Y[0], X[1] - Y[1], X[2] - Y[2]};
+      // (link geometry: intersecting axes take the fixed normal +z; a frame origin ON a centre is the reference's own 0 / 0)
+      const float inv = 1.0f / (LINK ? link_normal_length(n) : sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]));
       if (ok) {
         const float wl = LINK ? sa.w * inv : 0.f, wo = r_obs * inv;
         __builtin_nontemporal_store(f32x3{X[0] - wl * n[0], X[1] - wl * n[1], X[2] - wl * n[2]}, reinterpret_cast<f32x3*>(p_link + off));
@@ -1104,8 +1105,9 @@ rmp2_self_stage_kernel(const DevProgram* __restrict__ prog, const DevProgram* __
         } else if (CAPS) {
           capsule_centre(ca, cb, X, Y);
         }
-        const float n[3] = {X[0] - Y[0], X[1] - Y[1], X[2] - Y[2]};
-        const float inv = 1.0f / sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        float n[3] = {X[0] - Y[0], X[1] - Y[1], X[2] - Y[2]};
+        // (link geometry: intersecting axes take the fixed normal +z; a frame origin ON a centre is the reference's own 0 / 0)
+        const float inv = 1.0f / (LINK ? link_normal_length(n) : sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]));
         if (ok) {
           const float wl = LINK ? sa.w * inv : 0.f, wo = r_obs * inv;
           __builtin_nontemporal_store(f32x3{X[0] - wl * n[0], X[1] - wl * n[1], X[2] - wl * n[2]}, reinterpret_cast<f32x3*>(p_link + off));
@@ -2199,7 +2201,9 @@ int dispatch_solve(const rmp2_handle* h, const float* q, const float* qd, const 
   const int hex_max = h->has_point ? 0 : 8192;
   // the fused rollout of a solve = PINV handle (the reference's only resolve, rmp.py:153-154, inside the closed loop): the hex
   // mapping carries the strict pseudo-inverse through its careful path at any fleet size
-  const bool strict_rollout = h->strict && rollout && !quad_certifies;
+  // (2-dof robots with link geometry on their distance leaves, which the hex mapping does not carry: the quad mapping, whose
+  //  closed-form 2 x 2 resolve IS the pseudo-inverse for every robot, inside the rollout as in the plain step)
+  const bool strict_rollout = h->strict && rollout && !quad_certifies && !(N == 2 && !hex_ok);
   // (the hex mapping certifies too since round 4 -- its Gauss-Jordan keeps the pivot rows --: strict small fleets take it like AUTO ones)
   // (2-dof robots under solve = PINV without a certificate -- sets without an inertia leaf, e.g. the TwoJoint half of config 5: the hex
   //  mapping resolves every robot through its careful path, the quad mapping by its closed-form 2 x 2 pseudo-inverse -- measured 14.3 us

@@ -704,10 +704,17 @@ __device__ __forceinline__ void pair_loop_link(const float* tab, int n_tab, int 
 #pragma unroll
         for (int c = 0; c < 3; ++c) X[c] = fmaf(sl, d1[c], LA[c]);
       }
-      const float diff[3] = {X[0] - Y[0], X[1] - Y[1], X[2] - Y[2]};
+      float diff[3] = {X[0] - Y[0], X[1] - Y[1], X[2] - Y[2]};
       const float d2 = diff[0] * diff[0] + diff[1] * diff[1] + diff[2] * diff[2];
       float dn, inv0;
       norm_and_inverse(d2, dn, inv0);
+      // intersecting axes (a sphere centred on the link's axis, two crossing segments): no common normal, and norm_and_inverse
+      // answers inf and NaN.  link_pair_fields' convention (rmp2_device.h), by selects: direction +z, reciprocal 1, norm 0 -- the
+      // gap reads -(r + lr) and the normal flips to -z as for any overlap.  A NaN d2 is not this case and propagates.
+      const bool crossing = d2 == 0.f;
+      diff[2] = crossing ? 1.f : diff[2];
+      inv0 = crossing ? 1.f : inv0;
+      dn = crossing ? 0.f : dn;
       // surface to surface along the axes' common normal.  The explicit form sees the two surface points only:
       // x = |p_link - p_obs| and n = (p_link - p_obs) / x -- for overlapping capsules the points have crossed, the distance
       // reads positive and the normal points the other way (taskmap.py:126-129 on PyBullet's points); same here.
