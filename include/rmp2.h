@@ -496,7 +496,10 @@ int rmp2_self_pairs(rmp2_handle *h, const float *q, float *p_link, float *p_obs,
  *   axis meets the hull (the centre inside, the segment piercing it, or within 1e-7 m of its surface): the separating face of
  *     least translation over the hull's planes, t_f = d_f - min over the segment's endpoints of n_f . x, f* = argmin t_f, x* the
  *     endpoint attaining that min; p_link = x* + t_f* n_f*, p_obs = x* - r n_f*.  Conservative against PyBullet's EPA, which
- *     also weighs edge-edge directions.
+ *     also weighs edge-edge directions.  The gap therefore JUMPS where a capsule's axis grazes an edge: on the unit cube [0, 1]^3
+ *     the axis (0.5, 0.5, 1.5)-(1.5, 0.5, 0.5) touches the edge x = z = 1 at (1, 0.5, 1) and no face separates it from the cube
+ *     by less than 0.5 (the faces +x and +z tie), so g = -(0.5 + r); the same axis 2e-7 m further out is apart, g = 2e-7 - r.  A
+ *     step of half the hull's width across the 1e-7 m touch threshold, by the rule; the distance itself is continuous there.
  *   FK_DISTANCE leaf: p_link, p_obs in the base frame (explicit-pair semantics: d = |p_link - p_obs|, the derivative follows
  *     the frame origin, quirk Q5).
  *   FK_POINT leaf: the fields rmp2_device.h link_pair_fields forms from the same two points: p_link = relative_position (the
@@ -505,6 +508,11 @@ int rmp2_self_pairs(rmp2_handle *h, const float *q, float *p_link, float *p_obs,
  *     the axis meets the hull).
  * p_link, p_obs device [R][L*K][3]; dist device [R][L*K] (|g| for every pair; required when the set has attached-point leaves,
  * else it may be NULL).  The device iteration is bounded: at most 32 GJK steps per pair (fp64), one pass over the planes.
+ * Non-finite inputs: a NaN or an infinity ANYWHERE in an obstacle record (centre or endpoints, radius, a capsule record's unused
+ * float) makes p_link, p_obs and dist of that record's pairs NaN for every robot and every leaf, and leaves every other pair's
+ * bits alone; a NaN or an infinity in a robot's q makes every pair output of that robot NaN, the leaves upstream of the joint
+ * included, and leaves the other robots' bits alone.  Never a finite distance, never +-inf beside finite points.  The step that
+ * follows turns such a pair into NaN on every joint of the robots that hold it, with RMP2_STATUS_NONFINITE.
  *
  * rmp2_step on a handle with hulls and a SHARED_SPHERES sphere / capsule table: this stage into a buffer of the handle, then the
  * explicit-pair step (two launches; the same numbers as calling the two).  Memory: the handle's stage buffer (rmp2_set_self_collision),
@@ -542,6 +550,9 @@ int rmp2_closest_points_hulls(rmp2_handle *h, const float *q, const rmp2_obstacl
  *   Either way p_link - p_obs = g u.  FK_DISTANCE leaves: both points in the base frame.  FK_POINT leaves: p_link =
  *   relative_position (h_A in the joint frame), p_obs = normal_vec = sign(g) u (base frame), dist = |g|.
  *   Bounded: at most 64 GJK steps per pair (fp64; the best simplex is kept), one pass over each hull's planes for the face rule.
+ *   Non-finite inputs: a NaN or an infinity in a robot's q makes p_link, p_obs and dist of EVERY self pair (and every obstacle
+ *   pair: rmp2_closest_points_hulls' contract) of that robot NaN, whichever frames the pair names, and leaves the other robots'
+ *   bits alone.  Never a finite distance, never +-inf beside finite points.
  * rmp2_self_pairs on such a handle gives the hull pairs (layout of rmp2_set_self_collision).  rmp2_step with obstacle input NONE
  * or a SHARED_SPHERES sphere / capsule table: each pair leaf's range is [K obstacle pairs | S_l self pairs], the obstacle pairs
  * formed on the same leaf hulls, bit-identical to rmp2_closest_points_hulls on a handle whose link hulls are those hulls; then

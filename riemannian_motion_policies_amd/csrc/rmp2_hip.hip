@@ -1180,6 +1180,12 @@ rmp2_hull_stage_kernel(const DevProgram* __restrict__ prog, const HullProg* __re
   const int robot = r0 + lane;
   if (lane < kHullRobots && robot < R) {
     const float* my_q = q + (size_t)robot * prog->n_dof;
+    // a non-finite q poisons EVERY pair leaf's frame of this robot, those upstream of the joint too (rmp2.h: every pair output
+    // of the robot is NaN): a NaN frame makes the axis NaN in phase 2 and hull_closest selects NaN into each field
+    float qz = 0.f;
+    for (int j = 0; j < prog->n_dof; ++j) qz += 0.f * my_q[j];
+    const bool qbad = !(qz == 0.f);
+    const float qn = __builtin_nanf("");
     FrameState cur;
     FrameState slot[SLOTS > 0 ? SLOTS : 1];
     for (int k = 0; k < prog->n_ops; ++k) {
@@ -1202,7 +1208,8 @@ rmp2_hull_stage_kernel(const DevProgram* __restrict__ prog, const HullProg* __re
         if (o < 0) continue;
         float4* rec = frm + ((size_t)lane * L + o) * 3;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) rec[i] = make_float4(cur.R[3 * i], cur.R[3 * i + 1], cur.R[3 * i + 2], cur.p[i]);
+        for (int i = 0; i < 3; ++i)
+          rec[i] = make_float4(qbad ? qn : cur.R[3 * i], qbad ? qn : cur.R[3 * i + 1], qbad ? qn : cur.R[3 * i + 2], qbad ? qn : cur.p[i]);
       }
     }
   }
@@ -1229,7 +1236,8 @@ rmp2_hull_stage_kernel(const DevProgram* __restrict__ prog, const HullProg* __re
         a[i] = Rm[i] * A[0] + Rm[3 + i] * A[1] + Rm[6 + i] * A[2];
         b[i] = Rm[i] * B[0] + Rm[3 + i] * B[1] + Rm[6 + i] * B[2];
       }
-      const double rad = ca.w;
+      // (a capsule record's unused 8th float counts too: non-finite ANYWHERE in a record makes its pairs NaN)
+      const double rad = CAPS && !(0.f * cb.w == 0.f) ? (double)__builtin_nanf("") : (double)ca.w;
       const HullHit hh = hull_closest(hverts + v0, nv, hplanes + f0, nf, a, b, rad);
       const size_t pair = (size_t)(r0 + r) * P + (size_t)obegin + k;
       if (point) {   // relative_position (frame), normal_vec = sign(g) u (base), distance |g|  (link_pair_fields' conventions)
@@ -1337,8 +1345,12 @@ rmp2_self_hull_stage_kernel(const DevProgram* __restrict__ prog_full, const Self
   const int lane = threadIdx.x;
   const int robot = blockIdx.x * nr + lane;
   if (lane >= nr || robot >= R) return;   // (no barrier below: a lane reads only what it wrote)
+  bool qbad;   // a non-finite q: every pair of this robot is NaN, whichever frames it names (rmp2.h)
   {
     const float* my_q = q + (size_t)robot * prog_full->n_dof;
+    float qz = 0.f;
+    for (int j = 0; j < prog_full->n_dof; ++j) qz += 0.f * my_q[j];
+    qbad = !(qz == 0.f);
     float cur[12];   // R row-major, then p  (visit_frame's positions; no velocities)
     float saved[SLOTS > 0 ? SLOTS : 1][12];
 #pragma unroll
@@ -1390,7 +1402,8 @@ rmp2_self_hull_stage_kernel(const DevProgram* __restrict__ prog_full, const Self
 #pragma unroll
       for (int c = 0; c < 3; ++c)
         Rm[3 * i + c] = (double)A[i] * (double)B[c] + (double)A[4 + i] * (double)B[4 + c] + (double)A[8 + i] * (double)B[8 + c];
-      t[i] = (double)A[i] * dp[0] + (double)A[4 + i] * dp[1] + (double)A[8 + i] * dp[2];
+      const double ti = (double)A[i] * dp[0] + (double)A[4 + i] * dp[1] + (double)A[8 + i] * dp[2];
+      t[i] = qbad ? (double)__builtin_nanf("") : ti;   // hull_pair_closest selects NaN into every field
     }
     const PairHit hh = hull_pair_closest(hverts + sp->hv0[ea], sp->hnv[ea], hplanes + sp->hf0[ea], sp->hnf[ea], hverts + sp->hv0[eb],
                                          sp->hnv[eb], hplanes + sp->hf0[eb], sp->hnf[eb], Rm, t);

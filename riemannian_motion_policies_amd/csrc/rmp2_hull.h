@@ -28,6 +28,12 @@ struct HullHit {
 
 __host__ __device__ inline double hdot(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+// The non-finite contract (include/rmp2.h): 0 * x is 0 for every finite x and NaN for NaN and +-inf, so a sum of such products is
+// NaN exactly when one input is not finite.  The routines below run on whatever they are given (every loop is bounded and every
+// index stays in range with NaN comparisons false) and select NaN into each output field at the end: finite results keep their bits.
+__host__ __device__ inline bool hull_poisoned(double zero_sum) { return !(zero_sum == 0.0); }
+__host__ __device__ inline double hull_nan() { return __builtin_nan(""); }
+
 // Closest point of conv(W[0..n)) to the origin, GJK's distance subalgorithm: lam = barycentric weights; the simplex is reduced
 // in place to the smallest feature that holds the point.  Returns false when a full tetrahedron contains the origin.
 struct HullSimplex {
@@ -183,8 +189,8 @@ __host__ __device__ inline bool hs_solve(HullSimplex& s) {
 
 // The nearest points of the convex hull (V: nv vertices as float4 .xyz; Pl: nf planes (n, d), n . x <= d inside) and the
 // segment a-b (a == b: a point) of radius r, all in the hull's coordinates.
-__host__ __device__ inline HullHit hull_closest(const float4* __restrict__ V, int nv, const float4* __restrict__ Pl, int nf,
-                                                const double a[3], const double b[3], double r) {
+__host__ __device__ inline HullHit hull_closest_finite(const float4* __restrict__ V, int nv, const float4* __restrict__ Pl, int nf,
+                                                       const double a[3], const double b[3], double r) {
   HullHit out;
   HullSimplex s;
   const bool seg = a[0] != b[0] || a[1] != b[1] || a[2] != b[2];
@@ -273,6 +279,19 @@ __host__ __device__ inline HullHit hull_closest(const float4* __restrict__ V, in
   const double* x = at_b ? b : a;
   for (int c = 0; c < 3; ++c) out.xp[c] = x[c], out.hp[c] = x[c] + tb * n[c], out.u[c] = -n[c];
   out.gap = -(tb + r);
+  return out;
+}
+
+// A non-finite a, b or r: every field NaN (hull_poisoned).  Without it a NaN in b alone is never picked by the support test
+// and the capsule is answered as the sphere at a, and a NaN in a falls through to the face rule's initial 1e300.
+__host__ __device__ inline HullHit hull_closest(const float4* __restrict__ V, int nv, const float4* __restrict__ Pl, int nf,
+                                                const double a[3], const double b[3], double r) {
+  HullHit out = hull_closest_finite(V, nv, Pl, nf, a, b, r);
+  const bool bad = hull_poisoned(0.0 * a[0] + 0.0 * a[1] + 0.0 * a[2] + 0.0 * b[0] + 0.0 * b[1] + 0.0 * b[2] + 0.0 * r);
+  const double qn = hull_nan();
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out.hp[c] = bad ? qn : out.hp[c], out.xp[c] = bad ? qn : out.xp[c], out.u[c] = bad ? qn : out.u[c];
+  out.gap = bad ? qn : out.gap;
   return out;
 }
 
@@ -409,9 +428,9 @@ __host__ __device__ inline bool pg_solve(const double W[4][3], int n, int& k, in
   return any;
 }
 
-__host__ __device__ inline PairHit hull_pair_closest(const float4* __restrict__ VA, int na, const float4* __restrict__ PA, int fa,
-                                                     const float4* __restrict__ VB, int nb, const float4* __restrict__ PB, int fb,
-                                                     const double Rm[9], const double t[3]) {
+__host__ __device__ inline PairHit hull_pair_closest_finite(const float4* __restrict__ VA, int na, const float4* __restrict__ PA, int fa,
+                                                            const float4* __restrict__ VB, int nb, const float4* __restrict__ PB, int fb,
+                                                            const double Rm[9], const double t[3]) {
   PairHit out;
   int ia[4] = {0, 0, 0, 0}, ib[4] = {0, 0, 0, 0};
   double lam[4] = {1.0, 0.0, 0.0, 0.0};
@@ -558,6 +577,22 @@ __host__ __device__ inline PairHit hull_pair_closest(const float4* __restrict__ 
   for (int c = 0; c < 3; ++c) out.pb[c] = y[c], out.pa[c] = y[c] - best * ns[c], out.u[c] = -ns[c];
   out.gap = best;
   out.face = 1;
+  return out;
+}
+
+// A non-finite entry of Rm or t: every real field NaN (hull_poisoned; iters and face are diagnostics and stay).
+__host__ __device__ inline PairHit hull_pair_closest(const float4* __restrict__ VA, int na, const float4* __restrict__ PA, int fa,
+                                                     const float4* __restrict__ VB, int nb, const float4* __restrict__ PB, int fb,
+                                                     const double Rm[9], const double t[3]) {
+  PairHit out = hull_pair_closest_finite(VA, na, PA, fa, VB, nb, PB, fb, Rm, t);
+  double z = 0.0 * t[0] + 0.0 * t[1] + 0.0 * t[2];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) z += 0.0 * Rm[i];
+  const bool bad = hull_poisoned(z);
+  const double qn = hull_nan();
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out.pa[c] = bad ? qn : out.pa[c], out.pb[c] = bad ? qn : out.pb[c], out.u[c] = bad ? qn : out.u[c];
+  out.gap = bad ? qn : out.gap;
   return out;
 }
 
