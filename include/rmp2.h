@@ -596,7 +596,8 @@ int rmp2_inverse_dynamics(rmp2_handle *h, const float *q, const float *qd, const
 /* ---- forward dynamics: the plant that answers the torques --------------------------------------------------------------------
  * After the torques the reference calls p.stepSimulation: the robot's own equations of motion answer them.  These three entry
  * points are that half for a fleet, on the model of rmp2_inverse_dynamics: the rigid bodies of the inertial table, a fixed base,
- * the gravity of rmp2_set_inertials; no damping, friction, rotor inertia, joint limits or contacts.  With
+ * the gravity of rmp2_set_inertials; no damping, friction, rotor inertia, joint limits or contacts (joint-limit stops: the block
+ * after this one, rmp2_dynamics_step_stops).  With
  * tau_id(a) = M(q) a + C(q, qd) qd + G(q), one routine serves both drives:
  *     qdd = qdd_in + M(q)^-1 (tau_applied - tau_id(qdd_in))
  *   torque drive:        qdd_in = 0, tau_applied = the caller's tau:  qdd = M^-1 (tau - C qd - G);
@@ -637,6 +638,38 @@ int rmp2_mass_matrix(rmp2_handle *h, const float *q, float *M /* [R][n_dof][n_do
 int rmp2_forward_dynamics(rmp2_handle *h, const float *q, const float *qd, const float *tau, float *qdd, int32_t R, void *stream);
 int rmp2_dynamics_step(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
                        float dt, int32_t substeps, float *qdd_out, float *tau_out, int32_t R, void *stream);
+
+/* ---- joint-limit stops: the plant's step inside [q_lower, q_upper] -----------------------------------------------------------
+ * rmp2_dynamics_step_stops is rmp2_dynamics_step with inelastic stops at the joint limits, acting at velocity level.  At a
+ * substep's state (q, qd), with a the acceleration of the block above (either drive, tau_limit as there) and v* = qd + dt a,
+ * every dof j that a joint owns has the velocity box
+ *     l_j = min((lo_j - q_j) / dt, 0),   h_j = max((hi_j - q_j) / dt, 0)
+ * (-inf / +inf limits: no bound; an unowned dof: no bound; a joint already outside its limits is not pushed back, it only cannot
+ * move further out; lo_j == hi_j locks the joint once it is there).  The step's velocity is the box-constrained minimiser in
+ * the kinetic-energy metric (Gauss' principle; the inelastic limit of what a constraint-impulse solver converges to):
+ *     v = argmin 1/2 (v - v*)^T M(q) (v - v*)   subject to   l <= v <= h,
+ * whose unique solution satisfies, with lambda = M (v - v*): lambda_j >= 0 where v_j = l_j, lambda_j <= 0 where v_j = h_j,
+ * lambda_j = 0 on free dofs, any sign where l_j = h_j.  Then qd <- v, q <- q + dt v; in a substep that ran the solver a dof whose
+ * bound came from its limit lands on the limit exactly and no rounding takes a joint that was inside its limits outside (a
+ * substep on the fast path below integrates as rmp2_dynamics_step does, to one fp32 rounding).  Outputs of the last substep:
+ *     qdd_out = a + (v - v*) / dt,   tau_out = the applied motor torque as above,   stop_out = lambda / dt (the stops' torque).
+ *   q_lower / q_upper: device [n_dof], shared by the fleet, both required (lower <= upper; +-inf where there is no limit).
+ *   stop_out: device [R][n_dof] or NULL.  status_out: device [R] or NULL: RMP2_STOP_* flags over the substeps, and in bits 8..
+ *   the largest number of solver iterations a substep of that robot took.
+ * Solver: the primal active-set method, one bound at a time, from v = clip(v*, l, h); every iterate is feasible and the
+ * objective never increases, so the iteration cap leaves a valid in-limits velocity and is reported (RMP2_STOP_CAPPED).
+ * A robot whose v* already lies in the box runs none of it: its q, qd, qdd_out and tau_out are those of rmp2_dynamics_step bit
+ * for bit, its stop_out is exactly 0 and its status 0.
+ * Stream-ordered, no allocation, capturable; refusals as for rmp2_dynamics_step, and null limit arrays ("null array").  The edge behaviour of
+ * the block above holds unchanged (unowned dofs, missing joints, M not positive definite -> the robot's rows NaN, non-finite
+ * input rows -> that robot NaN and the others untouched).  One lane per robot, M kept in LDS across the iterations
+ * (csrc/rmp2_joint_stops.h); every other entry point is untouched.  Parity with PyBullet's constraint solver is UNPINNED, as
+ * for the rest of the plant; the tests pin this against an fp64 restatement and against brute-force enumeration. */
+#define RMP2_STOP_ACTIVE 1u   /* some stop was active in some substep */
+#define RMP2_STOP_CAPPED 2u   /* the iteration cap was reached in some substep */
+int rmp2_dynamics_step_stops(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive,
+                             const float *tau_limit, const float *q_lower, const float *q_upper, float dt, int32_t substeps,
+                             float *qdd_out, float *tau_out, float *stop_out, uint32_t *status_out, int32_t R, void *stream);
 
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,

@@ -29,6 +29,7 @@
 #include "rmp2_hull.h"
 #include "rmp2_dynamics.h"
 #include "rmp2_forward_dynamics.h"
+#include "rmp2_joint_stops.h"
 
 using namespace rmp2;
 
@@ -2366,14 +2367,33 @@ void launch_dynamics_step(const rmp2_handle* h, float* q, float* qd, const float
   });
 }
 
-int dynamics_step_impl(rmp2_handle* h, const char* what, float* q, float* qd, const float* u, int accel, const float* lim, float dt,
-                       int substeps, int integrate, float* qdd_out, float* tau_out, int R, void* stream) {
+// The refusals the plant's steps share.  step_args_check: the drive, substeps and dt of rmp2_dynamics_step /
+// rmp2_dynamics_step_stops.  step_rows_check: R, the inertial table and the arrays every call needs; launch = false: R == 0, no-op.
+int step_args_check(rmp2_handle* h, const char* what, int drive, int substeps, float dt) {
+  if (drive != RMP2_DRIVE_TORQUE && drive != RMP2_DRIVE_ACCEL)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown drive " + std::to_string(drive));
+  if (substeps < 1) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": substeps < 1");
+  if (!std::isfinite(dt) || !(dt > 0.f)) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": dt must be finite and > 0");
+  return RMP2_OK;
+}
+
+int step_rows_check(rmp2_handle* h, const char* what, const float* q, const float* qd, const float* u, bool others_ok, int R,
+                    bool& launch) {
+  launch = false;
   if (R < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": R < 0");
   if (h->inert_n == 0)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no inertial table on this handle (call rmp2_set_inertials first)");
   if (R == 0) return RMP2_OK;
-  if (!q || !qd || !u || (!integrate && !qdd_out)) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": null array");
-  if (int rc = use_device(h)) return rc;
+  if (!q || !qd || !u || !others_ok) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": null array");
+  launch = true;
+  return use_device(h);
+}
+
+int dynamics_step_impl(rmp2_handle* h, const char* what, float* q, float* qd, const float* u, int accel, const float* lim, float dt,
+                       int substeps, int integrate, float* qdd_out, float* tau_out, int R, void* stream) {
+  bool launch;
+  if (int rc = step_rows_check(h, what, q, qd, u, integrate || qdd_out, R, launch)) return rc;
+  if (!launch) return RMP2_OK;
   hipStream_t s = (hipStream_t)stream;
   switch (h->n_template) {
     case 2: launch_dynamics_step<2>(h, q, qd, u, accel, lim, dt, substeps, integrate, qdd_out, tau_out, R, s); break;
@@ -2382,6 +2402,19 @@ int dynamics_step_impl(rmp2_handle* h, const char* what, float* q, float* qd, co
   }
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
+}
+
+// rmp2_dynamics_step_stops: the step with joint-limit stops (the kernel and its routines are rmp2_joint_stops.h)
+template <int N>
+void launch_dynamics_step_stops(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim,
+                                const float* qlo, const float* qhi, float dt, int substeps, float* qdd_out, float* tau_out,
+                                float* stop_out, uint32_t* status_out, int R, hipStream_t s) {
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  with_slots(h->n_slots_full, [&](auto S) {
+    hipLaunchKernelGGL((rmp2_dynamics_step_stops_kernel<N, S>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2], q,
+                       qd, u, accel, lim, qlo, qhi, dt, substeps, qdd_out, tau_out, stop_out, status_out, R);
+  });
 }
 
 }  // namespace
@@ -3887,12 +3920,29 @@ int rmp2_forward_dynamics(rmp2_handle* h, const float* q, const float* qd, const
 int rmp2_dynamics_step(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit, float dt,
                        int32_t substeps, float* qdd_out, float* tau_out, int32_t R, void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
-  if (drive != RMP2_DRIVE_TORQUE && drive != RMP2_DRIVE_ACCEL)
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "dynamics step: unknown drive " + std::to_string(drive));
-  if (substeps < 1) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "dynamics step: substeps < 1");
-  if (!std::isfinite(dt) || !(dt > 0.f)) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "dynamics step: dt must be finite and > 0");
+  if (int rc = step_args_check(h, "dynamics step", drive, substeps, dt)) return rc;
   return dynamics_step_impl(h, "dynamics step", q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, dt, substeps, 1, qdd_out, tau_out, R,
                             stream);
+}
+
+int rmp2_dynamics_step_stops(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
+                             const float* q_lower, const float* q_upper, float dt, int32_t substeps, float* qdd_out, float* tau_out,
+                             float* stop_out, uint32_t* status_out, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  const char* what = "dynamics step with stops";
+  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
+  bool launch;
+  if (int rc = step_rows_check(h, what, q, qd, u, q_lower && q_upper, R, launch)) return rc;
+  if (!launch) return RMP2_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int accel = drive == RMP2_DRIVE_ACCEL;
+  switch (h->n_template) {
+    case 2: launch_dynamics_step_stops<2>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, dt, substeps, qdd_out, tau_out, stop_out, status_out, R, s); break;
+    case 9: launch_dynamics_step_stops<9>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, dt, substeps, qdd_out, tau_out, stop_out, status_out, R, s); break;
+    default: launch_dynamics_step_stops<16>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, dt, substeps, qdd_out, tau_out, stop_out, status_out, R, s); break;
+  }
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
 }
 
 }  // extern "C"

@@ -67,6 +67,7 @@ class Engine:
         self._hulls_key = None     # the link hulls the handle holds (set_link_hulls), None = off
         self._inertials_key = None  # the inertial table and gravity the handle holds (set_inertials), None = off
         self._tau_limit = None     # (bytes, device tensor) of the last host tau_limit of dynamics_step: uploaded once per value
+        self._q_limits = None      # (bytes, lower, upper) of the last host q_limits of dynamics_step, likewise
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -575,27 +576,69 @@ class Engine:
             self._tau_limit = (key, torch.from_numpy(t).to(self.device))
         return self._tau_limit[1]
 
+    def _q_limits_device(self, q_limits):
+        try:
+            lower, upper = q_limits
+        except (TypeError, ValueError):
+            raise ValueError("q_limits must be a pair (lower, upper)") from None
+        on_device = [isinstance(x, torch.Tensor) and x.is_cuda for x in (lower, upper)]
+        if all(on_device):
+            _require_resident(self.device, q_lower=lower, q_upper=upper)
+            for name, x in (("lower", lower), ("upper", upper)):
+                if tuple(x.shape) != (self.n_dof,):
+                    raise ValueError(f"q_limits {name} must be [{self.n_dof}], got {list(x.shape)}")
+            return lower, upper
+        if any(on_device):
+            raise ValueError("q_limits: lower and upper must both be host arrays or both be device tensors")
+        lo, hi = (np.ascontiguousarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32) for x in (lower, upper))
+        for name, x in (("lower", lo), ("upper", hi)):
+            if x.shape != (self.n_dof,):
+                raise ValueError(f"q_limits {name} must be [{self.n_dof}], got {list(x.shape)}")
+        if not (lo <= hi).all():   # (false for a NaN as well; -inf / +inf = no limit on that side)
+            raise ValueError("q_limits must have lower <= upper and no NaN (-inf / +inf where a joint has no limit)")
+        key = lo.tobytes() + hi.tobytes()
+        if self._q_limits is None or self._q_limits[0] != key:   # (the same values again upload nothing)
+            self._q_limits = (key, torch.from_numpy(lo).to(self.device), torch.from_numpy(hi).to(self.device))
+        return self._q_limits[1], self._q_limits[2]
+
     def dynamics_step(self, q: torch.Tensor, qd: torch.Tensor, u: torch.Tensor, dt: float, substeps: int = 1, drive: str = "accel",
-                      tau_limit=None, qdd_out: Optional[torch.Tensor] = None, tau_out: Optional[torch.Tensor] = None) -> None:
+                      tau_limit=None, qdd_out: Optional[torch.Tensor] = None, tau_out: Optional[torch.Tensor] = None,
+                      q_limits=None, stop_out: Optional[torch.Tensor] = None, status_out: Optional[torch.Tensor] = None) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
         drive="torque": u is the torque, held and clamped.  tau_limit: [n] host array (uploaded once per value) or device tensor,
-        or None.  qdd_out / tau_out [R, n]: the last substep's qdd and applied torque.  Needs set_inertials."""
+        or None.  qdd_out / tau_out [R, n]: the last substep's qdd and applied torque.  Needs set_inertials.
+        q_limits = (lower, upper), [n] host arrays (validated, uploaded once per value) or device tensors: the step with
+        inelastic joint-limit stops (include/rmp2.h rmp2_dynamics_step_stops; urdf.read_joint_limits reads them).  stop_out
+        [R, n] fp32: the stops' torque of the last substep; status_out [R] int32: RMP2_STOP_ACTIVE (1) / RMP2_STOP_CAPPED (2) over
+        the substeps, the largest iteration count in bits 8 and up.  Both need q_limits.  None takes the call without stops."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
             raise ValueError(f"drive must be 'accel' or 'torque', got {drive!r}")
         q, qd, u = self._dynamics_rows("q, qd, u", q, qd, u)
         R = q.shape[0]
-        for name, o in (("qdd_out", qdd_out), ("tau_out", tau_out)):
+        for name, o in (("qdd_out", qdd_out), ("tau_out", tau_out), ("stop_out", stop_out)):
             if o is not None:
                 self._dynamics_out(name, o, (R, self.n_dof))
         lim = self._tau_limit_device(tau_limit)
         s = torch.cuda.current_stream(self.device).cuda_stream
         ptr = lambda t: None if t is None else t.data_ptr()
-        _native.check(self._lib.rmp2_dynamics_step(self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim),
-                                                   float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), R, s), self._h)
+        if q_limits is None:
+            if stop_out is not None or status_out is not None:
+                raise ValueError("stop_out / status_out need q_limits")
+            _native.check(self._lib.rmp2_dynamics_step(self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim),
+                                                       float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), R, s), self._h)
+            return
+        if status_out is not None:
+            if (not isinstance(status_out, torch.Tensor) or status_out.device != self.device or status_out.dtype != torch.int32
+                    or tuple(status_out.shape) != (R,) or not status_out.is_contiguous()):
+                raise ValueError(f"status_out must be a contiguous int32 [{R}] tensor on {self.device}")
+        lower, upper = self._q_limits_device(q_limits)
+        _native.check(self._lib.rmp2_dynamics_step_stops(self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim),
+                                                         lower.data_ptr(), upper.data_ptr(), float(dt), int(substeps), ptr(qdd_out),
+                                                         ptr(tau_out), ptr(stop_out), ptr(status_out), R, s), self._h)
 
     def differentiate(self, q: torch.Tensor, qd: torch.Tensor, frame: int):
         q, qd = _f32(q, self.device), _f32(qd, self.device)

@@ -600,6 +600,26 @@ def read_effort_limits(urdf_filepath: str, order: Sequence[str]) -> np.ndarray:
     return out
 
 
+def read_joint_limits(urdf_filepath: str, order: Sequence[str]):
+    """(lower, upper), float32 [n] each: the <limit lower= upper=> of the joints in `order` (rad, or m for a prismatic joint);
+    -inf / +inf for a continuous joint, a joint without <limit> or an absent attribute: the q_limits of Engine.dynamics_step."""
+    root = ElementTree.parse(urdf_filepath).getroot()
+    joints = {j.attrib["name"]: j for j in root.findall("joint")}
+    lower = np.full(len(order), -np.inf, dtype=np.float32)
+    upper = np.full(len(order), np.inf, dtype=np.float32)
+    for i, name in enumerate(order):
+        if name not in joints:
+            raise ValueError(f"{urdf_filepath}: no joint named {name!r}")
+        lim = joints[name].find("limit")
+        if lim is None or joints[name].attrib.get("type") == "continuous":
+            continue
+        if "lower" in lim.attrib:
+            lower[i] = float(lim.attrib["lower"])
+        if "upper" in lim.attrib:
+            upper[i] = float(lim.attrib["upper"])
+    return lower, upper
+
+
 def inertial_table(table: KinematicTable, inertials: dict) -> np.ndarray:
     """float32 [n_frames, 10] for rmp2_set_inertials: frame f's record describes its child link (table.link_names[f]) in FRAME
     coordinates, (m, cx, cy, cz, Ixx, Iyy, Izz, Ixy, Ixz, Iyz) -- c the centre of mass, the tensor about c in frame axes.
