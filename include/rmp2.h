@@ -597,7 +597,7 @@ int rmp2_inverse_dynamics(rmp2_handle *h, const float *q, const float *qd, const
  * After the torques the reference calls p.stepSimulation: the robot's own equations of motion answer them.  These three entry
  * points are that half for a fleet, on the model of rmp2_inverse_dynamics: the rigid bodies of the inertial table, a fixed base,
  * the gravity of rmp2_set_inertials; no damping, friction, rotor inertia, joint limits or contacts (joint-limit stops: the block
- * after this one, rmp2_dynamics_step_stops).  With
+ * after this one, rmp2_dynamics_step_stops; obstacle contacts: the one after that, rmp2_dynamics_step_contacts).  With
  * tau_id(a) = M(q) a + C(q, qd) qd + G(q), one routine serves both drives:
  *     qdd = qdd_in + M(q)^-1 (tau_applied - tau_id(qdd_in))
  *   torque drive:        qdd_in = 0, tau_applied = the caller's tau:  qdd = M^-1 (tau - C qd - G);
@@ -670,6 +670,51 @@ int rmp2_dynamics_step(rmp2_handle *h, float *q, float *qd, const float *u, int3
 int rmp2_dynamics_step_stops(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive,
                              const float *tau_limit, const float *q_lower, const float *q_upper, float dt, int32_t substeps,
                              float *qdd_out, float *tau_out, float *stop_out, uint32_t *status_out, int32_t R, void *stream);
+
+/* ---- obstacle contacts: the plant's step outside a table of spheres -----------------------------------------------------------
+ * rmp2_dynamics_step_contacts is rmp2_dynamics_step_stops with frictionless, inelastic, velocity-level contacts between the
+ * robot's link capsules (rmp2_set_contact_capsules: host [n_frames][8] = (a, radius, b, 0) in frame coordinates, a zero row =
+ * no capsule; NULL or n_frames == 0 switches them off) and a STATIC table of spheres shared by the fleet (device [K][4] =
+ * centre, radius; K <= 256).  Stops and contacts are solved together, one problem per substep.  At a substep's state (q, qd),
+ * with a, v* = qd + dt a and the box (l, h) of the block above, for each frame f with a non-zero capsule row and each sphere k:
+ *     X = the point of the capsule's world segment nearest the centre c_k;   n = (X - c_k) / |X - c_k|  (the fixed direction +z
+ *     where the centre lies on the segment: link_normal_length's convention);   gap g = |X - c_k| - r_k - r_f;
+ *     row J_fk[j] = n . (z_j x (X - o_j)) for a revolute ancestor dof j of f, n . z_j for a prismatic one, 0 otherwise (z_j, o_j:
+ *     the joint's world axis and origin);   bound b_fk = -max(g, 0) / dt: a pair already in penetration is not pushed out, it
+ *     only cannot go deeper -- the stops' rule.
+ * The CANDIDATES of a robot in a substep are the pairs with g <= d_act (metres, finite, >= 0), at most RMP2_MAX_CONTACTS; when
+ * more qualify the smallest gaps are taken, ties going to the lower pair index f K + k, and the excess is reported
+ * (RMP2_CONTACT_OVERFLOW).  The substep's velocity is
+ *     v = argmin 1/2 (v - v*)^T M(q) (v - v*)   s.t.   l <= v <= h,   J_c v >= b_c for every candidate c,
+ * which is unique (v = 0 is always feasible) and satisfies M (v - v*) = sigma + sum_c lambda_c J_c^T, lambda_c >= 0,
+ * lambda_c (J_c v - b_c) = 0, sigma as the block above's lambda.  CONTRACT: the result is the all-pairs solution whenever
+ * d_act >= dt x the largest approach speed of a pair and nothing overflows.  Then qd <- v, q <- q + dt v with the stops' exact
+ * landing and clamps.  Outputs of the last substep (each of the new ones may be NULL):
+ *     qdd_out, tau_out as above;  stop_out = sigma / dt;  contact_out [R][n_dof] = sum_c lambda_c J_c^T / dt;
+ *     contact_lambda [R][RMP2_MAX_CONTACTS] = lambda_c / dt, the normal force in N, 0 in empty slots;
+ *     contact_pair [R][RMP2_MAX_CONTACTS] int32 = f K + k, -1 in empty slots (slots in no particular order);
+ *     status_out: RMP2_STOP_ACTIVE, RMP2_STOP_CAPPED (the solver of stops or contacts stopped before optimality: the iteration
+ *     cap, or a row refused because it depends on the working set to fp32 resolution; the velocity returned violates no
+ *     constraint), RMP2_CONTACT_ACTIVE (some lambda_c > 0 in some substep), RMP2_CONTACT_OVERFLOW; iterations in bits 8.. .
+ * Solver: primal active set over the rows +-e_j and J_c from v = 0; M factored once per substep, one column M^-1 a_i per
+ * working row, the small Gram system solved every iteration (csrc/rmp2_contacts.h).  A substep in which a robot has no
+ * candidate runs the block above's substep itself: a robot without a candidate in any substep gets rmp2_dynamics_step_stops'
+ * results bit for bit with contact_* exactly 0 / -1, and with q_lower = q_upper = NULL (no limits) or limits far away
+ * rmp2_dynamics_step's.  K == 0 is the stops call.  The block above's edge behaviour holds; a non-finite sphere record makes
+ * every robot's outputs NaN.  Stream-ordered, no allocation, capturable.  Refusals as for the stops call (q_lower and q_upper
+ * both given or both NULL), and: no capsules set, K < 0, K > 256, a null table with K > 0, d_act not finite or < 0; a robot
+ * of more than 9 dofs: RMP2_ERR_UNSUPPORTED.  Friction, restitution, penetration recovery, self contacts and moving obstacles
+ * are not modelled; parity with PyBullet's solver is UNPINNED, as for the rest of the plant. */
+#define RMP2_MAX_CONTACTS 8
+#define RMP2_MAX_CONTACT_SPHERES 256
+#define RMP2_CONTACT_ACTIVE 4u     /* some contact carried force in some substep */
+#define RMP2_CONTACT_OVERFLOW 8u   /* more than RMP2_MAX_CONTACTS pairs qualified in some substep */
+int rmp2_set_contact_capsules(rmp2_handle *h, int32_t n_frames, const float *capsules /* host [n_frames][8]; NULL or 0 = off */);
+int rmp2_dynamics_step_contacts(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
+                                const float *q_lower, const float *q_upper /* both NULL = no limits */,
+                                const float *spheres /* device [K][4] */, int32_t K, float d_act, float dt, int32_t substeps,
+                                float *qdd_out, float *tau_out, float *stop_out, float *contact_out, float *contact_lambda,
+                                int32_t *contact_pair, uint32_t *status_out, int32_t R, void *stream);
 
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,

@@ -88,6 +88,12 @@ def lib():
         l.rmp2_dynamics_step_stops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int32, C.c_void_p]
+    if hasattr(l, "rmp2_dynamics_step_contacts"):   # (likewise for a diagnostic RMP2_LIB built before the contacts)
+        l.rmp2_set_contact_capsules.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        l.rmp2_dynamics_step_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                  C.c_void_p]
     l.rmp2_differentiate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_differentiate_euler.argtypes = l.rmp2_differentiate.argtypes

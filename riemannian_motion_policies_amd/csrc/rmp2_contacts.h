@@ -1,0 +1,563 @@
+// rmp2_contacts.h -- the plant's step with obstacle contacts (include/rmp2.h rmp2_dynamics_step_contacts).
+//
+// Frictionless, inelastic, velocity-level contacts between the robot's link capsules and a static shared table of spheres,
+// solved together with the joint-limit stops of rmp2_joint_stops.h.  Per substep, at the state (q, qd): a, v* = qd + dt a and
+// the velocity box (l, h) as there.  One kinematic walk over the program (id_visit, as fd_walk: the joints' world axes z_j and
+// origins o_j are stored when the walk passes them) forms, for every frame f with a capsule and every sphere k,
+//     X = the point of the capsule's world segment nearest the centre c_k,  n = (X - c_k) / |X - c_k|  (+z where X = c_k:
+//     link_normal_length's convention),  gap g = |X - c_k| - r_k - r_f,
+// keeps the pairs with g <= d_act -- at most kMaxContacts, the smallest gaps, ties to the lower pair index f K + k; the excess
+// is counted -- and writes each kept pair's row at once:  J[j] = n . (z_j x (X - o_j))  (revolute ancestor dof j),  n . z_j
+// (prismatic), 0 otherwise;  bound b = -max(g, 0) / dt.  The substep's velocity is
+//     v = argmin 1/2 (v - v*)^T M (v - v*)   s.t.   l <= v <= h,   J_c v >= b_c,
+// found by a primal active-set method over general rows a_i v >= beta_i (+e_j v >= l_j, -e_j v >= -h_j, J_c v >= b_c) from the
+// feasible start v = 0 (b <= 0, l <= 0 <= h):
+//   M is factored once per substep (in place, where fd_evaluate_saved stored it).  A row that enters the working set W gets its
+//   column Y_i = M^-1 a_i.  Each iteration forms the Gram matrix G = A_W Y_W, factors it (Cholesky, row by row), solves
+//   G mu = beta_W - A_W v*, x = v* + Y_W mu (dofs of W put on their bounds exactly);  if a row outside W is violated at x and
+//   decreases along x - v: go to the first such row on the segment and add it;  else take x, drop from W the most negative
+//   multiplier (never a dof with l_j == h_j), and stop when there is none.
+//   A Gram pivot below kContactPivot x its diagonal entry (a row that is dependent on W to fp32 resolution), or a row that
+//   would make W larger than the number of dofs: the row is left out and the substep ends at the current, feasible, iterate;
+//   this and the iteration cap (kContactMaxIter) are reported as RMP2_STOP_CAPPED.  A row outside W counts as violated /
+//   decreasing only beyond kContactTol x |a_i|_1 max|v*| (the box rows likewise, and x is clipped into the box when taken): two spheres on one spot give two identical rows, and the one outside
+//   W must not block on the other's rounding.
+// Every iterate is feasible (the box exactly, the contact rows to that tolerance).  A substep without a candidate runs
+// rmp2_joint_stops.h's substep, expression for expression.
+//
+// Per-lane storage (pointer + stride: on the device LDS, lane-interleaved, word k of lane l at k * 64 + l; on the host a local
+// array): U (the packed factor of M), the candidate rows J [8][N], the columns Y [N][N], the Gram factor and the multipliers.
+// These are indexed at run time (LDS addresses are per lane); every index into a REGISTER array is a compile-time constant
+// after unrolling -- dynamic picks are unrolled compares.  Host-compilable (tests/contacts_driver.cpp).
+#pragma once
+#include "rmp2_joint_stops.h"
+
+namespace rmp2 {
+
+constexpr int kMaxContacts = RMP2_MAX_CONTACTS;
+// Twice the worst iteration count of the fp64 restatement over every test fleet (tests/test_contacts_host.py).
+constexpr int kContactMaxIter = 14;
+constexpr float kContactPivot = 2.4e-7f;   // 4 x 2^-24: below it the pivot is its own rounding
+constexpr float kContactTol = 1e-5f;
+
+// words per lane: U, J, Y, the Gram factor, the multipliers
+constexpr int contact_words(int n) { return fd_tri(n) + kMaxContacts * n + n * n + fd_tri(n) + n; }
+
+template <int N>
+__host__ __device__ inline float ct_get(const float (&a)[N], int j) {
+  float r = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) r = i == j ? a[i] : r;
+  return r;
+}
+
+// The candidate search and the rows of one robot at q.  caps: [n_frames][8] (a, radius, b, 0) in frame coordinates; spheres:
+// [K][4], both read at uniform addresses.  Jr: the rows' storage.  cgap / cidx: gap and pair index per slot (cidx -1: empty).
+// Returns the number of candidates kept; excess: how many more qualified.
+template <int N, int SLOTS>
+__host__ __device__ inline int contact_candidates(const DevOp* ops, int n_ops, const float* caps, const float* spheres, int K,
+                                                  float d_act, const float (&q)[N], float* Jr, int stride,
+                                                  float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess) {
+  float ax[N][3], org[N][3];
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    for (int k = 0; k < 3; ++k) ax[j][k] = org[j][k] = 0.f;
+#pragma unroll
+  for (int c = 0; c < kMaxContacts; ++c) {
+    cgap[c] = 0.f;
+    cidx[c] = -1;
+  }
+  int count = 0, total = 0;
+  uint32_t revolute = 0u;
+  const float still[3] = {0.f, 0.f, 0.f};
+  IdState cur;
+  IdState slot[SLOTS > 0 ? SLOTS : 1];
+  for (int k = 0; k < n_ops; ++k) {
+    const DevOp& op = ops[k];
+    if (SLOTS > 0 && op.restore >= 0) {
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s)
+        if (op.restore == s) cur = slot[s];
+    }
+    const int qi = op.qidx;
+    float z[3];
+    id_visit(cur, op, ct_get<N>(q, qi), 0.f, 0.f, op.restore == -2, still, z);
+    if (SLOTS > 0 && op.save >= 0) {
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s)
+        if (op.save == s) slot[s] = cur;
+    }
+    if (qi >= 0) {
+      if (op.jtype == RMP2_JOINT_REVOLUTE) revolute |= 1u << qi;
+#pragma unroll
+      for (int j = 0; j < N; ++j)
+        if (j == qi)
+          for (int c = 0; c < 3; ++c) {
+            ax[j][c] = z[c];
+            org[j][c] = cur.p[c];
+          }
+    }
+    const float* cp = caps + (size_t)op.frame * 8;
+    bool has = false;
+    for (int i = 0; i < 8; ++i) has = has || cp[i] != 0.f;
+    if (!has || K <= 0) continue;
+    const float al[3] = {cp[0], cp[1], cp[2]}, dl[3] = {cp[4] - cp[0], cp[5] - cp[1], cp[6] - cp[2]};
+    const float rf = cp[3];
+    float A[3], D[3];
+    for (int i = 0; i < 3; ++i) {
+      A[i] = cur.R[3 * i + 0] * al[0] + cur.R[3 * i + 1] * al[1] + cur.R[3 * i + 2] * al[2] + cur.p[i];
+      D[i] = cur.R[3 * i + 0] * dl[0] + cur.R[3 * i + 1] * dl[1] + cur.R[3 * i + 2] * dl[2];
+    }
+    const float dd = id_dot(D, D);
+    const float inv_dd = dd > 0.f ? 1.f / dd : 0.f;
+    const uint32_t mask = op.anc_mask;
+    for (int s = 0; s < K; ++s) {
+      const float c[3] = {spheres[4 * s + 0], spheres[4 * s + 1], spheres[4 * s + 2]};
+      const float rs = spheres[4 * s + 3];
+      const float rel[3] = {c[0] - A[0], c[1] - A[1], c[2] - A[2]};
+      float t = id_dot(rel, D) * inv_dd;
+      t = fminf(fmaxf(t, 0.f), 1.f);
+      float X[3], n[3];
+      for (int i = 0; i < 3; ++i) {
+        X[i] = A[i] + t * D[i];
+        n[i] = X[i] - c[i];
+      }
+      const float dn = sqrtf(id_dot(n, n));
+      const float len = link_normal_length(n);   // (+z and 1 where the centre lies on the axis)
+      const float g = dn - rs - rf;
+      if (!(g <= d_act)) continue;   // (also a NaN gap)
+      ++total;
+      const int idx = op.frame * K + s;
+      int put = -1;
+      if (count < kMaxContacts) {
+        put = count++;
+      } else {   // the kept pair of largest (gap, index); it goes if the new pair is smaller
+        float wg = cgap[0];
+        int wi = cidx[0], ws = 0;
+#pragma unroll
+        for (int e = 1; e < kMaxContacts; ++e)
+          if (cgap[e] > wg || (cgap[e] == wg && cidx[e] > wi)) {
+            wg = cgap[e];
+            wi = cidx[e];
+            ws = e;
+          }
+        if (g < wg || (g == wg && idx < wi)) put = ws;
+      }
+      if (put < 0) continue;
+#pragma unroll
+      for (int e = 0; e < kMaxContacts; ++e)
+        if (e == put) {
+          cgap[e] = g;
+          cidx[e] = idx;
+        }
+      const float inv = 1.f / len;
+      const float nu[3] = {n[0] * inv, n[1] * inv, n[2] * inv};
+      float* row = Jr + (size_t)put * N * stride;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        float val = 0.f;
+        if ((mask >> j) & 1u) {
+          if ((revolute >> j) & 1u) {
+            const float d[3] = {X[0] - org[j][0], X[1] - org[j][1], X[2] - org[j][2]};
+            float zx[3];
+            id_cross(ax[j], d, zx);
+            val = id_dot(nu, zx);
+          } else {
+            val = id_dot(nu, ax[j]);
+          }
+        }
+        row[j * stride] = val;
+      }
+    }
+  }
+  excess = total - count;
+  return count;
+}
+
+// Row ids: [0, N) +e_j v >= l_j;  [N, 2N) -e_j v >= -h_j;  2N + c: J_c v >= b_c.
+template <int N>
+__host__ __device__ inline float ct_row_dot(int r, const float* Jr, int stride, const float (&x)[N]) {
+  if (r < N) return ct_get<N>(x, r);
+  if (r < 2 * N) return -ct_get<N>(x, r - N);
+  const float* row = Jr + (size_t)(r - 2 * N) * N * stride;
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < N; ++j) s += row[j * stride] * x[j];
+  return s;
+}
+
+template <int N>
+__host__ __device__ inline float ct_row_dot_col(int r, const float* Jr, const float* Yk, int stride) {
+  if (r < N) return Yk[r * stride];
+  if (r < 2 * N) return -Yk[(r - N) * stride];
+  const float* row = Jr + (size_t)(r - 2 * N) * N * stride;
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < N; ++j) s += row[j * stride] * Yk[j * stride];
+  return s;
+}
+
+__host__ __device__ inline int ct_slot(uint64_t wl, int i) { return (int)((wl >> (6 * i)) & 63u); }
+
+// The velocity of one substep with candidates.  U: the factor of M (fd_cholesky's).  nc candidates with bounds cb.  v: out, the
+// minimiser (or the feasible iterate at which the solver stopped).  sigma: the stops' multipliers (M (v - v*) = sigma + J^T
+// lamc), lamc: the contacts'.  Returns the number of iterations; capped: stopped before optimality (see the head).
+template <int N>
+__host__ __device__ inline int contacts_solve(const float* U, const float* Jr, float* Yw, float* Lw, float* mu, int stride,
+                                              const float (&vstar)[N], const float (&lb)[N], const float (&ub)[N], int nc,
+                                              const float (&cb)[kMaxContacts], float (&v)[N], float (&sigma)[N],
+                                              float (&lamc)[kMaxContacts], bool& capped) {
+  static_assert(6 * N <= 64 && 2 * N + kMaxContacts <= 64, "the working set is packed into 64 bits, 6 per slot");
+  int m = 0, it = 0;
+  uint64_t wl = 0u;      // the rows of W, slot by slot
+  uint64_t inW = 0u;     // bit r: row r is in W
+  capped = false;
+  float vmax = 0.f;   // the velocity scale of the problem
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    v[j] = 0.f;
+    vmax = fmaxf(vmax, fabsf(vstar[j]));
+  }
+  for (;;) {
+    if (it >= kContactMaxIter) {
+      capped = true;
+      break;
+    }
+    ++it;
+    // G = A_W Y_W = L L^T, row by row; the diagonal holds 1 / L_ii
+    bool refuse = false;
+    for (int i = 0; i < m; ++i) {
+      const int ri = ct_slot(wl, i);
+      float* Li = Lw + (size_t)(i * (i + 1) / 2) * stride;
+      for (int k = 0; k <= i; ++k) {
+        const float g = ct_row_dot_col<N>(ri, Jr, Yw + (size_t)k * N * stride, stride);
+        const float* Lk = Lw + (size_t)(k * (k + 1) / 2) * stride;
+        float s = g;
+        for (int p = 0; p < k; ++p) s -= Li[p * stride] * Lk[p * stride];
+        if (k < i) {
+          Li[k * stride] = s * Lk[k * stride];
+        } else {
+          if (!(s > kContactPivot * g) || !(s <= FLT_MAX)) refuse = true;
+          Li[i * stride] = 1.f / sqrtf(s);
+        }
+      }
+    }
+    if (refuse) {   // the row added last depends on the others: it stays out, the step ends here
+      --m;
+      inW &= ~(1ull << ct_slot(wl, m));
+      capped = true;
+      break;
+    }
+    // G mu = beta_W - A_W v*
+    for (int i = 0; i < m; ++i) {
+      const int ri = ct_slot(wl, i);
+      const float beta = ri < N ? ct_get<N>(lb, ri) : (ri < 2 * N ? -ct_get<N>(ub, ri - N) : ct_get<kMaxContacts>(cb, ri - 2 * N));
+      float s = beta - ct_row_dot<N>(ri, Jr, stride, vstar);
+      const float* Li = Lw + (size_t)(i * (i + 1) / 2) * stride;
+      for (int p = 0; p < i; ++p) s -= Li[p * stride] * mu[p * stride];
+      mu[i * stride] = s * Li[i * stride];
+    }
+    for (int i = m - 1; i >= 0; --i) {
+      float s = mu[i * stride];
+      for (int p = i + 1; p < m; ++p) s -= Lw[(size_t)(p * (p + 1) / 2 + i) * stride] * mu[p * stride];
+      mu[i * stride] = s * Lw[(size_t)(i * (i + 1) / 2 + i) * stride];
+    }
+    float x[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = vstar[j];
+    for (int i = 0; i < m; ++i) {
+      const float mi = mu[i * stride];
+      const float* Yi = Yw + (size_t)i * N * stride;
+#pragma unroll
+      for (int j = 0; j < N; ++j) x[j] += mi * Yi[j * stride];
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {   // (a dof of W stays on its bound exactly)
+      if ((inW >> j) & 1u) x[j] = lb[j];
+      if ((inW >> (N + j)) & 1u) x[j] = ub[j];
+      // W spans the dofs: every row of W is active at v, so the equality problem's solution IS v; what x differs by is the
+      // rounding of an often ill-conditioned Gram solve (two contacts on neighbouring links), and must not move the iterate
+      if (m == N) x[j] = v[j];
+    }
+    // the first row outside W that the segment from v to x meets
+    float alpha = 2.f, bval = 0.f;
+    int brow = -1;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const bool in = ((inW >> j) | (inW >> (N + j))) & 1u;
+      const bool below = x[j] < lb[j] - kContactTol * vmax, above = x[j] > ub[j] + kContactTol * vmax;
+      if (!in && (below || above)) {
+        const float b = below ? lb[j] : ub[j];
+        const float a = (b - v[j]) / (x[j] - v[j]);
+        if (a < alpha) {
+          alpha = a;
+          bval = b;
+          brow = below ? j : N + j;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kMaxContacts; ++c)
+      if (c < nc && !((inW >> (2 * N + c)) & 1u)) {
+        const float* row = Jr + (size_t)c * N * stride;
+        float jx = 0.f, jv = 0.f, jp = 0.f, rn = 0.f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          const float r = row[j * stride];
+          jx += r * x[j];
+          jv += r * v[j];
+          jp += r * (x[j] - v[j]);
+          rn += fabsf(r);
+        }
+        const float scale = rn * vmax;
+        if (jx < cb[c] - kContactTol * (scale + fabsf(cb[c])) && jp < -kContactTol * scale) {
+          const float a = (jv - cb[c]) / -jp;
+          if (a < alpha) {
+            alpha = a;
+            brow = 2 * N + c;
+          }
+        }
+      }
+    if (brow >= 0) {
+      alpha = alpha < 0.f ? 0.f : (alpha > 1.f ? 1.f : alpha);
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const bool in = ((inW >> j) | (inW >> (N + j))) & 1u;
+        float t = v[j] + alpha * (x[j] - v[j]);
+        t = t < lb[j] ? lb[j] : (t > ub[j] ? ub[j] : t);   // (a rounding must not leave the box)
+        v[j] = (brow == j || brow == N + j) ? bval : (in ? v[j] : t);
+      }
+      if (m >= N) {   // (W already spans the dofs: only a rounding can ask for more)
+        capped = true;
+        break;
+      }
+      float y[N];
+      const float* row = Jr + (size_t)(brow >= 2 * N ? brow - 2 * N : 0) * N * stride;
+#pragma unroll
+      for (int j = 0; j < N; ++j) y[j] = brow == j ? 1.f : (brow == N + j ? -1.f : (brow >= 2 * N ? row[j * stride] : 0.f));
+      {
+        float Ul[fd_tri(N)];
+#pragma unroll
+        for (int k = 0; k < fd_tri(N); ++k) Ul[k] = U[k * stride];
+        fd_solve<N>(Ul, y);
+      }
+      float* Ym = Yw + (size_t)m * N * stride;
+#pragma unroll
+      for (int j = 0; j < N; ++j) Ym[j * stride] = y[j];
+      mu[m * stride] = 0.f;
+      wl = (wl & ~(63ull << (6 * m))) | ((uint64_t)brow << (6 * m));
+      inW |= 1ull << brow;
+      ++m;
+      continue;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = x[j] < lb[j] ? lb[j] : (x[j] > ub[j] ? ub[j] : x[j]);   // (a rounding, below the tolerance)
+    float worst = 0.f;
+    int drop = -1;
+    for (int i = 0; i < m; ++i) {
+      const int ri = ct_slot(wl, i);
+      const int j = ri < N ? ri : ri - N;
+      const bool locked = ri < 2 * N && ct_get<N>(lb, j) == ct_get<N>(ub, j);
+      const float mi = mu[i * stride];
+      if (!locked && mi < worst) {
+        worst = mi;
+        drop = i;
+      }
+    }
+    if (drop < 0) break;
+    inW &= ~(1ull << ct_slot(wl, drop));
+    for (int i = drop; i + 1 < m; ++i) {
+      const float* Yn = Yw + (size_t)(i + 1) * N * stride;
+      float* Yi = Yw + (size_t)i * N * stride;
+#pragma unroll
+      for (int j = 0; j < N; ++j) Yi[j * stride] = Yn[j * stride];
+      mu[i * stride] = mu[(i + 1) * stride];
+      const uint64_t r = (uint64_t)ct_slot(wl, i + 1);
+      wl = (wl & ~(63ull << (6 * i))) | (r << (6 * i));
+    }
+    --m;
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) sigma[j] = 0.f;
+#pragma unroll
+  for (int c = 0; c < kMaxContacts; ++c) lamc[c] = 0.f;
+  for (int i = 0; i < m; ++i) {
+    const int ri = ct_slot(wl, i);
+    const float mi = mu[i * stride];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      if (ri == j) sigma[j] += mi;
+      if (ri == N + j) sigma[j] -= mi;
+    }
+#pragma unroll
+    for (int c = 0; c < kMaxContacts; ++c)
+      if (ri == 2 * N + c) lamc[c] = fmaxf(mi, 0.f);   // (negative only where the solver stopped early)
+  }
+  return it;
+}
+
+// rmp2_dynamics_step_contacts of one robot.  qlo / qhi: [n_dof] or both null (no limits).  contact_out [n_dof], lambda_out /
+// pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats.
+template <int N, int SLOTS>
+__host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, int n_ops, int n_dof, const float* inert,
+                                                             const float base_acc[3], float* q_io, float* qd_io,
+                                                             const float* u_in, bool accel, const float* lim, const float* qlo,
+                                                             const float* qhi, const float* caps, const float* spheres, int K,
+                                                             float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
+                                                             float* stop_out, float* contact_out, float* lambda_out,
+                                                             int32_t* pair_out, uint32_t* status_out, float* lds, int stride) {
+  float* Ms = lds;
+  float* Jr = Ms + (size_t)fd_tri(N) * stride;
+  float* Yw = Jr + (size_t)kMaxContacts * N * stride;
+  float* Lw = Yw + (size_t)N * N * stride;
+  float* mu = Lw + (size_t)fd_tri(N) * stride;
+  float q[N], qd[N], u[N], qdd[N], tapp[N], stop[N], cont[N], lamc[kMaxContacts];
+  int cidx[kMaxContacts];
+  float poison = 0.f;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    q[j] = j < n_dof ? q_io[j] : 0.f;
+    qd[j] = j < n_dof ? qd_io[j] : 0.f;
+    u[j] = j < n_dof ? u_in[j] : 0.f;
+    poison += q[j] * 0.f + qd[j] * 0.f + u[j] * 0.f;
+  }
+  float table_poison = 0.f;   // a non-finite sphere record: every robot NaN
+  for (int s = 0; s < 4 * K; ++s) table_poison += spheres[s] * 0.f;
+  uint32_t status = 0u;
+  int most = 0;
+  for (int s = 0; s < substeps; ++s) {
+    const uint32_t owned = fd_evaluate_saved<N, SLOTS>(ops, n_ops, n_dof, inert, base_acc, q, qd, u, accel, lim, qdd, tapp, Ms, stride);
+    float vstar[N], lb[N], ub[N], v[N], cgap[kMaxContacts];
+    uint32_t W = 0u, upper = 0u;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      vstar[j] = qd[j] + dt * qdd[j];
+      lb[j] = -INFINITY;
+      ub[j] = INFINITY;
+      if (qlo && j < n_dof && ((owned >> j) & 1u)) {
+        lb[j] = fminf((qlo[j] - q[j]) / dt, 0.f);
+        ub[j] = fmaxf((qhi[j] - q[j]) / dt, 0.f);
+      }
+      const bool below = vstar[j] < lb[j], above = vstar[j] > ub[j];
+      v[j] = below ? lb[j] : (above ? ub[j] : vstar[j]);
+      if (below || above) W |= 1u << j;
+      if (above) upper |= 1u << j;
+      cont[j] = 0.f;
+    }
+    int excess = 0;
+    const int nc = contact_candidates<N, SLOTS>(ops, n_ops, caps, spheres, K, d_act, q, Jr, stride, cgap, cidx, excess);
+    if (excess > 0) status |= RMP2_CONTACT_OVERFLOW;
+#pragma unroll
+    for (int c = 0; c < kMaxContacts; ++c) lamc[c] = 0.f;
+    if (nc == 0) {   // rmp2_joint_stops.h's substep, in its own words
+      if (!W) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          qd[j] += dt * qdd[j];
+          q[j] += dt * qd[j];
+          stop[j] = 0.f;
+        }
+        continue;
+      }
+      bool capped;
+      const int it = stops_solve<N>(Ms, stride, vstar, lb, ub, v, W, upper, stop, capped);
+      status |= RMP2_STOP_ACTIVE | (capped ? RMP2_STOP_CAPPED : 0u);
+      most = it > most ? it : most;
+    } else {
+      float Ul[fd_tri(N)], cb[kMaxContacts];
+#pragma unroll
+      for (int k = 0; k < fd_tri(N); ++k) Ul[k] = Ms[k * stride];
+      const bool ok = fd_cholesky<N>(Ul);
+#pragma unroll
+      for (int k = 0; k < fd_tri(N); ++k) Ms[k * stride] = Ul[k];
+#pragma unroll
+      for (int c = 0; c < kMaxContacts; ++c) cb[c] = -fmaxf(cgap[c], 0.f) / dt;
+      bool capped;
+      const int it = contacts_solve<N>(Ms, Jr, Yw, Lw, mu, stride, vstar, lb, ub, nc, cb, v, stop, lamc, capped);
+      most = it > most ? it : most;
+      bool any_stop = false, any_contact = false;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        any_stop = any_stop || stop[j] != 0.f;
+        if (!ok) v[j] = stop[j] = NAN;
+      }
+#pragma unroll
+      for (int c = 0; c < kMaxContacts; ++c) {
+        any_contact = any_contact || lamc[c] > 0.f;
+        if (c < nc) {
+          const float l = ok ? lamc[c] : NAN;
+          const float* row = Jr + (size_t)c * N * stride;
+#pragma unroll
+          for (int j = 0; j < N; ++j) cont[j] += l * row[j * stride];
+          lamc[c] = l / dt;
+        }
+      }
+      status |= (any_stop ? RMP2_STOP_ACTIVE : 0u) | (any_contact ? RMP2_CONTACT_ACTIVE : 0u) | (capped ? RMP2_STOP_CAPPED : 0u);
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      qdd[j] += (v[j] - vstar[j]) / dt;
+      stop[j] /= dt;
+      cont[j] /= dt;
+      qd[j] = v[j];
+      const float q0 = q[j];
+      float q1 = q0 + dt * v[j];
+      if (qlo && j < n_dof && ((owned >> j) & 1u)) {
+        const float lo = qlo[j], hi = qhi[j];
+        // a dof on a bound that its limit set lands on the limit; a rounding takes no dof that was inside outside
+        if (v[j] != 0.f && v[j] == lb[j]) q1 = lo;
+        if (v[j] != 0.f && v[j] == ub[j]) q1 = hi;
+        if (q0 >= lo && q1 < lo) q1 = lo;
+        if (q0 <= hi && q1 > hi) q1 = hi;
+      }
+      q[j] = q1;
+    }
+  }
+  const bool bad = !(poison == 0.f) || !(table_poison == 0.f);
+#pragma unroll
+  for (int j = 0; j < N; ++j)
+    if (j < n_dof) {
+      q_io[j] = bad ? NAN : q[j];
+      qd_io[j] = bad ? NAN : qd[j];
+      if (qdd_out) qdd_out[j] = bad ? NAN : qdd[j];
+      if (tau_out) tau_out[j] = bad ? NAN : tapp[j];
+      if (stop_out) stop_out[j] = bad ? NAN : stop[j];
+      if (contact_out) contact_out[j] = bad ? NAN : cont[j];
+    }
+#pragma unroll
+  for (int c = 0; c < kMaxContacts; ++c) {
+    if (lambda_out) lambda_out[c] = bad ? NAN : lamc[c];
+    if (pair_out) pair_out[c] = bad ? -1 : cidx[c];
+  }
+  if (status_out) *status_out = status | ((uint32_t)most << 8);
+}
+
+#if defined(__HIPCC__)
+// One lane per robot, one wave per block; the per-lane storage of the wave's 64 robots in LDS, lane-interleaved.
+template <int N, int SLOTS>
+__global__ void __launch_bounds__(kWave)
+rmp2_dynamics_step_contacts_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
+                                   float az, float* q, float* qd, const float* __restrict__ u, int accel,
+                                   const float* __restrict__ lim, const float* __restrict__ qlo, const float* __restrict__ qhi,
+                                   const float* __restrict__ caps, const float* __restrict__ spheres, int K, float d_act, float dt,
+                                   int substeps, float* __restrict__ qdd_out, float* __restrict__ tau_out,
+                                   float* __restrict__ stop_out, float* __restrict__ contact_out, float* __restrict__ lambda_out,
+                                   int32_t* __restrict__ pair_out, uint32_t* __restrict__ status_out, int R) {
+  static_assert(contact_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
+  __shared__ float lds[contact_words(N) * kWave];
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const size_t crow = (size_t)robot * kMaxContacts;
+  const float base_acc[3] = {ax, ay, az};
+  dynamics_step_contacts_robot<N, SLOTS>(prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim,
+                                         qlo, qhi, caps, spheres, K, d_act, dt, substeps, qdd_out ? qdd_out + row : nullptr,
+                                         tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
+                                         contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr,
+                                         pair_out ? pair_out + crow : nullptr, status_out ? status_out + robot : nullptr,
+                                         lds + threadIdx.x, kWave);
+}
+#endif
+
+}  // namespace rmp2

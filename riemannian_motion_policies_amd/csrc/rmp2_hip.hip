@@ -30,6 +30,7 @@
 #include "rmp2_dynamics.h"
 #include "rmp2_forward_dynamics.h"
 #include "rmp2_joint_stops.h"
+#include "rmp2_contacts.h"
 
 using namespace rmp2;
 
@@ -2417,6 +2418,21 @@ void launch_dynamics_step_stops(const rmp2_handle* h, float* q, float* qd, const
   });
 }
 
+// rmp2_dynamics_step_contacts: the step with stops and obstacle contacts (the kernel and its routines are rmp2_contacts.h)
+template <int N>
+void launch_dynamics_step_contacts(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim,
+                                   const float* qlo, const float* qhi, const float* spheres, int K, float d_act, float dt,
+                                   int substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,
+                                   float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s) {
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  with_slots(h->n_slots_full, [&](auto S) {
+    hipLaunchKernelGGL((rmp2_dynamics_step_contacts_kernel<N, S>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2],
+                       q, qd, u, accel, lim, qlo, qhi, h->d_contact_caps, spheres, K, d_act, dt, substeps, qdd_out, tau_out,
+                       stop_out, contact_out, lambda_out, pair_out, status_out, R);
+  });
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -2714,6 +2730,7 @@ int rmp2_destroy(rmp2_handle* h) {
   if (h->d_hull_planes) (void)hipFree(h->d_hull_planes);
   if (h->d_shull) (void)hipFree(h->d_shull);
   if (h->d_inert) (void)hipFree(h->d_inert);
+  if (h->d_contact_caps) (void)hipFree(h->d_contact_caps);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
   return RMP2_OK;
@@ -3940,6 +3957,60 @@ int rmp2_dynamics_step_stops(rmp2_handle* h, float* q, float* qd, const float* u
     case 2: launch_dynamics_step_stops<2>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, dt, substeps, qdd_out, tau_out, stop_out, status_out, R, s); break;
     case 9: launch_dynamics_step_stops<9>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, dt, substeps, qdd_out, tau_out, stop_out, status_out, R, s); break;
     default: launch_dynamics_step_stops<16>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, dt, substeps, qdd_out, tau_out, stop_out, status_out, R, s); break;
+  }
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
+int rmp2_set_contact_capsules(rmp2_handle* h, int32_t n_frames, const float* capsules) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (n_frames < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact capsules: n_frames < 0");
+  if (n_frames == 0 || !capsules) {   // off: rmp2_dynamics_step_contacts is refused again
+    h->contact_n = 0;
+    return RMP2_OK;
+  }
+  if (n_frames != h->n_frames)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact capsules: one record per frame (" + std::to_string(h->n_frames) + "), got " +
+                                                  std::to_string(n_frames));
+  for (int f = 0; f < n_frames; ++f) {
+    const float* r = capsules + (size_t)f * 8;
+    for (int k = 0; k < 8; ++k)
+      if (!std::isfinite(r[k]))
+        return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact capsules: frame " + std::to_string(f) + ": a value is not finite");
+    if (r[3] < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact capsules: frame " + std::to_string(f) + ": radius < 0");
+  }
+  if (int rc = use_device(h)) return rc;
+  if (!h->d_contact_caps) HIP_TRY(h, hipMalloc(&h->d_contact_caps, sizeof(float) * 8 * RMP2_MAX_FRAMES));
+  // (a synchronous copy: no launch still reads the old table)
+  HIP_TRY(h, hipMemcpy(h->d_contact_caps, capsules, sizeof(float) * 8 * n_frames, hipMemcpyHostToDevice));
+  h->contact_n = n_frames;
+  return RMP2_OK;
+}
+
+int rmp2_dynamics_step_contacts(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
+                                const float* q_lower, const float* q_upper, const float* spheres, int32_t K, float d_act, float dt,
+                                int32_t substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,
+                                float* contact_lambda, int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  const char* what = "dynamics step with contacts";
+  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
+  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K < 0");
+  if (K > RMP2_MAX_CONTACT_SPHERES)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K > " + std::to_string(RMP2_MAX_CONTACT_SPHERES));
+  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": d_act must be finite and >= 0");
+  if (h->contact_n == 0)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
+  if (h->n_template > 9)
+    return fail(h, RMP2_ERR_UNSUPPORTED, std::string(what) + ": robots of more than 9 dofs are not supported (this one has " +
+                                             std::to_string(h->n_dof) + ")");
+  bool launch;
+  if (int rc = step_rows_check(h, what, q, qd, u, (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres), R, launch)) return rc;
+  if (!launch) return RMP2_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int accel = drive == RMP2_DRIVE_ACCEL;
+  switch (h->n_template) {
+    case 2: launch_dynamics_step_contacts<2>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s); break;
+    default: launch_dynamics_step_contacts<9>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s); break;
   }
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;

@@ -91,6 +91,9 @@ struct rmp2_handle {
   // inverse dynamics (rmp2_set_inertials): off while inert_n == 0
   int inert_n = 0;
   float* d_inert = nullptr;             // [n_frames][10] inertial records
+  // obstacle contacts (rmp2_set_contact_capsules): off while contact_n == 0
+  int contact_n = 0;
+  float* d_contact_caps = nullptr;      // [n_frames][8] link capsules in frame coordinates
   float base_acc[3] = {0.f, 0.f, 9.81f};  // -g
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
   mutable bool quad_id_lean = false;       // the last quad launch ran the structured identity-leaf loop (launch_quad)

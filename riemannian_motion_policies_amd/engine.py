@@ -14,6 +14,8 @@ import torch
 from . import _native
 from . import descriptor as D
 
+MAX_CONTACTS = 8   # include/rmp2.h RMP2_MAX_CONTACTS
+
 
 def _f32(t: torch.Tensor, device) -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
@@ -504,6 +506,18 @@ class Engine:
     def has_inertials(self) -> bool:
         return self._inertials_key is not None
 
+    def set_contact_capsules(self, capsules) -> None:
+        """Link capsules for the contacts of dynamics_step(contacts=): host [n_frames, 8] = (a, radius, b, 0) per frame in frame
+        coordinates, a zero row where a frame has no capsule (urdf.contact_capsules builds them); None switches them off
+        (include/rmp2.h rmp2_set_contact_capsules).  Synchronous."""
+        if capsules is None:
+            _native.check(self._lib.rmp2_set_contact_capsules(self._h, 0, None), self._h)
+            return
+        c = np.ascontiguousarray(capsules.detach().cpu() if isinstance(capsules, torch.Tensor) else capsules, dtype=np.float32)
+        if c.ndim != 2 or c.shape[1] != 8:
+            raise ValueError(f"capsules must be [n_frames, 8], got {list(c.shape)}")
+        _native.check(self._lib.rmp2_set_contact_capsules(self._h, c.shape[0], c.ctypes.data), self._h)
+
     def inverse_dynamics(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Joint torques tau [R, n] = M(q) qdd + C(q, qd) qd + G(q) (include/rmp2.h rmp2_inverse_dynamics) on the current stream;
         q, qd, qdd [R, n] on the engine's device.  Needs set_inertials."""
@@ -603,7 +617,9 @@ class Engine:
 
     def dynamics_step(self, q: torch.Tensor, qd: torch.Tensor, u: torch.Tensor, dt: float, substeps: int = 1, drive: str = "accel",
                       tau_limit=None, qdd_out: Optional[torch.Tensor] = None, tau_out: Optional[torch.Tensor] = None,
-                      q_limits=None, stop_out: Optional[torch.Tensor] = None, status_out: Optional[torch.Tensor] = None) -> None:
+                      q_limits=None, stop_out: Optional[torch.Tensor] = None, status_out: Optional[torch.Tensor] = None,
+                      contacts: Optional[torch.Tensor] = None, d_act: float = 0.0, contact_out: Optional[torch.Tensor] = None,
+                      contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
@@ -612,7 +628,13 @@ class Engine:
         q_limits = (lower, upper), [n] host arrays (validated, uploaded once per value) or device tensors: the step with
         inelastic joint-limit stops (include/rmp2.h rmp2_dynamics_step_stops; urdf.read_joint_limits reads them).  stop_out
         [R, n] fp32: the stops' torque of the last substep; status_out [R] int32: RMP2_STOP_ACTIVE (1) / RMP2_STOP_CAPPED (2) over
-        the substeps, the largest iteration count in bits 8 and up.  Both need q_limits.  None takes the call without stops."""
+        the substeps, the largest iteration count in bits 8 and up.  Both need q_limits.  None takes the call without stops.
+        contacts = spheres [K, 4] fp32 on the engine's device (K <= 256; the static table the links must stay out of): the step
+        with stops AND frictionless inelastic contacts of the link capsules (include/rmp2.h rmp2_dynamics_step_contacts; needs
+        set_contact_capsules; q_limits optional).  d_act: metres, the gap up to which a pair is a candidate.  contact_out [R, n]
+        fp32: the contacts' joint torque; contact_lambda_out [R, 8] fp32: normal forces; contact_pair_out [R, 8] int32: frame * K
+        + sphere, -1 in empty slots; status_out also carries RMP2_CONTACT_ACTIVE (4) / RMP2_CONTACT_OVERFLOW (8).  Without
+        contacts= the call takes the paths above."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
@@ -625,6 +647,32 @@ class Engine:
         lim = self._tau_limit_device(tau_limit)
         s = torch.cuda.current_stream(self.device).cuda_stream
         ptr = lambda t: None if t is None else t.data_ptr()
+
+        def check_int(name, t, shape):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32
+                                  or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
+
+        if contacts is None:
+            if contact_out is not None or contact_lambda_out is not None or contact_pair_out is not None:
+                raise ValueError("contact_out / contact_lambda_out / contact_pair_out need contacts")
+        else:
+            _require_resident(self.device, contacts=contacts)
+            if contacts.dim() != 2 or contacts.shape[1] != 4:
+                raise ValueError(f"contacts must be [K, 4] spheres (centre, radius), got {list(contacts.shape)}")
+            if contact_out is not None:
+                self._dynamics_out("contact_out", contact_out, (R, self.n_dof))
+            if contact_lambda_out is not None:
+                self._dynamics_out("contact_lambda_out", contact_lambda_out, (R, MAX_CONTACTS))
+            check_int("contact_pair_out", contact_pair_out, (R, MAX_CONTACTS))
+            check_int("status_out", status_out, (R,))
+            lower, upper = (None, None) if q_limits is None else self._q_limits_device(q_limits)
+            _native.check(self._lib.rmp2_dynamics_step_contacts(
+                self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
+                contacts.data_ptr() if contacts.shape[0] else None, int(contacts.shape[0]), float(d_act), float(dt), int(substeps),
+                ptr(qdd_out), ptr(tau_out), ptr(stop_out), ptr(contact_out), ptr(contact_lambda_out), ptr(contact_pair_out),
+                ptr(status_out), R, s), self._h)
+            return
         if q_limits is None:
             if stop_out is not None or status_out is not None:
                 raise ValueError("stop_out / status_out need q_limits")

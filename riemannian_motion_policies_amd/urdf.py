@@ -423,6 +423,12 @@ def self_collision_capsules(urdf_filepath: str, table: KinematicTable, default_r
     return out
 
 
+def contact_capsules(urdf_filepath: str, table: KinematicTable, default_radius: float = 0.06, fitted="auto") -> np.ndarray:
+    """Capsules [n_frames, 8] for Engine.set_contact_capsules (include/rmp2.h rmp2_set_contact_capsules): rows 0 .. F - 1 of
+    self_collision_capsules -- the base link is static and takes no part in the plant's contacts."""
+    return np.ascontiguousarray(self_collision_capsules(urdf_filepath, table, default_radius=default_radius, fitted=fitted)[:table.n_frames])
+
+
 # ---- convex-hull link geometry (simulation.py:462-484: PyBullet loads each .obj collision mesh as its convex hull) ------------
 
 MAX_HULL_VERTICES = 512   # include/rmp2.h RMP2_MAX_HULL_VERTICES
