@@ -207,7 +207,7 @@ def solve_qp(M, vstar, l, h, J, b, cap=REFERENCE_CAP):
                 x[r_ - n] = h[r_ - n]
         if len(W) == n:          # (W spans the dofs: the equality problem's solution is v itself; x differs by rounding only)
             x = v.copy()
-        alpha, brow, bval = dtype.type(2), -1, zero
+        alpha, brow, bval, viol = dtype.type(2), -1, zero, zero      # (ties go to the row x violates most, relative to |a_i|_1)
         inbox = np.zeros(n, bool)
         for r_ in W:
             if r_ < 2 * n:
@@ -218,9 +218,10 @@ def solve_qp(M, vstar, l, h, J, b, cap=REFERENCE_CAP):
                 below, above = x[j] < l[j] - tol * vmax, x[j] > h[j] + tol * vmax
                 if not inbox[j] and (below or above):
                     bb = l[j] if below else h[j]
-                    a_ = (bb - v[j]) / (x[j] - v[j])
-                    if a_ < alpha:
-                        alpha, brow, bval = a_, (j if below else n + j), bb
+                    a_ = max((bb - v[j]) / (x[j] - v[j]), zero)
+                    w_ = abs(x[j] - bb)
+                    if a_ < alpha or (a_ == alpha and w_ > viol):
+                        alpha, brow, bval, viol = a_, (j if below else n + j), bb, w_
             for c in range(nc):
                 if 2 * n + c in W:
                     continue
@@ -228,9 +229,10 @@ def solve_qp(M, vstar, l, h, J, b, cap=REFERENCE_CAP):
                 jx, jv, jp = (row * x).sum(dtype=dtype), (row * v).sum(dtype=dtype), (row * pvec).sum(dtype=dtype)
                 scale = np.abs(row).sum(dtype=dtype) * vmax
                 if jx < beta[2 * n + c] - tol * (scale + abs(beta[2 * n + c])) and jp < -tol * scale:
-                    a_ = (jv - beta[2 * n + c]) / -jp
-                    if a_ < alpha:
-                        alpha, brow = a_, 2 * n + c
+                    a_ = max((jv - beta[2 * n + c]) / -jp, zero)
+                    w_ = (beta[2 * n + c] - jx) / np.abs(row).sum(dtype=dtype)
+                    if a_ < alpha or (a_ == alpha and w_ > viol):
+                        alpha, brow, viol = a_, 2 * n + c, w_
         if brow >= 0:
             alpha = min(max(alpha, zero), one)
             vn = np.clip(v + alpha * pvec, l, h)

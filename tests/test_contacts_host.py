@@ -18,7 +18,7 @@ parallel, so the Gram matrix of the working set multiplies that by its condition
 Hard invariants carry no K: joints inside their limits end inside, lambda >= 0, empty slots are 0 / -1.
 
 The iteration cap of the device routine (rmp2_contacts.h kContactMaxIter) is twice the fp64 loop's worst count over these fleets
-(WORST_ITERS, asserted below)."""
+(WORST_ITERS, asserted below), the stress catalogue of tests/contacts_scene.py and the random trees' fleets included."""
 import os
 import re
 import shutil
@@ -39,7 +39,7 @@ CSRC = os.path.join(ROOT, "riemannian_motion_policies_amd", "csrc")
 
 MEASURED = dict(res=0.0537, vel=10.29, force=4.018, step=16.0, gap=0.1174)     # the envelope's worst ratios
 K_RES, K_VEL, K_FORCE, K_STEP, K_GAP = 0.3, 50.0, 20.0, 70.0, 0.5
-WORST_ITERS = 7
+WORST_ITERS = 17
 DT = H.DT
 D_ACT = 0.03      # >= dt x the fleets' largest approach speed (joint rates up to 1 rad / s: below 3 m / s at any point of a link)
 STEP_SUBSTEPS = 4
@@ -65,7 +65,17 @@ def _ancestors(t, f):
     return out
 
 
-def contact_fleet(rng, t, inert, g, caps, B, n_spheres=16, n_base=6, dt=DT):
+def default_link_filter(t, f, depth):
+    """(links the joints can carry well clear; not the fingers, which sit within d_act of the hand and would triple its pairs)"""
+    return depth(f) >= min(3, t.n_dof) and t.joint_type[f] != 2
+
+
+def movable_link_filter(t, f, depth):
+    """Any capsule frame with a movable ancestor (the random trees: few frames, many of them prismatic)."""
+    return depth(f) >= 1
+
+
+def contact_fleet(rng, t, inert, g, caps, B, n_spheres=16, n_base=6, dt=DT, link_filter=default_link_filter, tries=1000):
     """(q, qd, qdd [B, n] fp32, spheres [n_spheres, 4] fp32) of a fleet whose table is shared: n_base base states inside the limits
     (every second one with two joints within reach of a limit), two or three spheres touching links of each (gap 0 .. 1 mm, on the
     side a joint motion carries the link to), robots = a base state + noise of 2 mrad with random qd, qdd; every fourth robot is
@@ -74,8 +84,9 @@ def contact_fleet(rng, t, inert, g, caps, B, n_spheres=16, n_base=6, dt=DT):
     lo64, hi64 = np.maximum(lo.astype(np.float64), -3.0), np.minimum(hi.astype(np.float64), 3.0)
     n = t.n_dof
     depth = lambda f: bin(int(sum(1 << int(t.q_index[a]) for a in _ancestors(t, f) if t.joint_type[a] != 0 and t.q_index[a] >= 0))).count("1")
-    # (links the joints can carry well clear; not the fingers, which sit within d_act of the hand and would triple its pairs)
-    frames = [f for f in CR.capsule_frames(caps) if depth(f) >= min(3, n) and t.joint_type[f] != 2]
+    frames = [f for f in CR.capsule_frames(caps) if link_filter(t, f, depth)]
+    if not frames:
+        raise AssertionError("no link to touch")
     base_q = lo64 + (hi64 - lo64) * rng.uniform(0.2, 0.8, (n_base, n))
     for b in range(1, n_base, 2):
         for j in rng.choice(n, 2, replace=False):
@@ -88,7 +99,7 @@ def contact_fleet(rng, t, inert, g, caps, B, n_spheres=16, n_base=6, dt=DT):
         for s in range(3 if b % 2 == 0 else 2):
             if len(spheres) >= n_spheres:
                 break
-            for _ in range(1000):      # (a sphere that some link can never get clear of is proposed again)
+            for _ in range(tries):      # (a sphere that some link can never get clear of is proposed again)
                 free = [f_ for f_ in frames if f_ not in used] or frames
                 f = free[rng.integers(len(free))]
                 A = R[f][b] @ caps[f, 0:3].astype(np.float64) + p[f][b]
@@ -228,7 +239,7 @@ def step_ratio(c, got):
     return max((np.abs(got["q"] - c["ref"]["q"]).max(1) / bq).max(), (np.abs(got["qd"] - c["ref"]["qd"]).max(1) / bqd).max())
 
 
-def check_device_kkt(c, got, what):
+def check_device_kkt(c, got, what, K_GAP=K_GAP, K_FORCE=K_FORCE):
     """The KKT conditions from the device's own contact_pair / contact_lambda with the rows rebuilt in fp64: lambda >= 0; lambda
     above the force bound only on a pair whose linearised gap is within the gap bound of 0; no candidate below minus that bound;
     empty slots 0 / -1; joints inside their limits end inside."""
@@ -256,9 +267,81 @@ def input_conditions(cases):
                 iters=int(cat("iters").max()))
 
 
+# ---- contacts on random trees -------------------------------------------------------------------------------------------------
+# The N = 9 instantiation with fewer than 9 dofs (padded), 0, 1 and 2 save slots, contact rows with prismatic ancestor columns
+# (n . z_j) and branches whose anc_mask zeroes stored dofs.  The bounds' K's are the trees' own, by the same rule: 4 x the
+# envelope's worst ratio on these fleets (MEASURED_TREES), rounded up to one significant figure.
+MEASURED_TREES = dict(res=0.0597, vel=31.79, force=10.33, step=28.25, gap=0.2875)     # the envelope's worst ratios on the trees
+K_TREES = dict(res=0.3, vel=200.0, force=50.0, step=200.0, gap=2.0)
+TREE_R = 65
+
+
+def random_capsules(rng, t):
+    """[n_frames, 8] float32: per frame no capsule (20 %), a sphere (20 %) or a capsule, radius 0.03 .. 0.06."""
+    caps = np.zeros((t.n_frames, 8), np.float32)
+    for f in range(t.n_frames):
+        kind = rng.uniform()
+        a = rng.uniform(-0.05, 0.05, 3)
+        b = a + rng.uniform(-0.15, 0.15, 3)
+        if kind >= 0.2:
+            caps[f, 0:3], caps[f, 3], caps[f, 4:7] = a, rng.uniform(0.03, 0.06), (a if kind < 0.4 else b)
+    return caps
+
+
+def prismatic_ancestors(t, f):
+    """The dofs of the prismatic joints on the path from frame f to the base (f's own joint included)."""
+    return {int(t.q_index[a]) for a in _ancestors(t, f) if t.joint_type[a] == 2 and t.q_index[a] >= 0}
+
+
+TREE_ATTEMPTS = 3      # capsule draws per tree before it is left out (most trees are too small to get clear of a sphere they touch)
+_tree_fleets = {}
+
+
+def tree_fleets(tmp_dir, R=TREE_R):
+    """[(name, table, inertials, caps, q, qd, qdd, spheres)]: the random trees of test_forward_dynamics_host.random_robots(seed=0)
+    with at most 9 dofs on which the fleet builder succeeds, with random capsules (seeded per tree and attempt)."""
+    if R not in _tree_fleets:
+        out = []
+        for k, (name, t, inert) in enumerate(H.random_robots(tmp_dir, seed=0)):
+            if t.n_dof > 9:
+                continue
+            for attempt in range(TREE_ATTEMPTS):
+                rng = np.random.default_rng(700 + k + 100 * attempt)
+                caps = random_capsules(rng, t)
+                try:
+                    fleet = contact_fleet(rng, t, inert, H.GRAVITY, caps, R, 16, 4, link_filter=movable_link_filter, tries=60)
+                except AssertionError:
+                    continue
+                out.append((name, t, inert, caps, *fleet))
+                break
+        _tree_fleets[R] = out
+    return _tree_fleets[R]
+
+
+_tree_cases = {}
+
+
+def tree_cases(tmp_dir, substeps=1, R=TREE_R):
+    """contact_cases on tree_fleets, the trees' gravity, both drives per tree; beside the usual fields `slots`, `prismatic` (how
+    many prismatic dofs the contact links have among their ancestors) and `prismatic_row` (the most of them in one row)."""
+    if (substeps, R) in _tree_cases:
+        return _tree_cases[(substeps, R)]
+    out = []
+    for name, t, inert, caps, q, qd, qdd, spheres in tree_fleets(tmp_dir, R):
+        limits = JR.table_limits(t)
+        pris = [prismatic_ancestors(t, f) for f in CR.capsule_frames(caps)]
+        for drive, u, lim in fleet_inputs(t, inert, H.GRAVITY, q, qd, qdd):
+            ref = CR.dynamics_step(t, inert, caps, spheres, D_ACT, q, qd, u, drive, DT, substeps, lim, limits, H.GRAVITY)
+            out.append(dict(name=name, t=t, inert=inert, g=H.GRAVITY, caps=caps, spheres=spheres, q=q, qd=qd, u=u, drive=drive, lim=lim,
+                            limits=limits, ref=ref, substeps=substeps, R=R, K=len(spheres), slots=int(t.depth_first_schedule()[3]),
+                            prismatic=len(set().union(*pris)), prismatic_row=max(len(p) for p in pris)))
+    _tree_cases[(substeps, R)] = out
+    return out
+
+
 # ---- 1: the reference ----------------------------------------------------------------------------------------------------------
 
-def test_fleets_meet_the_input_conditions_and_the_iteration_cap(cases, steps, golden_dir):
+def test_fleets_meet_the_input_conditions_and_the_iteration_cap(cases, steps, golden_dir, tmp_path_factory):
     cond = input_conditions(cases)
     print(cond)
     assert cond["active"] >= 0.30 and cond["two"] >= 0.05 and cond["both"] >= 0.05 and cond["none"] >= 0.20, cond
@@ -266,9 +349,20 @@ def test_fleets_meet_the_input_conditions_and_the_iteration_cap(cases, steps, go
     gpu = gpu_cases(golden_dir)
     worst = max(cond["iters"], input_conditions(steps)["iters"], input_conditions(gpu)["iters"])
     assert not any(c["ref"]["capped"].any() or c["ref"]["overflow"].any() for c in steps + gpu)
+    assert worst == 7, worst                                      # (the touching fleets alone, as before the catalogue)
+    import contacts_scene as CS                                  # (it imports this module)
+    stress = CS.catalogue(golden_dir)
+    assert not any(c["ref"]["capped"].any() for c in stress)
+    tmp = tmp_path_factory.mktemp("trees")
+    trees = tree_cases(tmp) + tree_cases(tmp, substeps=STEP_SUBSTEPS)
+    assert not any(c["ref"]["capped"].any() for c in trees)
+    steps4 = [c["ref_step"] for c in CS.with_steps(stress)]
+    assert not any(r["capped"].any() for r in steps4)
+    worst = max(worst, input_conditions(stress)["iters"], input_conditions(trees)["iters"], max(int(r["iters"].max()) for r in steps4))
     assert worst == WORST_ITERS, worst
     src = open(os.path.join(CSRC, "rmp2_contacts.h")).read()
-    assert int(re.search(r"kContactMaxIter = (\d+);", src).group(1)) == 2 * WORST_ITERS
+    assert int(re.search(r"#define RMP2_CONTACT_MAX_ITER (\d+)\n", src).group(1)) == 2 * WORST_ITERS
+    assert "constexpr int kContactMaxIter = RMP2_CONTACT_MAX_ITER;" in src
 
 
 def _robot_problem(c, r):
@@ -386,7 +480,7 @@ def run_driver(exe, tmp_path, c, substeps=1, spheres=None, limits="case", d_act=
     return CR.read_driver_output(str(tmp_path / "out.bin"), len(q), c["t"].n_dof)
 
 
-def flags_agree(c, status):
+def flags_agree(c, status, K_FORCE=K_FORCE):
     """The device's flags against the reference's, where the reference is clear of the decision: a robot whose reference has a
     contact force above the force bound has RMP2_CONTACT_ACTIVE; one without a candidate in any substep has neither it nor
     overflow; nothing is capped or overflowed."""
@@ -596,6 +690,77 @@ def test_driver_runs_clean_under_the_host_sanitizers(tmp_path_factory, cases, tm
     c = _panda(cases)
     plain = run_driver(exe, tmp_path, c, substeps=2)
     assert np.isfinite(plain["qd"]).all()
+
+
+# ---- 4: random trees ----------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def trees(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("trees")
+    return tree_cases(tmp), tree_cases(tmp, substeps=STEP_SUBSTEPS)
+
+
+def test_default_link_filter_keeps_the_existing_fleets_bytes(golden_dir):
+    import hashlib
+    c = contact_cases(golden_dir, seed=511, fleets=(("panda", 65),), n_spheres=16)[0]
+    h = hashlib.sha256()
+    for k in ("q", "qd", "u", "spheres"):
+        h.update(np.ascontiguousarray(c[k]).tobytes())
+    assert h.hexdigest() == "f8387f1c7479e37b32aa1be8dab8fa344f217c58a20f3e36bfa3c424521e8207"      # (taken before the parameter existed)
+
+
+def tree_cover(one):
+    """What the trees' fleets are for, asserted on the fleets and not on the trees' names."""
+    dofs, slots = {c["t"].n_dof for c in one}, {c["slots"] for c in one}
+    assert len({c["name"] for c in one}) >= 4
+    assert 9 in dofs and any(3 <= n <= 8 for n in dofs) and {0, 1, 2} <= slots, (dofs, slots)
+    assert max(c["prismatic"] for c in one) >= 3 and max(c["prismatic_row"] for c in one) >= 2
+    for c in one:
+        cond = input_conditions([c])
+        assert cond["active"] >= 0.30 and cond["none"] >= 0.20 and cond["capped"] == 0 and cond["overflow"] == 0, (c["name"], cond)
+
+
+def test_tree_fleets_cover_padded_dofs_slots_and_prismatic_columns(trees):
+    tree_cover(trees[0])
+    rows = 0      # contact rows with a prismatic column, and rows whose link's anc_mask leaves out a dof of the tree
+    for c in trees[0]:
+        J, k = c["ref"]["J"], c["ref"]["n_cand"]
+        pris = sorted(set().union(*[prismatic_ancestors(c["t"], f) for f in CR.capsule_frames(c["caps"])]))
+        rows += sum(int((J[r, :k[r]][:, pris] != 0).any(1).sum()) for r in range(len(k))) if pris else 0
+    assert rows >= 100
+
+
+def test_envelope_backs_the_tree_bounds(trees):
+    worst = envelope_ratios(*trees)
+    print("envelope worst ratios on the trees", worst)
+    for k, K in K_TREES.items():
+        assert np.isclose(K, _round_up_1sf(4 * MEASURED_TREES[k])), (k, K, MEASURED_TREES[k])
+        assert np.isclose(worst[k], MEASURED_TREES[k], rtol=1e-3), (k, worst[k], MEASURED_TREES[k])
+
+
+def test_device_routine_on_the_cpu_on_trees_within_half_of_each_tree_bound(driver, stops_driver, trees, tmp_path):
+    import test_joint_stops_host as SH
+    worst = dict(res=0.0, vel=0.0, force=0.0, step=0.0, gap=0.0)
+    strong = 0
+    for c in trees[0]:
+        d = run_driver(driver, tmp_path, c)
+        for k, v in zip(("res", "vel", "force", "gap"), one_step_ratios(c, d)):
+            worst[k] = max(worst[k], float(v))
+        strong += check_device_kkt(c, d, c["name"], K_TREES["gap"], K_TREES["force"])
+        flags_agree(c, d["status"], K_TREES["force"])
+        s = SH.run_driver(stops_driver, tmp_path, c["t"], c["inert"], c["q"], c["qd"], c["u"], c["drive"], c["lim"], c["limits"], 1, c["g"])
+        clear = c["ref"]["n_cand"] == 0
+        assert clear.sum() >= 0.2 * len(clear)
+        for k in ("q", "qd", "qdd", "tau", "stop"):
+            assert _bits_equal(d[k][clear], s[k][clear]), (c["name"], k)
+    for c in trees[1]:
+        d = run_driver(driver, tmp_path, c, substeps=c["substeps"])
+        worst["step"] = max(worst["step"], float(step_ratio(c, d)))
+        flags_agree(c, d["status"], K_TREES["force"])
+    print("CPU driver worst ratios on the trees", worst, "strong contacts", strong)
+    assert strong >= 100
+    for k, K in K_TREES.items():
+        assert worst[k] <= 0.5 * K, (k, worst[k], K)
 
 
 def test_contact_capsules_are_the_self_collision_rows_without_the_base():
