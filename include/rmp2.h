@@ -716,6 +716,42 @@ int rmp2_dynamics_step_contacts(rmp2_handle *h, float *q, float *qd, const float
                                 float *qdd_out, float *tau_out, float *stop_out, float *contact_out, float *contact_lambda,
                                 int32_t *contact_pair, uint32_t *status_out, int32_t R, void *stream);
 
+/* ---- obstacle contacts with per-robot lists over a shared pool of spheres -----------------------------------------------------
+ * rmp2_dynamics_step_contacts_lists is rmp2_dynamics_step_contacts with every robot's own set of spheres: robot r's spheres are
+ * spheres[csr_index[i]] for i in [csr_offset[r], csr_offset[r + 1]), in list order, out of a pool `spheres` (device [K][4],
+ * 16-byte aligned, K <= RMP2_MAX_CONTACT_POOL).  csr_offset (device [R + 1]) and csr_index (device [csr_offset[R]]) have the
+ * layout of rmp2_obstacles' fields of those names: the arrays built for rmp2_step's RMP2_OBS_RAGGED_SPHERES feed the plant
+ * unchanged.  Everything else is the block above word for word: the pairs are (frame with a capsule, list entry); gap, normal,
+ * row and bound; the candidates (g <= d_act, at most RMP2_MAX_CONTACTS, smallest gaps, ties to the lower pair index); solver,
+ * landing, clamps, outputs and status flags.  contact_pair stays f K + k with K the POOL's size and k the POOL index (not the
+ * position in the list).
+ * Bit for bit: a robot with an empty list gets rmp2_dynamics_step_stops' results, contact_* exactly 0 / -1;  a robot whose list
+ * is strictly ascending gets the results of rmp2_dynamics_step_contacts on the compacted table spheres[list] (status word
+ * included), contact_pair f K' + k' becoming f K + list[k'] -- the evaluation order (frames outer, entries inner) and every
+ * expression are the same code, and the tie order survives a monotone map.  A robot's results depend on no other robot's list,
+ * not on R and not on its lane.  Unsorted lists: the same candidate set; slot order and bits may differ.  A repeated index is
+ * two pairs with identical rows (as in the policy's ragged mode); both may take a slot.
+ * INVALID lists are refused per robot, on the device (the host cannot see device arrays): a negative csr_offset[r], a negative
+ * length, a length above RMP2_MAX_CONTACT_LIST, or an entry outside [0, K).  No record is read through a bad entry (every entry
+ * is range-checked, once per launch, before anything is read through it); every output row of that robot is NaN, its
+ * contact_pair -1 and its status_out exactly RMP2_CONTACT_LIST_INVALID; other robots are untouched.  That csr_index holds
+ * csr_offset[r + 1] entries is the caller's contract, as for rmp2_step.  A non-finite record makes the robots that LIST it NaN
+ * (the scan covers a robot's own entries, not the pool); the others are untouched.
+ * Stream-ordered, no allocation, no host read-back of csr_offset: capturable.  Refusals as for rmp2_dynamics_step_contacts
+ * except that the table's cap of 256 is the list's, not the pool's, and: csr_offset or csr_index NULL with R > 0, K < 0,
+ * K > RMP2_MAX_CONTACT_POOL, a null or misaligned pool with K > 0; a robot of more than 9 dofs: RMP2_ERR_UNSUPPORTED.  K == 0
+ * is accepted: every list must then be empty to be valid. */
+#define RMP2_MAX_CONTACT_LIST 256          /* entries per robot */
+#define RMP2_MAX_CONTACT_POOL (1 << 24)    /* records in the pool; 32 * K must fit the int32 pair index */
+#define RMP2_CONTACT_LIST_INVALID 16u      /* status_out of a robot whose list was refused (alone: no other bit, no iterations) */
+int rmp2_dynamics_step_contacts_lists(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
+                                      const float *q_lower, const float *q_upper /* both NULL = no limits */,
+                                      const float *spheres /* device [K][4] */, int32_t K,
+                                      const int32_t *csr_offset /* device [R+1] */,
+                                      const int32_t *csr_index /* device [csr_offset[R]] */, float d_act, float dt,
+                                      int32_t substeps, float *qdd_out, float *tau_out, float *stop_out, float *contact_out,
+                                      float *contact_lambda, int32_t *contact_pair, uint32_t *status_out, int32_t R, void *stream);
+
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,
  * plain steps on shared or ragged sphere tables, both fleets beyond 8 192 robots -- the two steps are ONE grid (the first

@@ -56,13 +56,122 @@ __host__ __device__ inline float ct_get(const float (&a)[N], int j) {
   return r;
 }
 
-// The candidate search and the rows of one robot at q.  caps: [n_frames][8] (a, radius, b, 0) in frame coordinates; spheres:
-// [K][4], both read at uniform addresses.  Jr: the rows' storage.  cgap / cidx: gap and pair index per slot (cidx -1: empty).
-// Returns the number of candidates kept; excess: how many more qualified.
-template <int N, int SLOTS>
-__host__ __device__ inline int contact_candidates(const DevOp* ops, int n_ops, const float* caps, const float* spheres, int K,
-                                                  float d_act, const float (&q)[N], float* Jr, int stride,
-                                                  float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess) {
+// Where a robot's sphere records come from.  The candidate search and the step are written once over a source, which says how
+// many records the robot has (count) and what the pair index f K + k counts in (pool); the arithmetic on a record is the same
+// code for both, only the fetch differs (if constexpr on kList).
+struct SphereRec {
+  float c[3], r;
+};
+
+// The fleet's shared table: every record in table order, read at uniform addresses.
+struct SphereTable {
+  const float* spheres;
+  int K;
+  static constexpr bool kList = false;
+  __host__ __device__ int count() const { return K; }
+  __host__ __device__ int pool() const { return K; }
+};
+
+// One robot's list over a shared pool (rmp2_dynamics_step_contacts_lists): records pool[index[i]], i = 0 .. len - 1, in list
+// order.  The addresses are the lane's own: a record is one 16-byte load (the pool is 16-byte aligned), and the cursor keeps the
+// next entry's record and the index after it in flight while the arithmetic runs on the current one, so that neither of the two
+// dependent fetches (index, then record) is waited for inside a trip.  scan() range-checks every entry BEFORE anything is read
+// through it and empties an invalid list: the cursor never sees an entry that was not checked.
+struct SphereList {
+  const float* spheres;   // the pool [K][4]
+  int K;
+  const int32_t* index;   // the robot's entries
+  int len;                // how many; < 0 or > RMP2_MAX_CONTACT_LIST: invalid
+  static constexpr bool kList = true;
+  __host__ __device__ int count() const { return len; }
+  __host__ __device__ int pool() const { return K; }
+  __host__ __device__ SphereRec record(int k) const {
+    SphereRec r;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float4 v = *reinterpret_cast<const float4*>(spheres + 4 * (size_t)k);
+    r.c[0] = v.x, r.c[1] = v.y, r.c[2] = v.z, r.r = v.w;
+#else
+    __builtin_memcpy(&r, spheres + 4 * (size_t)k, sizeof(r));
+#endif
+    return r;
+  }
+  __host__ __device__ float scan(bool& invalid) {
+    invalid = len < 0 || len > RMP2_MAX_CONTACT_LIST;
+    if (invalid) len = 0;
+    float p = 0.f;
+    for (int i = 0; i < len; ++i) {
+      const int k = index[i];
+      if ((uint32_t)k >= (uint32_t)K) {   // (also a negative entry)
+        invalid = true;
+        continue;
+      }
+      const SphereRec r = record(k);
+      p += r.c[0] * 0.f;
+      p += r.c[1] * 0.f;
+      p += r.c[2] * 0.f;
+      p += r.r * 0.f;
+    }
+    if (invalid) len = 0;
+    return p;
+  }
+  struct Cursor {
+    SphereRec rec;    // the record of the entry that next() hands out next
+    int k, k_next;    // that entry's index and the index after it
+    __host__ __device__ void begin(const SphereList& l) {
+      k = k_next = 0;
+      rec = SphereRec{{0.f, 0.f, 0.f}, 0.f};
+      if (l.len > 0) {
+        k = l.index[0];
+        rec = l.record(k);
+      }
+      if (l.len > 1) k_next = l.index[1];
+    }
+    // entry s's record and (returned) its index in the pool; the fetches of entry s + 1's record and of entry s + 2's index
+    // are issued before the caller uses what it got
+    __host__ __device__ int next(const SphereList& l, int s, float (&c)[3], float& rs) {
+      c[0] = rec.c[0], c[1] = rec.c[1], c[2] = rec.c[2];
+      rs = rec.r;
+#if defined(__HIP_DEVICE_COMPILE__)
+      // The four values enter the trip as the table's four loads do -- defined here, in this order -- and not as loop-carried
+      // registers: the optimiser orders the operands of a sum by where its terms are defined, and the contraction into fma
+      // follows that order, so as loop-carried values the dot products round differently from the table form's.  This leans on
+      // the compiler; the guard is tests/test_gpu_contacts_lists.py
+      // test_catalogue_in_one_launch_equals_the_shared_call_per_group_bit_for_bit, which fails when a compiler release orders
+      // them otherwise.  The robust form -- explicit fmaf in id_dot, or contraction switched off -- changes the table kernel's
+      // code and bits as well, and is left for a change that may do that.
+      asm volatile("" : "+v"(c[0]));
+      asm volatile("" : "+v"(c[1]));
+      asm volatile("" : "+v"(c[2]));
+      asm volatile("" : "+v"(rs));
+#endif
+      const int k_now = k;
+      if (s + 1 < l.len) {
+        k = k_next;
+        rec = l.record(k);
+      }
+      if (s + 2 < l.len) k_next = l.index[s + 2];
+      return k_now;
+    }
+  };
+};
+
+// Robot r's span of csr_index from csr_offset [R + 1]: the entries start at index + beg; returns their number, or -1 where the
+// offsets give no list (a negative start or a negative length).  A length above RMP2_MAX_CONTACT_LIST is returned as it is:
+// SphereList::scan refuses it.
+__host__ __device__ inline int contact_list_span(const int32_t* csr_offset, int r, int& beg) {
+  const int b = csr_offset[r], e = csr_offset[r + 1];
+  beg = b < 0 ? 0 : b;
+  return b < 0 || e < b ? -1 : e - b;
+}
+
+// The candidate search and the rows of one robot at q.  caps: [n_frames][8] (a, radius, b, 0) in frame coordinates, read at
+// uniform addresses; src: the robot's spheres (above).  Jr: the rows' storage.  cgap / cidx: gap and pair index per slot (cidx
+// -1: empty).  Returns the number of candidates kept; excess: how many more qualified.
+template <int N, int SLOTS, class Src>
+__host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_ops, const float* caps, Src src,
+                                                       float d_act, const float (&q)[N], float* Jr, int stride,
+                                                       float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess) {
+  const int K = src.count();   // the robot's records (the pair index is made of src.pool())
   float ax[N][3], org[N][3];
 #pragma unroll
   for (int j = 0; j < N; ++j)
@@ -116,9 +225,17 @@ __host__ __device__ inline int contact_candidates(const DevOp* ops, int n_ops, c
     const float dd = id_dot(D, D);
     const float inv_dd = dd > 0.f ? 1.f / dd : 0.f;
     const uint32_t mask = op.anc_mask;
+    SphereList::Cursor cursor;
+    if constexpr (Src::kList) cursor.begin(src);
     for (int s = 0; s < K; ++s) {
-      const float c[3] = {spheres[4 * s + 0], spheres[4 * s + 1], spheres[4 * s + 2]};
-      const float rs = spheres[4 * s + 3];
+      float c[3], rs;
+      int sk = s;   // the record's index in the pool
+      if constexpr (Src::kList) {
+        sk = cursor.next(src, s, c, rs);
+      } else {
+        c[0] = src.spheres[4 * s + 0], c[1] = src.spheres[4 * s + 1], c[2] = src.spheres[4 * s + 2];
+        rs = src.spheres[4 * s + 3];
+      }
       const float rel[3] = {c[0] - A[0], c[1] - A[1], c[2] - A[2]};
       float t = id_dot(rel, D) * inv_dd;
       t = fminf(fmaxf(t, 0.f), 1.f);
@@ -132,7 +249,7 @@ __host__ __device__ inline int contact_candidates(const DevOp* ops, int n_ops, c
       const float g = dn - rs - rf;
       if (!(g <= d_act)) continue;   // (also a NaN gap)
       ++total;
-      const int idx = op.frame * K + s;
+      const int idx = op.frame * src.pool() + sk;
       int put = -1;
       if (count < kMaxContacts) {
         put = count++;
@@ -177,6 +294,14 @@ __host__ __device__ inline int contact_candidates(const DevOp* ops, int n_ops, c
   }
   excess = total - count;
   return count;
+}
+
+// (the shared table: [K][4] read at uniform addresses)
+template <int N, int SLOTS>
+__host__ __device__ inline int contact_candidates(const DevOp* ops, int n_ops, const float* caps, const float* spheres, int K,
+                                                  float d_act, const float (&q)[N], float* Jr, int stride,
+                                                  float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess) {
+  return contact_candidates_from<N, SLOTS>(ops, n_ops, caps, SphereTable{spheres, K}, d_act, q, Jr, stride, cgap, cidx, excess);
 }
 
 // Row ids: [0, N) +e_j v >= l_j;  [N, 2N) -e_j v >= -h_j;  2N + c: J_c v >= b_c.
@@ -410,16 +535,28 @@ __host__ __device__ inline int contacts_solve(const float* U, const float* Jr, f
   return it;
 }
 
-// rmp2_dynamics_step_contacts of one robot.  qlo / qhi: [n_dof] or both null (no limits).  contact_out [n_dof], lambda_out /
-// pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats.
-template <int N, int SLOTS>
+template <bool LIST>
+__host__ __device__ inline auto contact_source(const float* spheres, int K, const int32_t* list, int list_len) {
+  if constexpr (LIST) return SphereList{spheres, K, list, list_len};
+  else return SphereTable{spheres, K};
+}
+
+// rmp2_dynamics_step_contacts of one robot, and with LIST rmp2_dynamics_step_contacts_lists of one robot: the same routine, the
+// robot's spheres being the table spheres [K][4] itself or the list_len records spheres[list[i]] of it (contact_list_span gives
+// list and list_len from csr_offset / csr_index).  qlo / qhi: [n_dof] or both null (no limits).  contact_out [n_dof], lambda_out
+// / pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats.  The spheres are scanned
+// once, before the substeps: a non-finite record makes the robot NaN, an invalid list NaN with the status word
+// RMP2_CONTACT_LIST_INVALID alone (its substeps run on no spheres, and nothing is read through its entries).
+template <int N, int SLOTS, bool LIST = false>
 __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, int n_ops, int n_dof, const float* inert,
                                                              const float base_acc[3], float* q_io, float* qd_io,
                                                              const float* u_in, bool accel, const float* lim, const float* qlo,
                                                              const float* qhi, const float* caps, const float* spheres, int K,
                                                              float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
                                                              float* stop_out, float* contact_out, float* lambda_out,
-                                                             int32_t* pair_out, uint32_t* status_out, float* lds, int stride) {
+                                                             int32_t* pair_out, uint32_t* status_out, float* lds, int stride,
+                                                             const int32_t* list = nullptr, int list_len = 0) {
+  auto src = contact_source<LIST>(spheres, K, list, list_len);
   float* Ms = lds;
   float* Jr = Ms + (size_t)fd_tri(N) * stride;
   float* Yw = Jr + (size_t)kMaxContacts * N * stride;
@@ -435,8 +572,13 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
     u[j] = j < n_dof ? u_in[j] : 0.f;
     poison += q[j] * 0.f + qd[j] * 0.f + u[j] * 0.f;
   }
-  float table_poison = 0.f;   // a non-finite sphere record: every robot NaN
-  for (int s = 0; s < 4 * K; ++s) table_poison += spheres[s] * 0.f;
+  float table_poison = 0.f;   // a non-finite sphere record: every robot it belongs to NaN
+  bool invalid = false;
+  if constexpr (LIST) {
+    table_poison = src.scan(invalid);
+  } else {
+    for (int s = 0; s < 4 * src.K; ++s) table_poison += src.spheres[s] * 0.f;
+  }
   uint32_t status = 0u;
   int most = 0;
   for (int s = 0; s < substeps; ++s) {
@@ -459,7 +601,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
       cont[j] = 0.f;
     }
     int excess = 0;
-    const int nc = contact_candidates<N, SLOTS>(ops, n_ops, caps, spheres, K, d_act, q, Jr, stride, cgap, cidx, excess);
+    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess);
     if (excess > 0) status |= RMP2_CONTACT_OVERFLOW;
 #pragma unroll
     for (int c = 0; c < kMaxContacts; ++c) lamc[c] = 0.f;
@@ -527,7 +669,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
       q[j] = q1;
     }
   }
-  const bool bad = !(poison == 0.f) || !(table_poison == 0.f);
+  const bool bad = !(poison == 0.f) || !(table_poison == 0.f) || invalid;
 #pragma unroll
   for (int j = 0; j < N; ++j)
     if (j < n_dof) {
@@ -543,7 +685,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
     if (lambda_out) lambda_out[c] = bad ? NAN : lamc[c];
     if (pair_out) pair_out[c] = bad ? -1 : cidx[c];
   }
-  if (status_out) *status_out = status | ((uint32_t)most << 8);
+  if (status_out) *status_out = invalid ? RMP2_CONTACT_LIST_INVALID : status | ((uint32_t)most << 8);
 }
 
 #if defined(__HIPCC__)
@@ -571,6 +713,37 @@ rmp2_dynamics_step_contacts_kernel(const DevProgram* __restrict__ prog, const fl
                                          contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr,
                                          pair_out ? pair_out + crow : nullptr, status_out ? status_out + robot : nullptr,
                                          lds + threadIdx.x, kWave);
+}
+
+// The same with every robot's own list over a shared pool: the lanes' trip counts and sphere addresses differ.
+template <int N, int SLOTS>
+__global__ void __launch_bounds__(kWave)
+rmp2_dynamics_step_contacts_lists_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
+                                         float az, float* q, float* qd, const float* __restrict__ u, int accel,
+                                         const float* __restrict__ lim, const float* __restrict__ qlo,
+                                         const float* __restrict__ qhi, const float* __restrict__ caps,
+                                         const float* __restrict__ spheres, int K, const int32_t* __restrict__ csr_offset,
+                                         const int32_t* __restrict__ csr_index, float d_act, float dt, int substeps,
+                                         float* __restrict__ qdd_out, float* __restrict__ tau_out, float* __restrict__ stop_out,
+                                         float* __restrict__ contact_out, float* __restrict__ lambda_out,
+                                         int32_t* __restrict__ pair_out, uint32_t* __restrict__ status_out, int R) {
+  static_assert(contact_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
+  __shared__ float lds[contact_words(N) * kWave];
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const size_t crow = (size_t)robot * kMaxContacts;
+  const float base_acc[3] = {ax, ay, az};
+  int beg;
+  const int len = contact_list_span(csr_offset, robot, beg);
+  dynamics_step_contacts_robot<N, SLOTS, true>(prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0,
+                                               lim, qlo, qhi, caps, spheres, K, d_act, dt, substeps,
+                                               qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr,
+                                               stop_out ? stop_out + row : nullptr, contact_out ? contact_out + row : nullptr,
+                                               lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
+                                               status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave,
+                                               csr_index + beg, len);
 }
 #endif
 

@@ -2435,6 +2435,16 @@ void launch_dynamics_step_contacts(const rmp2_handle* h, float* q, float* qd, co
 
 }  // namespace
 
+// rmp2_dynamics_step_contacts_lists: the same with per-robot lists over a pool.  Its kernels and their launcher are a translation
+// unit of their own (rmp2_contacts_lists_tu.hip), so that this unit's device code is what it is without them.
+namespace rmp2 {
+void launch_dynamics_step_contacts_lists(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim,
+                                         const float* qlo, const float* qhi, const float* spheres, int K, const int32_t* csr_offset,
+                                         const int32_t* csr_index, float d_act, float dt, int substeps, float* qdd_out,
+                                         float* tau_out, float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out,
+                                         uint32_t* status_out, int R, hipStream_t s);
+}
+
 // =========================================================================================
 // C ABI
 // =========================================================================================
@@ -4012,6 +4022,39 @@ int rmp2_dynamics_step_contacts(rmp2_handle* h, float* q, float* qd, const float
     case 2: launch_dynamics_step_contacts<2>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s); break;
     default: launch_dynamics_step_contacts<9>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s); break;
   }
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
+int rmp2_dynamics_step_contacts_lists(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
+                                      const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
+                                      const int32_t* csr_offset, const int32_t* csr_index, float d_act, float dt, int32_t substeps,
+                                      float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
+                                      int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  const char* what = "dynamics step with contact lists";
+  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
+  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K < 0");
+  if (K > RMP2_MAX_CONTACT_POOL)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K > " + std::to_string(RMP2_MAX_CONTACT_POOL));
+  if (K > 0 && spheres && ((uintptr_t)spheres & 15u))
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": the pool must be 16-byte aligned");
+  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": d_act must be finite and >= 0");
+  if (h->contact_n == 0)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
+  if (h->n_template > 9)
+    return fail(h, RMP2_ERR_UNSUPPORTED, std::string(what) + ": robots of more than 9 dofs are not supported (this one has " +
+                                             std::to_string(h->n_dof) + ")");
+  bool launch;
+  if (int rc = step_rows_check(h, what, q, qd, u,
+                               (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres) && csr_offset && csr_index, R, launch))
+    return rc;
+  if (!launch) return RMP2_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int accel = drive == RMP2_DRIVE_ACCEL;
+  launch_dynamics_step_contacts_lists(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index, d_act, dt,
+                                      substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R,
+                                      s);   // (N in {2, 9} by the handle's template size, SLOTS by its program)
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }

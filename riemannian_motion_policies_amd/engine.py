@@ -15,6 +15,9 @@ from . import _native
 from . import descriptor as D
 
 MAX_CONTACTS = 8   # include/rmp2.h RMP2_MAX_CONTACTS
+MAX_CONTACT_LIST = 256        # include/rmp2.h RMP2_MAX_CONTACT_LIST: entries per robot of dynamics_step(contact_lists=)
+MAX_CONTACT_POOL = 1 << 24    # include/rmp2.h RMP2_MAX_CONTACT_POOL: records in its pool
+CONTACT_LIST_INVALID = 16     # include/rmp2.h RMP2_CONTACT_LIST_INVALID: status_out of a robot whose list was refused
 
 
 def _f32(t: torch.Tensor, device) -> torch.Tensor:
@@ -70,6 +73,7 @@ class Engine:
         self._inertials_key = None  # the inertial table and gravity the handle holds (set_inertials), None = off
         self._tau_limit = None     # (bytes, device tensor) of the last host tau_limit of dynamics_step: uploaded once per value
         self._q_limits = None      # (bytes, lower, upper) of the last host q_limits of dynamics_step, likewise
+        self._empty_index = None   # one int32 on the device: csr_index of dynamics_step(contact_lists=) when every list is empty
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -517,6 +521,8 @@ class Engine:
         if c.ndim != 2 or c.shape[1] != 8:
             raise ValueError(f"capsules must be [n_frames, 8], got {list(c.shape)}")
         _native.check(self._lib.rmp2_set_contact_capsules(self._h, c.shape[0], c.ctypes.data), self._h)
+        if self._empty_index is None:   # (here, not in the step: dynamics_step allocates nothing and can be captured)
+            self._empty_index = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def inverse_dynamics(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Joint torques tau [R, n] = M(q) qdd + C(q, qd) qd + G(q) (include/rmp2.h rmp2_inverse_dynamics) on the current stream;
@@ -619,7 +625,8 @@ class Engine:
                       tau_limit=None, qdd_out: Optional[torch.Tensor] = None, tau_out: Optional[torch.Tensor] = None,
                       q_limits=None, stop_out: Optional[torch.Tensor] = None, status_out: Optional[torch.Tensor] = None,
                       contacts: Optional[torch.Tensor] = None, d_act: float = 0.0, contact_out: Optional[torch.Tensor] = None,
-                      contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None) -> None:
+                      contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None,
+                      contact_lists=None) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
@@ -634,7 +641,13 @@ class Engine:
         set_contact_capsules; q_limits optional).  d_act: metres, the gap up to which a pair is a candidate.  contact_out [R, n]
         fp32: the contacts' joint torque; contact_lambda_out [R, 8] fp32: normal forces; contact_pair_out [R, 8] int32: frame * K
         + sphere, -1 in empty slots; status_out also carries RMP2_CONTACT_ACTIVE (4) / RMP2_CONTACT_OVERFLOW (8).  Without
-        contacts= the call takes the paths above."""
+        contacts= the call takes the paths above.
+        contact_lists = (csr_offset [R + 1], csr_index) int32 on the engine's device, with contacts = a POOL [K, 4] (K up to
+        MAX_CONTACT_POOL): every robot's own spheres, robot r's being contacts[csr_index[csr_offset[r]:csr_offset[r + 1]]] (at most
+        MAX_CONTACT_LIST of them) -- the arrays of obstacles(spheres=, csr_offset=, csr_index=) feed the plant unchanged
+        (include/rmp2.h rmp2_dynamics_step_contacts_lists).  contact_pair_out stays frame * K + the POOL index.  The lists are
+        checked on the device: a robot with an invalid list (an entry outside [0, K), more than MAX_CONTACT_LIST entries, a
+        negative length) gets NaN rows and status_out == CONTACT_LIST_INVALID; nothing is read back, the call stays capturable."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
@@ -654,6 +667,8 @@ class Engine:
                 raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
 
         if contacts is None:
+            if contact_lists is not None:
+                raise ValueError("contact_lists needs contacts (the pool the lists index)")
             if contact_out is not None or contact_lambda_out is not None or contact_pair_out is not None:
                 raise ValueError("contact_out / contact_lambda_out / contact_pair_out need contacts")
         else:
@@ -667,6 +682,24 @@ class Engine:
             check_int("contact_pair_out", contact_pair_out, (R, MAX_CONTACTS))
             check_int("status_out", status_out, (R,))
             lower, upper = (None, None) if q_limits is None else self._q_limits_device(q_limits)
+            if contact_lists is not None:
+                try:
+                    csr_offset, csr_index = contact_lists
+                except (TypeError, ValueError):
+                    raise ValueError("contact_lists must be a pair (csr_offset, csr_index)") from None
+                for name, t, shape in (("csr_offset", csr_offset, (R + 1,)), ("csr_index", csr_index, None)):
+                    if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32
+                            or not t.is_contiguous() or (t.dim() != 1 if shape is None else tuple(t.shape) != shape)):
+                        raise ValueError(f"contact_lists {name} must be a contiguous int32 {'1-D' if shape is None else list(shape)} "
+                                         f"tensor on {self.device}")
+                if csr_index.numel() == 0:   # every list empty: the C ABI still wants a readable pointer (it cannot see the counts)
+                    csr_index = self._empty_index   # (made by set_contact_capsules; without capsules the call is refused anyway)
+                _native.check(self._lib.rmp2_dynamics_step_contacts_lists(
+                    self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
+                    contacts.data_ptr() if contacts.shape[0] else None, int(contacts.shape[0]), csr_offset.data_ptr(),
+                    ptr(csr_index), float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), ptr(stop_out),
+                    ptr(contact_out), ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s), self._h)
+                return
             _native.check(self._lib.rmp2_dynamics_step_contacts(
                 self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
                 contacts.data_ptr() if contacts.shape[0] else None, int(contacts.shape[0]), float(d_act), float(dt), int(substeps),

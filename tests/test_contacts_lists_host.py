@@ -1,0 +1,349 @@
+"""Per-robot obstacle lists over a shared pool (include/rmp2.h rmp2_dynamics_step_contacts_lists) on the host: the list form of
+the device routine of rmp2_contacts.h run on the CPU through tests/contacts_lists_driver.cpp, against the shared-table form of
+the same routine (tests/contacts_driver.cpp) BIT FOR BIT wherever the contract promises it, against the stops' driver on empty
+lists, and against the fp64 reference of tests/contacts_reference.py applied to spheres[list] per robot within the bounds of
+tests/test_contacts_host.py, unchanged (K_RES, K_VEL, K_FORCE, K_GAP on the robots kept by contacts_scene.kept).  The invalid
+lists also run under the host sanitizers, on a pool allocated at exactly K records.  No GPU.  Helpers at the top are shared
+with tests/test_gpu_contacts_lists.py."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import contacts_reference as CR
+import contacts_scene as CS
+import forward_dynamics_reference as FR
+import joint_stops_reference as JR
+import test_contacts_host as S
+from test_contacts_host import D_ACT, DT, ROOT
+
+MAX_LIST = 256
+LIST_INVALID = 16
+INT32_MIN = -2 ** 31
+FLOATS = ("q", "qd", "qdd", "tau", "stop", "contact", "lam")
+
+
+# ---- pools and lists ----------------------------------------------------------------------------------------------------------
+
+def filler(n, start=0):
+    """n spheres far from every robot, all different."""
+    k = np.arange(start, start + n, dtype=np.float32)
+    return np.stack([40.0 + 0.5 * k, -30.0 - 0.25 * k, 20.0 + 0.125 * k, np.full(len(k), 0.05, np.float32)], 1).astype(np.float32)
+
+
+def embed(rng, table, K_pool):
+    """(pool [K_pool, 4], pos [len(table)] ascending): the table's records at random positions among far-away filler."""
+    pos = np.sort(rng.choice(K_pool, len(table), replace=False))
+    pool = filler(K_pool)
+    pool[pos] = table
+    return pool, pos
+
+
+def csr(lists):
+    """(csr_offset [R + 1], csr_index) int32 of the lists, one after the other."""
+    off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32)
+    idx = np.concatenate([np.asarray(l, np.int64) for l in lists] + [np.zeros(0, np.int64)]).astype(np.int32)
+    return off, idx
+
+
+def map_pairs(pair, lst, K_pool):
+    """contact_pair of the compacted table spheres[lst] (f K' + k') in the pool's terms (f K + lst[k']); -1 stays."""
+    pair, lst = np.asarray(pair), np.asarray(lst, np.int64)
+    if len(lst) == 0:
+        return pair.copy()
+    f, k = np.divmod(np.maximum(pair, 0), len(lst))
+    return np.where(pair >= 0, f * K_pool + lst[k], -1).astype(np.int32)
+
+
+def unmap_pairs(pair, lst, K_pool):
+    """The inverse on a list without regard to order: the pool's pair index as the FIRST position of that record in lst."""
+    pair, lst = np.asarray(pair), np.asarray(lst, np.int64)
+    first = {int(k): i for i, k in reversed(list(enumerate(lst)))}
+    out = np.full(pair.shape, -1, np.int32)
+    for i, p in np.ndenumerate(pair):
+        if p >= 0:
+            out[i] = (int(p) // K_pool) * len(lst) + first[int(p) % K_pool]
+    return out
+
+
+def same_rows(got, want, rows_got, rows_want, what):
+    for k in FLOATS:
+        assert S._bits_equal(got[k][rows_got], want[k][rows_want]), (what, k)
+    assert np.array_equal(got["status"][rows_got], want["status"][rows_want]), what
+
+
+def all_nan(d, rows, what):
+    for k in FLOATS:
+        assert np.isnan(d[k][rows]).all(), (what, k)
+    assert (d["pair"][rows] == -1).all(), what
+
+
+# ---- the drivers ---------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver")
+
+
+@pytest.fixture(scope="module")
+def lists_driver(tmp_path_factory):
+    return S._build(tmp_path_factory, "contacts_lists_driver.cpp", "contacts_lists_driver")
+
+
+@pytest.fixture(scope="module")
+def lists_driver_san(tmp_path_factory):
+    return S._build(tmp_path_factory, "contacts_lists_driver.cpp", "contacts_lists_driver_san",
+                    ("-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"))
+
+
+@pytest.fixture(scope="module")
+def stops_driver(tmp_path_factory):
+    return S._build(tmp_path_factory, "joint_stops_driver.cpp", "joint_stops_driver")
+
+
+def run_lists(exe, tmp_path, c, pool, off, idx, substeps=1, rows=slice(None)):
+    """The list driver on the case's robots `rows`: contacts_reference.read_driver_output's dict.  A sanitizer report fails it:
+    the exit status must be 0 and nothing may be written to stderr."""
+    q, qd, u = c["q"][rows], c["qd"][rows], c["u"][rows]
+    path = str(tmp_path / "lin.bin")
+    CR.write_driver_input(path, c["t"], c["inert"], c["caps"], pool, D_ACT, q, qd, u, c["drive"], c["lim"], c["limits"], DT,
+                          substeps, c["g"])
+    off, idx = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(idx, np.int32)
+    assert len(off) == len(q) + 1
+    with open(path, "ab") as f:
+        off.tofile(f)
+        np.array([len(idx)], np.int32).tofile(f)
+        idx.tofile(f)
+    p = subprocess.run([exe, path, str(tmp_path / "lout.bin")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
+    return CR.read_driver_output(str(tmp_path / "lout.bin"), len(q), c["t"].n_dof)
+
+
+@pytest.fixture(scope="module")
+def cases(golden_dir):
+    """The Panda and the two-joint robot, both drives, 64 robots each (the fleets the stress catalogue starts from)."""
+    return S.contact_cases(golden_dir, seed=500, fleets=(("panda", 64), ("two_joint", 64)))
+
+
+@pytest.fixture(scope="module")
+def tree_case(tmp_path_factory):
+    """One random tree with save slots (the N = 9 instantiation with SLOTS > 0 and padded dofs), acceleration drive."""
+    for name, t, inert, caps, q, qd, qdd, spheres in S.tree_fleets(tmp_path_factory.mktemp("trees")):
+        if int(t.depth_first_schedule()[3]) >= 1:
+            drive, u, lim = S.fleet_inputs(t, inert, S.H.GRAVITY, q, qd, qdd)[0]
+            return dict(name=name, t=t, inert=inert, g=S.H.GRAVITY, caps=caps, spheres=spheres, q=q, qd=qd, u=u, drive=drive,
+                        lim=lim, limits=JR.table_limits(t))
+    raise AssertionError("no tree with a save slot")
+
+
+N_SUBSETS = 6
+
+
+def subset_lists(rng, c, factor=3):
+    """(pool, lists per robot, the distinct lists): the case's table embedded in a pool of about factor x K records; robot r
+    lists subset r % N_SUBSETS -- ascending random subsets of the pool, the first of them every record of the table."""
+    K = len(c["spheres"])
+    pool, pos = embed(rng, c["spheres"], factor * K + 5)
+    subsets = [pos]
+    for _ in range(N_SUBSETS - 1):
+        part = pos[rng.uniform(size=K) < 0.6]
+        extra = rng.choice(np.setdiff1d(np.arange(len(pool)), pos), int(rng.integers(0, K)), replace=False)
+        subsets.append(np.sort(np.concatenate([part, extra])))
+    return pool, [subsets[r % N_SUBSETS] for r in range(len(c["q"]))], subsets
+
+
+# ---- 1: identity and compaction ------------------------------------------------------------------------------------------------
+
+def test_ascending_lists_equal_the_shared_call_on_the_compacted_table_bit_for_bit(driver, lists_driver, cases, tree_case, tmp_path):
+    rng = np.random.default_rng(1300)
+    contacts = 0
+    for c in cases + [tree_case]:
+        for substeps in (1, 3):
+            pool, lists, subsets = subset_lists(rng, c)
+            assert all((np.diff(l) > 0).all() for l in subsets) and 2.5 * len(c["spheres"]) <= len(pool)
+            d = run_lists(lists_driver, tmp_path, c, pool, *csr(lists), substeps=substeps)
+            for k, lst in enumerate(subsets):
+                rows = np.arange(k, len(c["q"]), N_SUBSETS)
+                want = S.run_driver(driver, tmp_path, c, substeps=substeps, spheres=pool[lst])
+                same_rows(d, want, rows, rows, (c["name"], k))
+                assert np.array_equal(d["pair"][rows], map_pairs(want["pair"][rows], lst, len(pool))), (c["name"], k)
+                contacts += int((want["pair"][rows] >= 0).sum())
+    assert contacts >= 500
+
+
+# ---- 2: empty lists -------------------------------------------------------------------------------------------------------------
+
+def test_empty_lists_are_the_stops_step_bit_for_bit(stops_driver, lists_driver, cases, tmp_path):
+    import test_joint_stops_host as SH
+    for c in cases:
+        B = len(c["q"])
+        for substeps in (1, 3):
+            s = SH.run_driver(stops_driver, tmp_path, c["t"], c["inert"], c["q"], c["qd"], c["u"], c["drive"], c["lim"], c["limits"],
+                              substeps, c["g"])
+            for pool in (c["spheres"], np.zeros((0, 4), np.float32)):
+                d = run_lists(lists_driver, tmp_path, c, pool, np.zeros(B + 1, np.int32), np.zeros(0, np.int32), substeps=substeps)
+                for k in ("q", "qd", "qdd", "tau", "stop"):
+                    assert S._bits_equal(d[k], s[k]), (c["name"], k)
+                assert (d["status"] == s["status"]).all() and (d["contact"] == 0).all() and (d["lam"] == 0).all() and (d["pair"] == -1).all()
+        # and beside robots that list the whole table
+        lists = [np.arange(len(c["spheres"])) if r % 2 else np.zeros(0, np.int64) for r in range(B)]
+        d = run_lists(lists_driver, tmp_path, c, c["spheres"], *csr(lists))
+        s = SH.run_driver(stops_driver, tmp_path, c["t"], c["inert"], c["q"], c["qd"], c["u"], c["drive"], c["lim"], c["limits"], 1, c["g"])
+        for k in ("q", "qd", "qdd", "tau", "stop"):
+            assert S._bits_equal(d[k][0::2], s[k][0::2]), (c["name"], k)
+        assert (d["status"][0::2] == s["status"][0::2]).all() and (d["pair"][0::2] == -1).all() and (d["lam"][0::2] == 0).all()
+        assert (d["pair"][1::2] >= 0).any()
+
+
+# ---- 3: unsorted and repeated ---------------------------------------------------------------------------------------------------
+
+N_ORDERS = 4
+
+
+def shuffled_groups(rng, c, pool, pos):
+    """[(rows, list, the contacts_scene group of those robots on spheres[list])]: N_ORDERS shuffles of the table's positions and a
+    few filler entries, one entry of each repeated; robot r has shuffle r % N_ORDERS."""
+    out = []
+    K = len(c["spheres"])
+    for k in range(N_ORDERS):
+        lst = np.concatenate([pos, rng.choice(np.setdiff1d(np.arange(len(pool)), pos), 3, replace=False)])
+        lst = np.concatenate([lst, [pos[int(rng.integers(K))]]])            # (the repeat: a record of the case's table)
+        lst = lst[rng.permutation(len(lst))]
+        rows = np.arange(k, len(c["q"]), N_ORDERS)
+        out.append((rows, lst, CS._group(c, "lists", f"order{k}", c["q"][rows], c["qd"][rows], c["u"][rows], pool[lst], c["limits"], c["lim"])))
+    return out
+
+
+def check_against_reference(g, got, lst, K_pool, what):
+    """The candidate pair set, the hard invariants on every robot and the bounds on the kept ones, of a group on spheres[lst].
+    Returns how many robots were kept."""
+    ref_pairs = map_pairs(g["ref"]["pair"], lst, K_pool)
+    assert np.array_equal(np.sort(got["pair"], 1), np.sort(ref_pairs, 1)), what
+    local = dict(got, pair=unmap_pairs(got["pair"], lst, K_pool))
+    CS.hard_invariants(g, local, what)
+    keep = CS.kept(g)
+    CS.check_kept(g, local, keep, what)
+    return int(keep.sum())
+
+
+def test_unsorted_lists_with_a_repeat_against_the_reference(lists_driver, cases, tmp_path):
+    rng = np.random.default_rng(1301)
+    kept = 0
+    for c in cases:
+        pool, pos = embed(rng, c["spheres"], 3 * len(c["spheres"]))
+        groups = shuffled_groups(rng, c, pool, pos)
+        lists = [groups[r % N_ORDERS][1] for r in range(len(c["q"]))]
+        d = run_lists(lists_driver, tmp_path, c, pool, *csr(lists))
+        for k, (rows, lst, g) in enumerate(groups):
+            assert (np.diff(lst) < 0).any() and len(set(lst.tolist())) == len(lst) - 1
+            kept += check_against_reference(g, {key: v[rows] for key, v in d.items()}, lst, len(pool), (c["name"], k))
+    print("kept", kept)
+    assert kept >= 150
+
+
+# ---- 4, 5: invalid lists and non-finite records ------------------------------------------------------------------------------
+
+BAD = 3
+
+
+def invalid_inputs(K, m):
+    """{label: (csr_offset, csr_index)} for 8 robots that all list 0 .. m - 1 of a pool of K records, robot BAD's list broken."""
+    base = np.arange(m, dtype=np.int64)
+    out = {}
+    for label, entry in (("entry K", K), ("entry -1", -1), ("entry INT32_MIN", INT32_MIN)):
+        lists = [base.copy() for _ in range(8)]
+        lists[BAD][m // 2] = entry
+        out[label] = csr(lists)
+    lists = [base.copy() for _ in range(8)]
+    lists[BAD] = np.arange(MAX_LIST + 1) % m
+    out["length 257"] = csr(lists)
+    off = m * np.arange(9)
+    off[BAD + 1:] -= 2 * m        # 0, m, 2m, 3m, 2m, 3m, ...: robot BAD's length is -m, every other robot still reads 0 .. m - 1
+    assert off[BAD + 1] - off[BAD] == -m
+    out["negative length"] = (off.astype(np.int32), np.tile(base, 8).astype(np.int32))
+    off = m * np.arange(9)
+    off[BAD] = -m      # 0, m, 2m, -m, 4m, ...: robot BAD starts at -m, its length 5m <= 256 is fine; robot BAD - 1's length is negative
+    assert 5 * m <= MAX_LIST
+    out["negative start"] = (off.astype(np.int32), np.tile(base, 8).astype(np.int32))
+    return out
+
+
+INVALID_ROBOTS = {"negative start": [BAD - 1, BAD]}      # (a CSR start belongs to two robots); every other input: [BAD]
+
+
+def test_invalid_lists_are_refused_per_robot_and_read_nothing(lists_driver, lists_driver_san, cases, tmp_path):
+    for c in (S._panda(cases), S._two(cases)):
+        K = m = len(c["spheres"])
+        rows = slice(0, 8)
+        good = run_lists(lists_driver, tmp_path, c, c["spheres"], *csr([np.arange(m)] * 8), rows=rows)
+        assert (good["pair"] >= 0).any() and np.isfinite(good["qd"]).all()
+        for label, (off, idx) in invalid_inputs(K, m).items():
+            bad = INVALID_ROBOTS.get(label, [BAD])
+            others = ~np.isin(np.arange(8), bad)
+            for exe in (lists_driver, lists_driver_san):
+                d = run_lists(exe, tmp_path, c, c["spheres"], off, idx, rows=rows)
+                all_nan(d, bad, label)
+                assert (d["status"][bad] == LIST_INVALID).all(), (label, d["status"][bad])
+                same_rows(d, good, others, others, label)
+                assert np.array_equal(d["pair"][others], good["pair"][others]), label
+        # a pool of no records: every entry is out of range, an empty list is valid
+        off, idx = csr([np.zeros(0, np.int64)] * 4 + [np.array([0])] + [np.zeros(0, np.int64)] * 3)
+        for exe in (lists_driver, lists_driver_san):
+            d = run_lists(exe, tmp_path, c, np.zeros((0, 4), np.float32), off, idx, rows=rows)
+            all_nan(d, [4], "K = 0")
+            assert d["status"][4] == LIST_INVALID and np.isfinite(d["qd"][np.arange(8) != 4]).all()
+
+
+def test_a_non_finite_record_poisons_only_the_robots_that_list_it(lists_driver, cases, tmp_path):
+    for c in (S._panda(cases), S._two(cases)):
+        K = len(c["spheres"])
+        pool = np.concatenate([c["spheres"], filler(2)])
+        rows = slice(0, 8)
+        lists = [np.arange(K) for _ in range(8)]
+        lists[BAD] = np.arange(K + 1)                    # (the only robot that lists record K)
+        good = run_lists(lists_driver, tmp_path, c, pool, *csr(lists), rows=rows)
+        others = np.arange(8) != BAD
+        for bad_value, field in ((np.nan, 1), (np.inf, 3), (-np.inf, 0)):
+            broken = pool.copy()
+            broken[K, field] = bad_value
+            broken[K + 1, 2] = np.nan                    # (and a record nobody lists)
+            d = run_lists(lists_driver, tmp_path, c, broken, *csr(lists), rows=rows)
+            all_nan(d, [BAD], "non-finite record")
+            same_rows(d, good, others, others, "non-finite record")
+            assert np.array_equal(d["pair"][others], good["pair"][others])
+
+
+# ---- 6: overflow ---------------------------------------------------------------------------------------------------------------
+
+def test_overflow_keeps_what_the_compacted_table_keeps(driver, lists_driver, cases, tmp_path):
+    c = S._panda(cases)
+    r = int(np.nonzero(c["ref"]["n_contact"] >= 1)[0][0])
+    base = c["spheres"][int(c["ref"]["pair"][r, 0]) % len(c["spheres"])]
+    table = np.tile(base, (12, 1)).astype(np.float32)
+    table[:, 3] = base[3] - 0.001 * np.arange(12)          # twelve gaps 1 mm apart, all within d_act
+    table[5, 3] = table[4, 3]                              # and one tie
+    pool, pos = embed(np.random.default_rng(1302), table, 40)
+    sel = slice(r, r + 1)
+    want = S.run_driver(driver, tmp_path, c, spheres=table, q=c["q"][sel], qd=c["qd"][sel], u=c["u"][sel])
+    d = run_lists(lists_driver, tmp_path, c, pool, *csr([pos]), rows=sel)
+    assert want["status"][0] & CR.OVERFLOW and (want["pair"] >= 0).all()
+    same_rows(d, want, [0], [0], "overflow")
+    assert np.array_equal(d["pair"], map_pairs(want["pair"], pos, len(pool)))
+    ref = CR.substep(c["t"], c["inert"], c["caps"], table, D_ACT, c["q"][sel], c["qd"][sel], c["u"][sel], c["drive"], DT, c["lim"], c["limits"], c["g"])
+    assert sorted(d["pair"][0]) == sorted(map_pairs(ref["pair"], pos, len(pool))[0])
+
+
+# ---- the interface ---------------------------------------------------------------------------------------------------------------
+
+def test_symbol_declared_and_bound_with_its_constants(hip_lib):
+    import ctypes as C
+    lib = C.CDLL(hip_lib)
+    hdr = open(os.path.join(ROOT, "include", "rmp2.h")).read()
+    assert re.search(r"\bint rmp2_dynamics_step_contacts_lists\(", hdr) and hasattr(lib, "rmp2_dynamics_step_contacts_lists")
+    assert "#define RMP2_MAX_CONTACT_LIST 256" in hdr and "#define RMP2_MAX_CONTACT_POOL (1 << 24)" in hdr
+    assert "#define RMP2_CONTACT_LIST_INVALID 16u" in hdr
+    assert re.search(r"#define RMP2_ABI_VERSION (\d+)", hdr).group(1) == "5"
+    from riemannian_motion_policies_amd import engine as E
+    assert E.MAX_CONTACT_LIST == MAX_LIST and E.CONTACT_LIST_INVALID == LIST_INVALID
