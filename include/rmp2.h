@@ -458,7 +458,8 @@ int rmp2_closest_points_links(rmp2_handle *h, const float *q, const rmp2_obstacl
  *                     dist = distance (data_management.py:33-53), as rmp2_device.h link_pair_fields forms them for a table.
  * p_link, p_obs device [R][S][3]; dist device [R][S] (required when an attached-point leaf has self pairs, else may be NULL).
  * Intersecting capsule axes take the fixed normal +z (finite).  Feeding the arrays to an EXPLICIT_PAIRS step reproduces what
- * rmp2_step does with self collision on and no obstacle table.
+ * rmp2_step does with self collision on and no obstacle table.  A NaN or an infinity in one robot's q stays in that robot's rows:
+ * every other robot's rows keep their bits (the staged step answers such a robot with a non-finite qdd and RMP2_STATUS_NONFINITE).
  *
  * rmp2_step on a handle with self collision: the stage, then the explicit-pair step (two launches).  Obstacle input NONE, or
  * SHARED_SPHERES with sphere or capsule records (with or without link_capsules) on sets without attached-point leaves: leaf l's

@@ -1,13 +1,19 @@
 """Self collision on the GPU: the self-pair stage against a float64 numpy restatement, the staged step against the CPU oracle,
 its composition with the obstacle stage (bit for bit), and the refusals.
 
-Checker: oracle.forward_kinematics in fp64 plus segment-segment closest points (below), and oracle.step on explicit pairs.
+Checker: oracle.forward_kinematics in fp64 plus segment-segment closest points (tests/self_pair_reference.py), and oracle.step on
+explicit pairs.
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from self_pair_reference import _seg_seg, _world_segments, self_pairs_np  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -43,67 +49,6 @@ def _setup(config, solve="auto"):
     pairs = U.self_collision_pairs(table, leaf_frames)
     caps = U.self_collision_capsules(U.PANDA_URDF, table)
     return table, desc, pairs, caps
-
-
-def _world_segments(T, cap):
-    """T [R, 4, 4] (None: the base), cap [8] -> A, B [R, 3] and radius."""
-    if T is None:
-        return cap[None, 0:3].astype(np.float64), cap[None, 4:7].astype(np.float64), float(cap[3])
-    c = cap.astype(np.float64)
-    return T[:, :3, 3] + T[:, :3, :3] @ c[0:3], T[:, :3, 3] + T[:, :3, :3] @ c[4:7], float(c[3])
-
-
-def _seg_seg(p1, q1, p2, q2):
-    """Clamped closest points of segments p1-q1 and p2-q2 (rows), fp64."""
-    d1, d2, r = q1 - p1, q2 - p2, p1 - p2
-    a, e = (d1 * d1).sum(-1), (d2 * d2).sum(-1)
-    f, c, b = (d2 * r).sum(-1), (d1 * r).sum(-1), (d1 * d2).sum(-1)
-    a, e = np.broadcast_to(a, f.shape), np.broadcast_to(e, f.shape)
-    with np.errstate(all="ignore"):
-        denom = a * e - b * b
-        s = np.where(denom > 0, np.clip((b * f - c * e) / np.where(denom > 0, denom, 1), 0, 1), 0.0)
-        t = np.where(e > 0, (b * s + f) / np.where(e > 0, e, 1), 0.0)
-        s = np.where(t < 0, np.clip(-c / np.where(a > 0, a, 1), 0, 1), np.where(t > 1, np.clip((b - c) / np.where(a > 0, a, 1), 0, 1), s))
-        t = np.clip(t, 0, 1)
-        s = np.where(a > 0, s, 0.0)
-        s = np.where((e > 0) | (a <= 0), s, np.clip(-c / np.where(a > 0, a, 1), 0, 1))
-    return p1 + s[:, None] * d1, p2 + t[:, None] * d2
-
-
-def self_pairs_np(desc, pairs, caps, q):
-    """(p_link, p_obs, dist, gap) [R, S, 3], [R, S, 3], [R, S], [R, S] in fp64: the layout of rmp2_self_pairs (leaf ordinal
-    order; the pairs of a leaf in the order given).  gap = signed surface distance."""
-    import oracle as O
-    from riemannian_motion_policies_amd import descriptor as D
-    dl = D.distance_leaf_indices(desc)
-    T = O.forward_kinematics(desc, q, "f64")
-    F = desc.robot.n_frames
-    order = sorted(range(len(pairs)), key=lambda k: pairs[k][0])
-    R, S = q.shape[0], len(pairs)
-    pl, po = np.empty((R, S, 3)), np.empty((R, S, 3))
-    dist, gap = np.empty((R, S)), np.empty((R, S))
-    for j, k in enumerate(order):
-        o, b = pairs[k]
-        leaf = desc.leaves[dl[o]]
-        fa = leaf.frame
-        A, B, ra = _world_segments(T[:, fa], caps[fa])
-        C_, D_, rb = _world_segments(None if b < 0 else T[:, b], caps[F if b < 0 else b])
-        C_, D_ = np.broadcast_to(C_, A.shape), np.broadcast_to(D_, A.shape)
-        X, Y = _seg_seg(A, B, C_, D_)
-        n = X - Y
-        nn = np.linalg.norm(n, axis=-1, keepdims=True)
-        u = np.where(nn == 0, np.array([0.0, 0.0, 1.0]), n / np.where(nn == 0, 1.0, nn))
-        g = nn[:, 0] - ra - rb
-        p_link, p_obs = X - ra * u, Y + rb * u
-        gap[:, j] = g
-        dist[:, j] = np.abs(g)
-        if leaf.taskmap == D.TASKMAP_FK_POINT:
-            Tf = T[:, fa]
-            pl[:, j] = np.einsum("rji,rj->ri", Tf[:, :3, :3], p_link - Tf[:, :3, 3])
-            po[:, j] = np.sign(g)[:, None] * u
-        else:
-            pl[:, j], po[:, j] = p_link, p_obs
-    return pl, po, dist, gap
 
 
 @pytest.mark.parametrize("config", ["config3", "exp05_panda"])
