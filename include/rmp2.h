@@ -548,8 +548,10 @@ int rmp2_closest_points_hulls(rmp2_handle *h, const float *q, const rmp2_obstacl
  *     negated face normals of B, s(n) = min_{y in B} n . y - max_{x in A} n . x (the plane offset d for the hull's own faces);
  *     n* = argmax s (A's faces first, the first maximum), y* the vertex of B attaining the min; p_obs = y*, p_link = y* - s n*,
  *     g = s < 0, u = -n*.  Edge-edge axes are not weighed: conservative against PyBullet's EPA, and unpinned (no reference depths).
+ *     Where n* is a face of B, every vertex of that face attains the min: y* is one of them, which one is left to rounding.
  *   Either way p_link - p_obs = g u.  FK_DISTANCE leaves: both points in the base frame.  FK_POINT leaves: p_link =
- *   relative_position (h_A in the joint frame), p_obs = normal_vec = sign(g) u (base frame), dist = |g|.
+ *   relative_position (h_A in the joint frame), p_obs = normal_vec = sign(g) u (base frame), dist = |g|.  u is found in A's frame
+ *   and turned into the base frame by R_A: normal_vec is in base coordinates however far A's frame has turned.
  *   Bounded: at most 64 GJK steps per pair (fp64; the best simplex is kept), one pass over each hull's planes for the face rule.
  *   Non-finite inputs: a NaN or an infinity in a robot's q makes p_link, p_obs and dist of EVERY self pair (and every obstacle
  *   pair: rmp2_closest_points_hulls' contract) of that robot NaN, whichever frames the pair names, and leaves the other robots'
@@ -557,7 +559,9 @@ int rmp2_closest_points_hulls(rmp2_handle *h, const float *q, const rmp2_obstacl
  * rmp2_self_pairs on such a handle gives the hull pairs (layout of rmp2_set_self_collision).  rmp2_step with obstacle input NONE
  * or a SHARED_SPHERES sphere / capsule table: each pair leaf's range is [K obstacle pairs | S_l self pairs], the obstacle pairs
  * formed on the same leaf hulls, bit-identical to rmp2_closest_points_hulls on a handle whose link hulls are those hulls; then
- * the explicit-pair step.  Buffer, growth and capture refusals as rmp2_set_self_collision's staged step.  RMP2_ERR_UNSUPPORTED,
+ * the explicit-pair step.  A pair leaf without self pairs (S_l == 0) keeps its K obstacle pairs alone.  Two pair leaves on one
+ * frame are two leaves: each has its own self pairs and its own K obstacle pairs on that frame's hull, and equal (frame, B) pairs
+ * give equal rows.  Buffer, growth and capture refusals as rmp2_set_self_collision's staged step.  RMP2_ERR_UNSUPPORTED,
  * naming the combination: rmp2_rollout, rmp2_step_pair, rmp2_exchange_step, RAGGED_SPHERES lists, CYLINDER tables,
  * caller-supplied EXPLICIT_PAIRS, link_capsules given, a table on a set with attached-point leaves. */
 int rmp2_set_self_collision_hulls(rmp2_handle *h, int32_t n_pairs, const int32_t *pairs, int32_t n_hulls, const int32_t *vert_offset,

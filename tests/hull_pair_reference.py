@@ -127,13 +127,16 @@ def face_margin(A: Hull, B: Hull, Rm, t):
     return s[-1] - s[-2]
 
 
-def self_hull_pairs_np(desc, hulls, pairs, q):
+def self_hull_pairs_np(desc, hulls, pairs, q, T=None):
     """(p_link, p_obs, dist, gap, face) [R, S, 3], [R, S, 3], [R, S], [R, S], [R, S] in fp64 in rmp2_self_pairs' layout for
     self pairs [(leaf ordinal, frame B or -1)] on `hulls` (urdf.self_collision_hulls).  Distance leaves: the two points in the
-    base frame; attached-point leaves: relative_position (frame), normal_vec = sign(gap) u (base), distance |gap|."""
+    base frame; attached-point leaves: relative_position (frame), normal_vec = sign(gap) u (base), distance |gap|.  T: the
+    frames [R, F, 4, 4] to place the hulls by (default: the oracle's fp64 frames; its fp32 frames give the fp32 walk's share)."""
     import oracle as O
     from riemannian_motion_policies_amd import descriptor as D
-    T = O.forward_kinematics(desc, np.asarray(q, np.float32), "f64")
+    if T is None:
+        T = O.forward_kinematics(desc, np.asarray(q, np.float32), "f64")
+    T = np.asarray(T, np.float64)
     dl = D.distance_leaf_indices(desc)
     F = desc.robot.n_frames
     cache = {}
