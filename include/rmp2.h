@@ -757,6 +757,44 @@ int rmp2_dynamics_step_contacts_lists(rmp2_handle *h, float *q, float *qd, const
                                       int32_t substeps, float *qdd_out, float *tau_out, float *stop_out, float *contact_out,
                                       float *contact_lambda, int32_t *contact_pair, uint32_t *status_out, int32_t R, void *stream);
 
+/* ---- half-space obstacles (floor, walls) beside the spheres -------------------------------------------------------------------
+ * rmp2_dynamics_step_contacts_planes is rmp2_dynamics_step_contacts (csr_offset == csr_index == NULL: spheres is the shared
+ * table, K <= RMP2_MAX_CONTACT_SPHERES) or rmp2_dynamics_step_contacts_lists (both given: spheres is the pool) with a table of
+ * half-spaces shared by the fleet: planes, device [P][4] fp32 = (nx, ny, nz, d), 16-byte aligned, 0 <= P <=
+ * RMP2_MAX_CONTACT_PLANES; free space is {x : n . x >= d}.  A unit normal is the caller's contract: the record is used as given.
+ * For each frame f with a capsule (world end points X_0 = A, X_1 = A + D, radius r_f), each plane p and each end e in {0, 1}:
+ *     gap g = n . X_e - d - r_f;   J[j] = n . (z_j x (X_e - o_j)) (revolute ancestor dof j), n . z_j (prismatic), 0 otherwise;
+ *     bound b = -max(g, 0) / dt   (a penetrating end is not pushed out; it cannot go deeper).
+ * Two rows per capsule and plane, so that a link lying flat on a plane is held at both ends; a capsule of zero length (D == 0
+ * exactly) gives the row e = 0 only.  Plane rows and sphere rows compete for the same RMP2_MAX_CONTACTS slots by the same rule
+ * (g <= d_act, smallest gap first, ties to the lower pair index, the excess reported as RMP2_CONTACT_OVERFLOW).  The PAIR INDEX
+ * of a plane row is F K + 2 (f P + p) + e, F the robot's frame count and K the sphere count (the pool's size in the list form):
+ * sphere pairs keep f K + k and sort before plane pairs on ties; the RMP2_CONTACT_PAIR_* macros take a value apart.  Solver, status
+ * flags, outputs, landing and clamps are those of the two calls above.
+ * P == 0 is the sphere call;  K == 0 with P > 0 a planes-only step;  K == 0 and P == 0 the stops' step.  A non-finite plane
+ * value makes every robot's outputs NaN (contact_pair -1), as a non-finite record of the shared sphere table does.
+ * Stream-ordered, no allocation, no read-back: capturable.  Refusals: those of the call it extends, and P < 0, P >
+ * RMP2_MAX_CONTACT_PLANES, a null or misaligned plane table with P > 0, one of csr_offset / csr_index without the other:
+ * RMP2_ERR_INVALID_ARGUMENT; a robot of more than 9 dofs: RMP2_ERR_UNSUPPORTED. */
+#define RMP2_MAX_CONTACT_PLANES 8
+#define RMP2_CONTACT_KIND_SPHERE 0
+#define RMP2_CONTACT_KIND_PLANE 1
+/* contact_pair (>= 0) -> kind, frame, record, end.  F: the robot's frame count; K, P: the call's sphere and plane counts.  record is
+ * the sphere's index (table or pool) or the plane's; end is the capsule's end point, 0 for a sphere. */
+#define RMP2_CONTACT_PAIR_KIND(pair, F, K) ((int64_t)(pair) >= (int64_t)(F) * (K) ? RMP2_CONTACT_KIND_PLANE : RMP2_CONTACT_KIND_SPHERE)
+#define RMP2_CONTACT_PAIR_PLANE_ROW(pair, F, K) ((int32_t)((int64_t)(pair) - (int64_t)(F) * (K))) /* 2 (f P + p) + e of a plane pair */
+#define RMP2_CONTACT_PAIR_FRAME(pair, F, K, P) \
+  (RMP2_CONTACT_PAIR_KIND(pair, F, K) ? (RMP2_CONTACT_PAIR_PLANE_ROW(pair, F, K) >> 1) / (P) : (pair) / (K))
+#define RMP2_CONTACT_PAIR_RECORD(pair, F, K, P) \
+  (RMP2_CONTACT_PAIR_KIND(pair, F, K) ? (RMP2_CONTACT_PAIR_PLANE_ROW(pair, F, K) >> 1) % (P) : (pair) % (K))
+#define RMP2_CONTACT_PAIR_END(pair, F, K) (RMP2_CONTACT_PAIR_KIND(pair, F, K) ? RMP2_CONTACT_PAIR_PLANE_ROW(pair, F, K) & 1 : 0)
+int rmp2_dynamics_step_contacts_planes(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
+                                       const float *q_lower, const float *q_upper, const float *spheres, int32_t K,
+                                       const int32_t *csr_offset, const int32_t *csr_index, const float *planes, int32_t P,
+                                       float d_act, float dt, int32_t substeps, float *qdd_out, float *tau_out, float *stop_out,
+                                       float *contact_out, float *contact_lambda, int32_t *contact_pair, uint32_t *status_out,
+                                       int32_t R, void *stream);
+
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,
  * plain steps on shared or ragged sphere tables, both fleets beyond 8 192 robots -- the two steps are ONE grid (the first

@@ -164,13 +164,57 @@ __host__ __device__ inline int contact_list_span(const int32_t* csr_offset, int 
   return b < 0 || e < b ? -1 : e - b;
 }
 
+// Half-space obstacles beside the spheres (rmp2_dynamics_step_contacts_planes).  The routines below take the planes as a defaulted
+// template parameter: with NoPlanes (every instantiation that existed before the planes) each `if constexpr (Pl::kOn)` is
+// discarded and the code is what it was.  PlaneTable: the fleet's records [P][4] = (n, d), free space n . x >= d, read at uniform
+// addresses like the shared sphere table; F, the robot's frame count, places the plane rows' pair indices after the spheres':
+// F K + 2 (f P + p) + e.
+struct NoPlanes {
+  static constexpr bool kOn = false;
+};
+struct PlaneTable {
+  const float* planes;
+  int P, F;
+  static constexpr bool kOn = true;
+};
+
+// The slot of a qualifying candidate (gap g, pair index idx) among the kept ones: a free slot, or the kept candidate of largest
+// (gap, index) when the new one is smaller, or -1.  The rule of the sphere trip below, which keeps its own inline statement of it
+// (its code is not to change); the plane trip calls this.
+__host__ __device__ inline int contact_slot(float g, int idx, int& count, float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts]) {
+  int put = -1;
+  if (count < kMaxContacts) {
+    put = count++;
+  } else {
+    float wg = cgap[0];
+    int wi = cidx[0], ws = 0;
+#pragma unroll
+    for (int e = 1; e < kMaxContacts; ++e)
+      if (cgap[e] > wg || (cgap[e] == wg && cidx[e] > wi)) {
+        wg = cgap[e];
+        wi = cidx[e];
+        ws = e;
+      }
+    if (g < wg || (g == wg && idx < wi)) put = ws;
+  }
+  if (put < 0) return put;
+#pragma unroll
+  for (int e = 0; e < kMaxContacts; ++e)
+    if (e == put) {
+      cgap[e] = g;
+      cidx[e] = idx;
+    }
+  return put;
+}
+
 // The candidate search and the rows of one robot at q.  caps: [n_frames][8] (a, radius, b, 0) in frame coordinates, read at
 // uniform addresses; src: the robot's spheres (above).  Jr: the rows' storage.  cgap / cidx: gap and pair index per slot (cidx
 // -1: empty).  Returns the number of candidates kept; excess: how many more qualified.
-template <int N, int SLOTS, class Src>
+template <int N, int SLOTS, class Src, class Pl = NoPlanes>
 __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_ops, const float* caps, Src src,
                                                        float d_act, const float (&q)[N], float* Jr, int stride,
-                                                       float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess) {
+                                                       float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess,
+                                                       Pl pl = Pl{}) {
   const int K = src.count();   // the robot's records (the pair index is made of src.pool())
   float ax[N][3], org[N][3];
 #pragma unroll
@@ -214,7 +258,11 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     const float* cp = caps + (size_t)op.frame * 8;
     bool has = false;
     for (int i = 0; i < 8; ++i) has = has || cp[i] != 0.f;
-    if (!has || K <= 0) continue;
+    if constexpr (Pl::kOn) {   // (a frame without spheres still meets the planes)
+      if (!has) continue;
+    } else {
+      if (!has || K <= 0) continue;
+    }
     const float al[3] = {cp[0], cp[1], cp[2]}, dl[3] = {cp[4] - cp[0], cp[5] - cp[1], cp[6] - cp[2]};
     const float rf = cp[3];
     float A[3], D[3];
@@ -225,6 +273,40 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     const float dd = id_dot(D, D);
     const float inv_dd = dd > 0.f ? 1.f / dd : 0.f;
     const uint32_t mask = op.anc_mask;
+    if constexpr (Pl::kOn) {
+      // the planes: one row per end of the segment (a zero-length capsule: the end 0 only), the normal the plane's as given
+      const int ends = (D[0] == 0.f && D[1] == 0.f && D[2] == 0.f) ? 1 : 2;
+      for (int p = 0; p < pl.P; ++p) {
+        const float nu[3] = {pl.planes[4 * p + 0], pl.planes[4 * p + 1], pl.planes[4 * p + 2]};
+        const float pd = pl.planes[4 * p + 3];
+        for (int e = 0; e < ends; ++e) {
+          float X[3];
+          for (int i = 0; i < 3; ++i) X[i] = e ? A[i] + D[i] : A[i];
+          const float g = id_dot(nu, X) - pd - rf;
+          if (!(g <= d_act)) continue;   // (also a NaN gap)
+          ++total;
+          const int idx = pl.F * src.pool() + 2 * (op.frame * pl.P + p) + e;
+          const int put = contact_slot(g, idx, count, cgap, cidx);
+          if (put < 0) continue;
+          float* row = Jr + (size_t)put * N * stride;
+#pragma unroll
+          for (int j = 0; j < N; ++j) {
+            float val = 0.f;
+            if ((mask >> j) & 1u) {
+              if ((revolute >> j) & 1u) {
+                const float d[3] = {X[0] - org[j][0], X[1] - org[j][1], X[2] - org[j][2]};
+                float zx[3];
+                id_cross(ax[j], d, zx);
+                val = id_dot(nu, zx);
+              } else {
+                val = id_dot(nu, ax[j]);
+              }
+            }
+            row[j * stride] = val;
+          }
+        }
+      }
+    }
     SphereList::Cursor cursor;
     if constexpr (Src::kList) cursor.begin(src);
     for (int s = 0; s < K; ++s) {
@@ -547,7 +629,7 @@ __host__ __device__ inline auto contact_source(const float* spheres, int K, cons
 // / pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats.  The spheres are scanned
 // once, before the substeps: a non-finite record makes the robot NaN, an invalid list NaN with the status word
 // RMP2_CONTACT_LIST_INVALID alone (its substeps run on no spheres, and nothing is read through its entries).
-template <int N, int SLOTS, bool LIST = false>
+template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes>
 __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, int n_ops, int n_dof, const float* inert,
                                                              const float base_acc[3], float* q_io, float* qd_io,
                                                              const float* u_in, bool accel, const float* lim, const float* qlo,
@@ -555,7 +637,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
                                                              float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
                                                              float* stop_out, float* contact_out, float* lambda_out,
                                                              int32_t* pair_out, uint32_t* status_out, float* lds, int stride,
-                                                             const int32_t* list = nullptr, int list_len = 0) {
+                                                             const int32_t* list = nullptr, int list_len = 0, Pl pl = Pl{}) {
   auto src = contact_source<LIST>(spheres, K, list, list_len);
   float* Ms = lds;
   float* Jr = Ms + (size_t)fd_tri(N) * stride;
@@ -579,6 +661,9 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
   } else {
     for (int s = 0; s < 4 * src.K; ++s) table_poison += src.spheres[s] * 0.f;
   }
+  if constexpr (Pl::kOn) {   // a non-finite plane value: every robot NaN
+    for (int s = 0; s < 4 * pl.P; ++s) table_poison += pl.planes[s] * 0.f;
+  }
   uint32_t status = 0u;
   int most = 0;
   for (int s = 0; s < substeps; ++s) {
@@ -601,7 +686,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
       cont[j] = 0.f;
     }
     int excess = 0;
-    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess);
+    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess, pl);
     if (excess > 0) status |= RMP2_CONTACT_OVERFLOW;
 #pragma unroll
     for (int c = 0; c < kMaxContacts; ++c) lamc[c] = 0.f;

@@ -2443,6 +2443,20 @@ void launch_dynamics_step_contacts_lists(const rmp2_handle* h, float* q, float* 
                                          const int32_t* csr_index, float d_act, float dt, int substeps, float* qdd_out,
                                          float* tau_out, float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out,
                                          uint32_t* status_out, int R, hipStream_t s);
+// rmp2_dynamics_step_contacts_planes: half-space obstacles beside the spheres, over the shared table or over per-robot lists.  Its
+// kernels and their launchers are rmp2_contact_planes_tu.hip, compiled once per form.
+void launch_dynamics_step_contacts_planes_table(const rmp2_handle* h, float* q, float* qd, const float* u, int accel,
+                                                const float* lim, const float* qlo, const float* qhi, const float* spheres, int K,
+                                                const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int P,
+                                                float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
+                                                float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out,
+                                                uint32_t* status_out, int R, hipStream_t s);
+void launch_dynamics_step_contacts_planes_lists(const rmp2_handle* h, float* q, float* qd, const float* u, int accel,
+                                                const float* lim, const float* qlo, const float* qhi, const float* spheres, int K,
+                                                const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int P,
+                                                float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
+                                                float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out,
+                                                uint32_t* status_out, int R, hipStream_t s);
 }
 
 // =========================================================================================
@@ -4055,6 +4069,48 @@ int rmp2_dynamics_step_contacts_lists(rmp2_handle* h, float* q, float* qd, const
   launch_dynamics_step_contacts_lists(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index, d_act, dt,
                                       substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R,
                                       s);   // (N in {2, 9} by the handle's template size, SLOTS by its program)
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
+}
+
+int rmp2_dynamics_step_contacts_planes(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
+                                       const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
+                                       const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
+                                       float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out, float* stop_out,
+                                       float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
+                                       int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  const char* what = "dynamics step with contact planes";
+  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
+  if ((csr_offset != nullptr) != (csr_index != nullptr))
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": csr_offset and csr_index go together (both null: the shared table)");
+  const bool lists = csr_offset != nullptr;
+  const int k_max = lists ? RMP2_MAX_CONTACT_POOL : RMP2_MAX_CONTACT_SPHERES;
+  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K < 0");
+  if (K > k_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K > " + std::to_string(k_max));
+  if (lists && K > 0 && spheres && ((uintptr_t)spheres & 15u))
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": the pool must be 16-byte aligned");
+  if (P < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": P < 0");
+  if (P > RMP2_MAX_CONTACT_PLANES)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": P > " + std::to_string(RMP2_MAX_CONTACT_PLANES));
+  if (P > 0 && !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": null plane table with P > 0");
+  if (P > 0 && ((uintptr_t)planes & 15u))
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": the plane table must be 16-byte aligned");
+  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": d_act must be finite and >= 0");
+  if (h->contact_n == 0)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
+  if (h->n_template > 9)
+    return fail(h, RMP2_ERR_UNSUPPORTED, std::string(what) + ": robots of more than 9 dofs are not supported (this one has " +
+                                             std::to_string(h->n_dof) + ")");
+  bool launch;
+  if (int rc = step_rows_check(h, what, q, qd, u, (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres), R, launch)) return rc;
+  if (!launch) return RMP2_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int accel = drive == RMP2_DRIVE_ACCEL;
+  // (N in {2, 9} by the handle's template size, SLOTS by its program)
+  (lists ? launch_dynamics_step_contacts_planes_lists : launch_dynamics_step_contacts_planes_table)(
+      h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index, planes, P, d_act, dt, substeps, qdd_out,
+      tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s);
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }

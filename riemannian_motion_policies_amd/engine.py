@@ -18,6 +18,24 @@ MAX_CONTACTS = 8   # include/rmp2.h RMP2_MAX_CONTACTS
 MAX_CONTACT_LIST = 256        # include/rmp2.h RMP2_MAX_CONTACT_LIST: entries per robot of dynamics_step(contact_lists=)
 MAX_CONTACT_POOL = 1 << 24    # include/rmp2.h RMP2_MAX_CONTACT_POOL: records in its pool
 CONTACT_LIST_INVALID = 16     # include/rmp2.h RMP2_CONTACT_LIST_INVALID: status_out of a robot whose list was refused
+MAX_CONTACT_PLANES = 8        # include/rmp2.h RMP2_MAX_CONTACT_PLANES: half-spaces of dynamics_step(contact_planes=)
+CONTACT_KIND_SPHERE, CONTACT_KIND_PLANE = 0, 1
+
+
+def contact_pair_split(pair: int, n_frames: int, K: int, P: int):
+    """(kind, frame, record, end) of a contact_pair value of dynamics_step (include/rmp2.h RMP2_CONTACT_PAIR_* macros): kind is
+    CONTACT_KIND_SPHERE (record: the sphere's index in the table or pool, end 0) or CONTACT_KIND_PLANE (record: the plane, end: 0
+    or 1, the capsule's end point).  n_frames: the robot's frame count; K, P: the call's sphere and plane counts.  None for an
+    empty slot (-1)."""
+    pair, base = int(pair), int(n_frames) * int(K)
+    if pair < 0:
+        return None
+    if pair >= base + 2 * int(n_frames) * int(P):
+        raise ValueError(f"contact pair {pair} is outside the range of {n_frames} frames, {K} spheres and {P} planes")
+    if pair < base:
+        return CONTACT_KIND_SPHERE, pair // K, pair % K, 0
+    r = pair - base
+    return CONTACT_KIND_PLANE, (r >> 1) // P, (r >> 1) % P, r & 1
 
 
 def _f32(t: torch.Tensor, device) -> torch.Tensor:
@@ -626,7 +644,7 @@ class Engine:
                       q_limits=None, stop_out: Optional[torch.Tensor] = None, status_out: Optional[torch.Tensor] = None,
                       contacts: Optional[torch.Tensor] = None, d_act: float = 0.0, contact_out: Optional[torch.Tensor] = None,
                       contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None,
-                      contact_lists=None) -> None:
+                      contact_lists=None, contact_planes: Optional[torch.Tensor] = None) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
@@ -647,7 +665,12 @@ class Engine:
         MAX_CONTACT_LIST of them) -- the arrays of obstacles(spheres=, csr_offset=, csr_index=) feed the plant unchanged
         (include/rmp2.h rmp2_dynamics_step_contacts_lists).  contact_pair_out stays frame * K + the POOL index.  The lists are
         checked on the device: a robot with an invalid list (an entry outside [0, K), more than MAX_CONTACT_LIST entries, a
-        negative length) gets NaN rows and status_out == CONTACT_LIST_INVALID; nothing is read back, the call stays capturable."""
+        negative length) gets NaN rows and status_out == CONTACT_LIST_INVALID; nothing is read back, the call stays capturable.
+        contact_planes = half-spaces [P, 4] fp32 = (unit normal, d) on the engine's device (P <= MAX_CONTACT_PLANES; free space
+        n . x >= d; urdf.contact_planes / urdf.floor build them): a floor or walls beside the spheres, with or without contacts=
+        and contact_lists= (include/rmp2.h rmp2_dynamics_step_contacts_planes; needs set_contact_capsules).  Every capsule gives
+        two rows per plane, one per end point; contact_pair_out holds n_frames * K + 2 * (frame * P + plane) + end for them
+        (contact_pair_split takes a value apart).  Without contact_planes= the call takes the routes above, unchanged."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
@@ -666,6 +689,48 @@ class Engine:
                                   or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
 
+        if contact_planes is not None:
+            _require_resident(self.device, contact_planes=contact_planes)
+            if (contact_planes.dim() != 2 or contact_planes.shape[1] != 4 or contact_planes.dtype != torch.float32
+                    or not contact_planes.is_contiguous()):
+                raise ValueError(f"contact_planes must be a contiguous fp32 [P, 4] tensor (normal, d), got {list(contact_planes.shape)}")
+            if contact_planes.shape[0] > MAX_CONTACT_PLANES:
+                raise ValueError(f"contact_planes holds {contact_planes.shape[0]} planes, at most {MAX_CONTACT_PLANES}")
+            if contacts is None and contact_lists is not None:
+                raise ValueError("contact_lists needs contacts (the pool the lists index)")
+            K = 0
+            if contacts is not None:
+                _require_resident(self.device, contacts=contacts)
+                if contacts.dim() != 2 or contacts.shape[1] != 4:
+                    raise ValueError(f"contacts must be [K, 4] spheres (centre, radius), got {list(contacts.shape)}")
+                K = int(contacts.shape[0])
+            if contact_out is not None:
+                self._dynamics_out("contact_out", contact_out, (R, self.n_dof))
+            if contact_lambda_out is not None:
+                self._dynamics_out("contact_lambda_out", contact_lambda_out, (R, MAX_CONTACTS))
+            check_int("contact_pair_out", contact_pair_out, (R, MAX_CONTACTS))
+            check_int("status_out", status_out, (R,))
+            lower, upper = (None, None) if q_limits is None else self._q_limits_device(q_limits)
+            csr_offset = csr_index = None
+            if contact_lists is not None:
+                try:
+                    csr_offset, csr_index = contact_lists
+                except (TypeError, ValueError):
+                    raise ValueError("contact_lists must be a pair (csr_offset, csr_index)") from None
+                for name, t, shape in (("csr_offset", csr_offset, (R + 1,)), ("csr_index", csr_index, None)):
+                    if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32
+                            or not t.is_contiguous() or (t.dim() != 1 if shape is None else tuple(t.shape) != shape)):
+                        raise ValueError(f"contact_lists {name} must be a contiguous int32 {'1-D' if shape is None else list(shape)} "
+                                         f"tensor on {self.device}")
+                if csr_index.numel() == 0:
+                    csr_index = self._empty_index
+            P = int(contact_planes.shape[0])
+            _native.check(self._lib.rmp2_dynamics_step_contacts_planes(
+                self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
+                contacts.data_ptr() if K else None, K, ptr(csr_offset), ptr(csr_index),
+                contact_planes.data_ptr() if P else None, P, float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out),
+                ptr(stop_out), ptr(contact_out), ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s), self._h)
+            return
         if contacts is None:
             if contact_lists is not None:
                 raise ValueError("contact_lists needs contacts (the pool the lists index)")

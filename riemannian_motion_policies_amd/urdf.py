@@ -429,6 +429,37 @@ def contact_capsules(urdf_filepath: str, table: KinematicTable, default_radius: 
     return np.ascontiguousarray(self_collision_capsules(urdf_filepath, table, default_radius=default_radius, fitted=fitted)[:table.n_frames])
 
 
+MAX_CONTACT_PLANES = 8   # include/rmp2.h RMP2_MAX_CONTACT_PLANES
+
+
+def contact_planes(rows) -> np.ndarray:
+    """Half-spaces [P, 4] float32 = (unit normal, d) for Engine.dynamics_step(contact_planes=) (include/rmp2.h
+    rmp2_dynamics_step_contacts_planes; free space is n . x >= d) from host rows (nx, ny, nz, d) whose normal may have any length:
+    normal and offset are divided by |n| in float64, so the half-space stays the one the row states.  Refused: a zero or
+    non-finite normal, a non-finite offset, more than MAX_CONTACT_PLANES rows."""
+    a = np.asarray(rows, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 4), np.float32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"contact planes must be rows (nx, ny, nz, d), got shape {list(a.shape)}")
+    if len(a) > MAX_CONTACT_PLANES:
+        raise ValueError(f"{len(a)} contact planes, at most {MAX_CONTACT_PLANES}")
+    if not np.isfinite(a).all():
+        raise ValueError("contact planes: a value is not finite")
+    length = np.linalg.norm(a[:, :3], axis=1)
+    if (length == 0).any():
+        raise ValueError(f"contact planes: row {int(np.argmax(length == 0))} has a zero normal")
+    out = (a / length[:, None]).astype(np.float32)
+    if not np.isfinite(out).all() or (np.abs(out[:, :3]).max(1) == 0).any():
+        raise ValueError("contact planes: a row does not normalise in float32")
+    return np.ascontiguousarray(out)
+
+
+def floor(z: float = 0.0) -> np.ndarray:
+    """The ground plane at height z as contact_planes' [1, 4]: the reference scenes' plane.urdf."""
+    return contact_planes([[0.0, 0.0, 1.0, float(z)]])
+
+
 # ---- convex-hull link geometry (simulation.py:462-484: PyBullet loads each .obj collision mesh as its convex hull) ------------
 
 MAX_HULL_VERTICES = 512   # include/rmp2.h RMP2_MAX_HULL_VERTICES
