@@ -90,21 +90,15 @@ def lib():
                                                C.c_int32, C.c_void_p]
     if hasattr(l, "rmp2_dynamics_step_contacts"):   # (likewise for a diagnostic RMP2_LIB built before the contacts)
         l.rmp2_set_contact_capsules.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        l.rmp2_dynamics_step_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                                  C.c_void_p]
-    if hasattr(l, "rmp2_dynamics_step_contacts_lists"):   # (likewise for a diagnostic RMP2_LIB built before the lists)
-        l.rmp2_dynamics_step_contacts_lists.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                                        C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    if hasattr(l, "rmp2_dynamics_step_contacts_planes"):   # (likewise for a diagnostic RMP2_LIB built before the planes)
-        l.rmp2_dynamics_step_contacts_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                                         C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                         C.c_int32, C.c_void_p]
+        # (handle, q, qd, u, drive, tau_limit, q_lower, q_upper, spheres, K) ... (d_act, dt, substeps, seven outputs, R, stream)
+        head = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        tail = [C.c_float, C.c_float, C.c_int32] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]
+        lists = [C.c_void_p, C.c_void_p]   # csr_offset, csr_index
+        l.rmp2_dynamics_step_contacts.argtypes = head + tail
+        if hasattr(l, "rmp2_dynamics_step_contacts_lists"):   # (likewise for a diagnostic RMP2_LIB built before the lists)
+            l.rmp2_dynamics_step_contacts_lists.argtypes = head + lists + tail
+        if hasattr(l, "rmp2_dynamics_step_contacts_planes"):   # (likewise for a diagnostic RMP2_LIB built before the planes)
+            l.rmp2_dynamics_step_contacts_planes.argtypes = head + lists + [C.c_void_p, C.c_int32] + tail
     l.rmp2_differentiate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_differentiate_euler.argtypes = l.rmp2_differentiate.argtypes

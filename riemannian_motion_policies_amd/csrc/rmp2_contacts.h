@@ -30,7 +30,15 @@
 // array): U (the packed factor of M), the candidate rows J [8][N], the columns Y [N][N], the Gram factor and the multipliers.
 // These are indexed at run time (LDS addresses are per lane); every index into a REGISTER array is a compile-time constant
 // after unrolling -- dynamic picks are unrolled compares.  Host-compilable (tests/contacts_driver.cpp).
+//
+// Forms.  The step has two orthogonal switches: LIST -- the robot's spheres are the fleet's shared table or its own list over a
+// shared pool (rmp2_dynamics_step_contacts_lists; SphereTable / SphereList below) -- and planes -- half-spaces beside the spheres
+// or none (rmp2_dynamics_step_contacts_planes; NoPlanes / PlaneTable).  All four are dynamics_step_contacts_robot<N, SLOTS, LIST,
+// Pl>, one body with the differences under `if constexpr`, behind ONE kernel, rmp2_dynamics_step_contacts_kernel<N, SLOTS, LIST,
+// PLANES> at the end of this file, which rmp2_contacts_tu.hip instantiates once per form (a code object each).
 #pragma once
+#include <type_traits>
+
 #include "rmp2_joint_stops.h"
 
 namespace rmp2 {
@@ -165,8 +173,7 @@ __host__ __device__ inline int contact_list_span(const int32_t* csr_offset, int 
 }
 
 // Half-space obstacles beside the spheres (rmp2_dynamics_step_contacts_planes).  The routines below take the planes as a defaulted
-// template parameter: with NoPlanes (every instantiation that existed before the planes) each `if constexpr (Pl::kOn)` is
-// discarded and the code is what it was.  PlaneTable: the fleet's records [P][4] = (n, d), free space n . x >= d, read at uniform
+// template parameter: with NoPlanes each `if constexpr (Pl::kOn)` is discarded and the code is what it is without planes.  PlaneTable: the fleet's records [P][4] = (n, d), free space n . x >= d, read at uniform
 // addresses like the shared sphere table; F, the robot's frame count, places the plane rows' pair indices after the spheres':
 // F K + 2 (f P + p) + e.
 struct NoPlanes {
@@ -774,15 +781,21 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
 }
 
 #if defined(__HIPCC__)
-// One lane per robot, one wave per block; the per-lane storage of the wave's 64 robots in LDS, lane-interleaved.
-template <int N, int SLOTS>
+// The step's one kernel: one lane per robot, one wave per block; the per-lane storage of the wave's 64 robots in LDS,
+// lane-interleaved (the plane rows go into the same candidate slots: no word more with PLANES).  LIST: every robot's own list over
+// a shared pool (csr_offset / csr_index; the lanes' trip counts and sphere addresses differ), else the shared table and both are
+// unused.  PLANES: planes [P][4] beside the spheres, read at uniform addresses, F the robot's frame count; else the three are
+// unused and the routines are instantiated with NoPlanes.
+template <int N, int SLOTS, bool LIST, bool PLANES>
 __global__ void __launch_bounds__(kWave)
 rmp2_dynamics_step_contacts_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
                                    float az, float* q, float* qd, const float* __restrict__ u, int accel,
                                    const float* __restrict__ lim, const float* __restrict__ qlo, const float* __restrict__ qhi,
-                                   const float* __restrict__ caps, const float* __restrict__ spheres, int K, float d_act, float dt,
-                                   int substeps, float* __restrict__ qdd_out, float* __restrict__ tau_out,
-                                   float* __restrict__ stop_out, float* __restrict__ contact_out, float* __restrict__ lambda_out,
+                                   const float* __restrict__ caps, const float* __restrict__ spheres, int K,
+                                   const int32_t* __restrict__ csr_offset, const int32_t* __restrict__ csr_index,
+                                   const float* __restrict__ planes, int P, int F, float d_act, float dt, int substeps,
+                                   float* __restrict__ qdd_out, float* __restrict__ tau_out, float* __restrict__ stop_out,
+                                   float* __restrict__ contact_out, float* __restrict__ lambda_out,
                                    int32_t* __restrict__ pair_out, uint32_t* __restrict__ status_out, int R) {
   static_assert(contact_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
   __shared__ float lds[contact_words(N) * kWave];
@@ -792,43 +805,21 @@ rmp2_dynamics_step_contacts_kernel(const DevProgram* __restrict__ prog, const fl
   const size_t row = (size_t)robot * n_dof;
   const size_t crow = (size_t)robot * kMaxContacts;
   const float base_acc[3] = {ax, ay, az};
-  dynamics_step_contacts_robot<N, SLOTS>(prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim,
-                                         qlo, qhi, caps, spheres, K, d_act, dt, substeps, qdd_out ? qdd_out + row : nullptr,
-                                         tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
-                                         contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr,
-                                         pair_out ? pair_out + crow : nullptr, status_out ? status_out + robot : nullptr,
-                                         lds + threadIdx.x, kWave);
-}
-
-// The same with every robot's own list over a shared pool: the lanes' trip counts and sphere addresses differ.
-template <int N, int SLOTS>
-__global__ void __launch_bounds__(kWave)
-rmp2_dynamics_step_contacts_lists_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
-                                         float az, float* q, float* qd, const float* __restrict__ u, int accel,
-                                         const float* __restrict__ lim, const float* __restrict__ qlo,
-                                         const float* __restrict__ qhi, const float* __restrict__ caps,
-                                         const float* __restrict__ spheres, int K, const int32_t* __restrict__ csr_offset,
-                                         const int32_t* __restrict__ csr_index, float d_act, float dt, int substeps,
-                                         float* __restrict__ qdd_out, float* __restrict__ tau_out, float* __restrict__ stop_out,
-                                         float* __restrict__ contact_out, float* __restrict__ lambda_out,
-                                         int32_t* __restrict__ pair_out, uint32_t* __restrict__ status_out, int R) {
-  static_assert(contact_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
-  __shared__ float lds[contact_words(N) * kWave];
-  const int robot = blockIdx.x * kWave + threadIdx.x;
-  if (robot >= R) return;
-  const int n_dof = prog->n_dof;
-  const size_t row = (size_t)robot * n_dof;
-  const size_t crow = (size_t)robot * kMaxContacts;
-  const float base_acc[3] = {ax, ay, az};
-  int beg;
-  const int len = contact_list_span(csr_offset, robot, beg);
-  dynamics_step_contacts_robot<N, SLOTS, true>(prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0,
-                                               lim, qlo, qhi, caps, spheres, K, d_act, dt, substeps,
-                                               qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr,
-                                               stop_out ? stop_out + row : nullptr, contact_out ? contact_out + row : nullptr,
-                                               lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
-                                               status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave,
-                                               csr_index + beg, len);
+  const int32_t* list = nullptr;
+  int len = 0;
+  if constexpr (LIST) {
+    int beg;
+    len = contact_list_span(csr_offset, robot, beg);
+    list = csr_index + beg;
+  }
+  using Pl = std::conditional_t<PLANES, PlaneTable, NoPlanes>;
+  Pl pl{};
+  if constexpr (PLANES) pl = {planes, P, F};
+  dynamics_step_contacts_robot<N, SLOTS, LIST, Pl>(
+      prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim, qlo, qhi, caps, spheres, K, d_act,
+      dt, substeps, qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
+      contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
+      status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, pl);
 }
 #endif
 

@@ -1,0 +1,40 @@
+// rmp2_contacts_tu.hip -- the instantiations of rmp2_dynamics_step_contacts_kernel (rmp2_contacts.h) of one form and their launcher.
+// Compiled four times, RMP2_TU_LIST = 0 (the shared sphere table) or 1 (per-robot lists over a pool) by RMP2_TU_PLANES = 0 or 1
+// (half-spaces beside the spheres), each a code object of its own: a form's device code does not depend on the others' being there.
+#include <cfloat>
+#include <cmath>
+
+#include "rmp2_host.h"
+#include "rmp2_contacts.h"
+
+#if !defined(RMP2_TU_LIST) || !defined(RMP2_TU_PLANES)
+#error "RMP2_TU_LIST and RMP2_TU_PLANES must each be 0 or 1"
+#endif
+
+namespace rmp2 {
+
+#if RMP2_TU_LIST && RMP2_TU_PLANES
+RMP2_DECL_CONTACTS(launch_contacts_lists_planes) {
+#elif RMP2_TU_LIST
+RMP2_DECL_CONTACTS(launch_contacts_lists) {
+#elif RMP2_TU_PLANES
+RMP2_DECL_CONTACTS(launch_contacts_table_planes) {
+#else
+RMP2_DECL_CONTACTS(launch_contacts_table) {
+#endif
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  // N = the handle's template size (2, or 9 for 3 .. 9 dofs), SLOTS = the unpruned program's save slots (0 .. 2)
+  auto launch = [&](auto N) {
+    with_slots(h->n_slots_full, [&](auto S) {
+      hipLaunchKernelGGL((rmp2_dynamics_step_contacts_kernel<N, S, RMP2_TU_LIST != 0, RMP2_TU_PLANES != 0>), grid, block, 0, s,
+                         h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd, u, accel, lim, qlo, qhi, h->d_contact_caps, spheres, K,
+                         csr_offset, csr_index, planes, P, h->n_frames, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
+                         lambda_out, pair_out, status_out, R);
+    });
+  };
+  if (h->n_template == 2) launch(std::integral_constant<int, 2>());
+  else launch(std::integral_constant<int, 9>());
+}
+
+}  // namespace rmp2

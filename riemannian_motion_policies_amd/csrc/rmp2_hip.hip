@@ -1714,17 +1714,6 @@ int realloc_device(rmp2_handle* h, T** p, size_t bytes) {
   return RMP2_OK;
 }
 
-// f(std::integral_constant<int, S>) with S = n, the save slots of a program: the SLOTS argument of a kernel template.  rmp2_create
-// refuses programs with more than 2.
-template <class F>
-auto with_slots(int n, F&& f) {
-  switch (n) {
-    case 0: return f(std::integral_constant<int, 0>());
-    case 1: return f(std::integral_constant<int, 1>());
-    default: return f(std::integral_constant<int, 2>());
-  }
-}
-
 // Structural zeros of the position Jacobian.  The reference differentiates the frame's position through the chain of LOCAL
 // transforms (kinematics.py:243-270): where the origin of frame f lies ON the axis of a revolute ancestor joint j for every q
 // -- joint f's own axis; consecutive joints whose <origin xyz> is 0 (Panda joints 1/2, 5/6); a tool frame straight up the last
@@ -2418,46 +2407,61 @@ void launch_dynamics_step_stops(const rmp2_handle* h, float* q, float* qd, const
   });
 }
 
-// rmp2_dynamics_step_contacts: the step with stops and obstacle contacts (the kernel and its routines are rmp2_contacts.h)
-template <int N>
-void launch_dynamics_step_contacts(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim,
-                                   const float* qlo, const float* qhi, const float* spheres, int K, float d_act, float dt,
-                                   int substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,
-                                   float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s) {
-  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
-  const float* a = h->base_acc;
-  with_slots(h->n_slots_full, [&](auto S) {
-    hipLaunchKernelGGL((rmp2_dynamics_step_contacts_kernel<N, S>), grid, block, 0, s, h->d_prog_full, h->d_inert, a[0], a[1], a[2],
-                       q, qd, u, accel, lim, qlo, qhi, h->d_contact_caps, spheres, K, d_act, dt, substeps, qdd_out, tau_out,
-                       stop_out, contact_out, lambda_out, pair_out, status_out, R);
-  });
+// The contact step's launchers (rmp2_contacts_tu.hip; the kernel and its routines are rmp2_contacts.h): [LIST][PLANES]
+constexpr decltype(&launch_contacts_table) kLaunchContacts[2][2] = {{launch_contacts_table, launch_contacts_table_planes},
+                                                                    {launch_contacts_lists, launch_contacts_lists_planes}};
+
+// The host path of the three contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
+// each entry point keeps its `what` and its own rules (table: K <= RMP2_MAX_CONTACT_SPHERES; lists: both CSR arrays, the pool
+// aligned; planes: the CSR arrays both set or both null, P and the plane table).  The planes entry always runs a PLANES kernel,
+// P == 0 included.
+enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes };
+
+int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float* q, float* qd, const float* u, int32_t drive,
+                       const float* tau_limit, const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
+                       const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P, float d_act, float dt,
+                       int32_t substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
+                       int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  const std::string w = what;
+  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
+  const bool with_planes = form == kContactsPlanes;
+  if (with_planes && (csr_offset != nullptr) != (csr_index != nullptr))
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": csr_offset and csr_index go together (both null: the shared table)");
+  const bool lists = form == kContactsLists || (with_planes && csr_offset);
+  const int k_max = lists ? RMP2_MAX_CONTACT_POOL : RMP2_MAX_CONTACT_SPHERES;
+  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": K < 0");
+  if (K > k_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": K > " + std::to_string(k_max));
+  if (lists && K > 0 && spheres && ((uintptr_t)spheres & 15u))
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the pool must be 16-byte aligned");
+  if (with_planes) {
+    if (P < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": P < 0");
+    if (P > RMP2_MAX_CONTACT_PLANES)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": P > " + std::to_string(RMP2_MAX_CONTACT_PLANES));
+    if (P > 0 && !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null plane table with P > 0");
+    if (P > 0 && ((uintptr_t)planes & 15u))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the plane table must be 16-byte aligned");
+  }
+  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": d_act must be finite and >= 0");
+  if (h->contact_n == 0)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
+  if (h->n_template > 9)
+    return fail(h, RMP2_ERR_UNSUPPORTED,
+                w + ": robots of more than 9 dofs are not supported (this one has " + std::to_string(h->n_dof) + ")");
+  bool launch;
+  const bool others_ok = (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres) &&
+                         (form != kContactsLists || (csr_offset && csr_index));
+  if (int rc = step_rows_check(h, what, q, qd, u, others_ok, R, launch)) return rc;
+  if (!launch) return RMP2_OK;
+  // (N in {2, 9} by the handle's template size, SLOTS by its program)
+  kLaunchContacts[lists][with_planes](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
+                                      csr_index, planes, P, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
+                                      contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
+  HIP_TRY(h, hipGetLastError());
+  return RMP2_OK;
 }
 
 }  // namespace
-
-// rmp2_dynamics_step_contacts_lists: the same with per-robot lists over a pool.  Its kernels and their launcher are a translation
-// unit of their own (rmp2_contacts_lists_tu.hip), so that this unit's device code is what it is without them.
-namespace rmp2 {
-void launch_dynamics_step_contacts_lists(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim,
-                                         const float* qlo, const float* qhi, const float* spheres, int K, const int32_t* csr_offset,
-                                         const int32_t* csr_index, float d_act, float dt, int substeps, float* qdd_out,
-                                         float* tau_out, float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out,
-                                         uint32_t* status_out, int R, hipStream_t s);
-// rmp2_dynamics_step_contacts_planes: half-space obstacles beside the spheres, over the shared table or over per-robot lists.  Its
-// kernels and their launchers are rmp2_contact_planes_tu.hip, compiled once per form.
-void launch_dynamics_step_contacts_planes_table(const rmp2_handle* h, float* q, float* qd, const float* u, int accel,
-                                                const float* lim, const float* qlo, const float* qhi, const float* spheres, int K,
-                                                const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int P,
-                                                float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
-                                                float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out,
-                                                uint32_t* status_out, int R, hipStream_t s);
-void launch_dynamics_step_contacts_planes_lists(const rmp2_handle* h, float* q, float* qd, const float* u, int accel,
-                                                const float* lim, const float* qlo, const float* qhi, const float* spheres, int K,
-                                                const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int P,
-                                                float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
-                                                float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out,
-                                                uint32_t* status_out, int R, hipStream_t s);
-}
 
 // =========================================================================================
 // C ABI
@@ -4015,29 +4019,9 @@ int rmp2_dynamics_step_contacts(rmp2_handle* h, float* q, float* qd, const float
                                 const float* q_lower, const float* q_upper, const float* spheres, int32_t K, float d_act, float dt,
                                 int32_t substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,
                                 float* contact_lambda, int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
-  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
-  const char* what = "dynamics step with contacts";
-  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
-  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K < 0");
-  if (K > RMP2_MAX_CONTACT_SPHERES)
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K > " + std::to_string(RMP2_MAX_CONTACT_SPHERES));
-  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": d_act must be finite and >= 0");
-  if (h->contact_n == 0)
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
-  if (h->n_template > 9)
-    return fail(h, RMP2_ERR_UNSUPPORTED, std::string(what) + ": robots of more than 9 dofs are not supported (this one has " +
-                                             std::to_string(h->n_dof) + ")");
-  bool launch;
-  if (int rc = step_rows_check(h, what, q, qd, u, (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres), R, launch)) return rc;
-  if (!launch) return RMP2_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int accel = drive == RMP2_DRIVE_ACCEL;
-  switch (h->n_template) {
-    case 2: launch_dynamics_step_contacts<2>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s); break;
-    default: launch_dynamics_step_contacts<9>(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s); break;
-  }
-  HIP_TRY(h, hipGetLastError());
-  return RMP2_OK;
+  return contacts_step_impl(h, "dynamics step with contacts", kContactsTable, q, qd, u, drive, tau_limit, q_lower, q_upper, spheres, K,
+                            nullptr, nullptr, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
+                            contact_lambda, contact_pair, status_out, R, stream);
 }
 
 int rmp2_dynamics_step_contacts_lists(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
@@ -4045,32 +4029,9 @@ int rmp2_dynamics_step_contacts_lists(rmp2_handle* h, float* q, float* qd, const
                                       const int32_t* csr_offset, const int32_t* csr_index, float d_act, float dt, int32_t substeps,
                                       float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
                                       int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
-  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
-  const char* what = "dynamics step with contact lists";
-  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
-  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K < 0");
-  if (K > RMP2_MAX_CONTACT_POOL)
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K > " + std::to_string(RMP2_MAX_CONTACT_POOL));
-  if (K > 0 && spheres && ((uintptr_t)spheres & 15u))
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": the pool must be 16-byte aligned");
-  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": d_act must be finite and >= 0");
-  if (h->contact_n == 0)
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
-  if (h->n_template > 9)
-    return fail(h, RMP2_ERR_UNSUPPORTED, std::string(what) + ": robots of more than 9 dofs are not supported (this one has " +
-                                             std::to_string(h->n_dof) + ")");
-  bool launch;
-  if (int rc = step_rows_check(h, what, q, qd, u,
-                               (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres) && csr_offset && csr_index, R, launch))
-    return rc;
-  if (!launch) return RMP2_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int accel = drive == RMP2_DRIVE_ACCEL;
-  launch_dynamics_step_contacts_lists(h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index, d_act, dt,
-                                      substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R,
-                                      s);   // (N in {2, 9} by the handle's template size, SLOTS by its program)
-  HIP_TRY(h, hipGetLastError());
-  return RMP2_OK;
+  return contacts_step_impl(h, "dynamics step with contact lists", kContactsLists, q, qd, u, drive, tau_limit, q_lower, q_upper,
+                            spheres, K, csr_offset, csr_index, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                            contact_out, contact_lambda, contact_pair, status_out, R, stream);
 }
 
 int rmp2_dynamics_step_contacts_planes(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
@@ -4079,40 +4040,9 @@ int rmp2_dynamics_step_contacts_planes(rmp2_handle* h, float* q, float* qd, cons
                                        float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out, float* stop_out,
                                        float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
                                        int32_t R, void* stream) {
-  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
-  const char* what = "dynamics step with contact planes";
-  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
-  if ((csr_offset != nullptr) != (csr_index != nullptr))
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": csr_offset and csr_index go together (both null: the shared table)");
-  const bool lists = csr_offset != nullptr;
-  const int k_max = lists ? RMP2_MAX_CONTACT_POOL : RMP2_MAX_CONTACT_SPHERES;
-  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K < 0");
-  if (K > k_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": K > " + std::to_string(k_max));
-  if (lists && K > 0 && spheres && ((uintptr_t)spheres & 15u))
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": the pool must be 16-byte aligned");
-  if (P < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": P < 0");
-  if (P > RMP2_MAX_CONTACT_PLANES)
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": P > " + std::to_string(RMP2_MAX_CONTACT_PLANES));
-  if (P > 0 && !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": null plane table with P > 0");
-  if (P > 0 && ((uintptr_t)planes & 15u))
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": the plane table must be 16-byte aligned");
-  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": d_act must be finite and >= 0");
-  if (h->contact_n == 0)
-    return fail(h, RMP2_ERR_INVALID_ARGUMENT, std::string(what) + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
-  if (h->n_template > 9)
-    return fail(h, RMP2_ERR_UNSUPPORTED, std::string(what) + ": robots of more than 9 dofs are not supported (this one has " +
-                                             std::to_string(h->n_dof) + ")");
-  bool launch;
-  if (int rc = step_rows_check(h, what, q, qd, u, (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres), R, launch)) return rc;
-  if (!launch) return RMP2_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int accel = drive == RMP2_DRIVE_ACCEL;
-  // (N in {2, 9} by the handle's template size, SLOTS by its program)
-  (lists ? launch_dynamics_step_contacts_planes_lists : launch_dynamics_step_contacts_planes_table)(
-      h, q, qd, u, accel, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index, planes, P, d_act, dt, substeps, qdd_out,
-      tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, s);
-  HIP_TRY(h, hipGetLastError());
-  return RMP2_OK;
+  return contacts_step_impl(h, "dynamics step with contact planes", kContactsPlanes, q, qd, u, drive, tau_limit, q_lower, q_upper,
+                            spheres, K, csr_offset, csr_index, planes, P, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                            contact_out, contact_lambda, contact_pair, status_out, R, stream);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rmp2_device.h"
@@ -114,6 +115,17 @@ struct rmp2_handle {
   } while (0)
 
 namespace rmp2 {
+// f(std::integral_constant<int, S>) with S = n, the save slots of a program: the SLOTS argument of a kernel template.  rmp2_create
+// refuses programs with more than 2.
+template <class F>
+auto with_slots(int n, F&& f) {
+  switch (n) {
+    case 0: return f(std::integral_constant<int, 0>());
+    case 1: return f(std::integral_constant<int, 1>());
+    default: return f(std::integral_constant<int, 2>());
+  }
+}
+
 // rmp2_quad_tu.hip: one object per template size N and save/restore slot count of the program
 #define RMP2_DECL_QUAD(NAME)                                                                                            \
   bool NAME(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs, const ObsArgs& o,         \
@@ -151,4 +163,16 @@ bool launch_hex_n9(const rmp2_handle* h, const float* q, const float* qd, const 
                    const OutArgs& out, const RolloutArgs& ro, int R, hipStream_t s);
 bool launch_hex_n16(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs, const ObsArgs& o,
                     const OutArgs& out, const RolloutArgs& ro, int R, hipStream_t s);
+// rmp2_contacts_tu.hip: the contact step's kernels (rmp2_contacts.h), one object per form -- [LIST][PLANES]: the shared sphere
+// table or per-robot lists over a pool, without or with half-spaces beside the spheres.  One signature; a form ignores the
+// arguments it has no use for (csr_offset / csr_index without LIST; planes / P without PLANES).
+#define RMP2_DECL_CONTACTS(NAME)                                                                                                  \
+  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
+            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
+            int P, float d_act, float dt, int substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,      \
+            float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
+RMP2_DECL_CONTACTS(launch_contacts_table);
+RMP2_DECL_CONTACTS(launch_contacts_table_planes);
+RMP2_DECL_CONTACTS(launch_contacts_lists);
+RMP2_DECL_CONTACTS(launch_contacts_lists_planes);
 }  // namespace rmp2

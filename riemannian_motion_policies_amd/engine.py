@@ -689,13 +689,16 @@ class Engine:
                                   or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
 
-        if contact_planes is not None:
-            _require_resident(self.device, contact_planes=contact_planes)
-            if (contact_planes.dim() != 2 or contact_planes.shape[1] != 4 or contact_planes.dtype != torch.float32
-                    or not contact_planes.is_contiguous()):
-                raise ValueError(f"contact_planes must be a contiguous fp32 [P, 4] tensor (normal, d), got {list(contact_planes.shape)}")
-            if contact_planes.shape[0] > MAX_CONTACT_PLANES:
-                raise ValueError(f"contact_planes holds {contact_planes.shape[0]} planes, at most {MAX_CONTACT_PLANES}")
+        if contacts is not None or contact_planes is not None:
+            P = 0
+            if contact_planes is not None:
+                _require_resident(self.device, contact_planes=contact_planes)
+                if (contact_planes.dim() != 2 or contact_planes.shape[1] != 4 or contact_planes.dtype != torch.float32
+                        or not contact_planes.is_contiguous()):
+                    raise ValueError(f"contact_planes must be a contiguous fp32 [P, 4] tensor (normal, d), got {list(contact_planes.shape)}")
+                P = int(contact_planes.shape[0])
+                if P > MAX_CONTACT_PLANES:
+                    raise ValueError(f"contact_planes holds {P} planes, at most {MAX_CONTACT_PLANES}")
             if contacts is None and contact_lists is not None:
                 raise ValueError("contact_lists needs contacts (the pool the lists index)")
             K = 0
@@ -722,55 +725,25 @@ class Engine:
                             or not t.is_contiguous() or (t.dim() != 1 if shape is None else tuple(t.shape) != shape)):
                         raise ValueError(f"contact_lists {name} must be a contiguous int32 {'1-D' if shape is None else list(shape)} "
                                          f"tensor on {self.device}")
-                if csr_index.numel() == 0:
-                    csr_index = self._empty_index
-            P = int(contact_planes.shape[0])
-            _native.check(self._lib.rmp2_dynamics_step_contacts_planes(
-                self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
-                contacts.data_ptr() if K else None, K, ptr(csr_offset), ptr(csr_index),
-                contact_planes.data_ptr() if P else None, P, float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out),
-                ptr(stop_out), ptr(contact_out), ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s), self._h)
-            return
-        if contacts is None:
-            if contact_lists is not None:
-                raise ValueError("contact_lists needs contacts (the pool the lists index)")
-            if contact_out is not None or contact_lambda_out is not None or contact_pair_out is not None:
-                raise ValueError("contact_out / contact_lambda_out / contact_pair_out need contacts")
-        else:
-            _require_resident(self.device, contacts=contacts)
-            if contacts.dim() != 2 or contacts.shape[1] != 4:
-                raise ValueError(f"contacts must be [K, 4] spheres (centre, radius), got {list(contacts.shape)}")
-            if contact_out is not None:
-                self._dynamics_out("contact_out", contact_out, (R, self.n_dof))
-            if contact_lambda_out is not None:
-                self._dynamics_out("contact_lambda_out", contact_lambda_out, (R, MAX_CONTACTS))
-            check_int("contact_pair_out", contact_pair_out, (R, MAX_CONTACTS))
-            check_int("status_out", status_out, (R,))
-            lower, upper = (None, None) if q_limits is None else self._q_limits_device(q_limits)
-            if contact_lists is not None:
-                try:
-                    csr_offset, csr_index = contact_lists
-                except (TypeError, ValueError):
-                    raise ValueError("contact_lists must be a pair (csr_offset, csr_index)") from None
-                for name, t, shape in (("csr_offset", csr_offset, (R + 1,)), ("csr_index", csr_index, None)):
-                    if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32
-                            or not t.is_contiguous() or (t.dim() != 1 if shape is None else tuple(t.shape) != shape)):
-                        raise ValueError(f"contact_lists {name} must be a contiguous int32 {'1-D' if shape is None else list(shape)} "
-                                         f"tensor on {self.device}")
                 if csr_index.numel() == 0:   # every list empty: the C ABI still wants a readable pointer (it cannot see the counts)
                     csr_index = self._empty_index   # (made by set_contact_capsules; without capsules the call is refused anyway)
-                _native.check(self._lib.rmp2_dynamics_step_contacts_lists(
-                    self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
-                    contacts.data_ptr() if contacts.shape[0] else None, int(contacts.shape[0]), csr_offset.data_ptr(),
-                    ptr(csr_index), float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), ptr(stop_out),
-                    ptr(contact_out), ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s), self._h)
-                return
-            _native.check(self._lib.rmp2_dynamics_step_contacts(
-                self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
-                contacts.data_ptr() if contacts.shape[0] else None, int(contacts.shape[0]), float(d_act), float(dt), int(substeps),
-                ptr(qdd_out), ptr(tau_out), ptr(stop_out), ptr(contact_out), ptr(contact_lambda_out), ptr(contact_pair_out),
-                ptr(status_out), R, s), self._h)
+            head = (self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
+                    contacts.data_ptr() if K else None, K)
+            tail = (float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), ptr(stop_out), ptr(contact_out),
+                    ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s)
+            lists = (ptr(csr_offset), ptr(csr_index))
+            if contact_planes is not None:
+                rc = self._lib.rmp2_dynamics_step_contacts_planes(*head, *lists, contact_planes.data_ptr() if P else None, P, *tail)
+            elif contact_lists is not None:
+                rc = self._lib.rmp2_dynamics_step_contacts_lists(*head, *lists, *tail)
+            else:
+                rc = self._lib.rmp2_dynamics_step_contacts(*head, *tail)
+            _native.check(rc, self._h)
             return
+        if contact_lists is not None:
+            raise ValueError("contact_lists needs contacts (the pool the lists index)")
+        if contact_out is not None or contact_lambda_out is not None or contact_pair_out is not None:
+            raise ValueError("contact_out / contact_lambda_out / contact_pair_out need contacts")
         if q_limits is None:
             if stop_out is not None or status_out is not None:
                 raise ValueError("stop_out / status_out need q_limits")

@@ -127,20 +127,3 @@ def linearised_gaps(c, got_qd, pair, dt):
                 jn[r, s] = np.abs(pr["J"][r, k]).sum()
     return out, jn
 
-
-def write_driver_input(path, c, q, qd, u, dt, substeps, d_act, spheres=None, planes=None, lists=None):
-    """Input of tests/contact_planes_driver.cpp for the case c: contacts_reference.write_driver_input's, then int32 has_lists,
-    [int32 offset [B + 1], int32 n_index, int32 index] and int32 P, float planes [P][4]."""
-    CR.write_driver_input(path, c["t"], c["inert"], c["caps"], c["spheres"] if spheres is None else spheres, d_act, q, qd, u,
-                          c["drive"], c["lim"], c["limits"], dt, substeps, c["g"])
-    pl = np.ascontiguousarray(c["planes"] if planes is None else planes, np.float32).reshape(-1, 4)
-    with open(path, "ab") as f:
-        np.array([0 if lists is None else 1], np.int32).tofile(f)
-        if lists is not None:
-            off, idx = (np.ascontiguousarray(x, np.int32) for x in lists)
-            assert len(off) == len(q) + 1
-            off.tofile(f)
-            np.array([len(idx)], np.int32).tofile(f)
-            idx.tofile(f)
-        np.array([len(pl)], np.int32).tofile(f)
-        pl.tofile(f)

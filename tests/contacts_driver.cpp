@@ -1,14 +1,20 @@
-// Host driver of rmp2_contacts.h for tests/test_contacts_host.py: no GPU, the device routine's own code on the CPU, the per-lane
-// storage in a local array (stride 1), with the template sizes the library picks.  Input (argv[1], native byte order;
-// tests/contacts_reference.py write_driver_input): the input of tests/forward_dynamics_driver.cpp in mode 2, followed by int32
-// has_limits, float lower[n_dof], upper[n_dof], float caps[F][8], int32 K, float d_act, float spheres[K][4].  Output (argv[2]):
-// float q, qd, qdd, tau, stop, contact [n_states][n_dof] each, float lambda[n_states][8], int32 pair[n_states][8], uint32
-// status[n_states].
+// Host driver of rmp2_contacts.h for the contact host tests (tests/test_contacts_host.py, test_contacts_lists_host.py,
+// test_contact_planes_host.py): no GPU, the device routine's own code on the CPU (dynamics_step_contacts_robot<N, SLOTS, LIST, Pl>,
+// what the kernel calls), the per-lane storage in a local array (stride 1), with the template sizes the library picks.  Input
+// (argv[1], native byte order; tests/contacts_reference.py write_driver_input): the input of tests/forward_dynamics_driver.cpp in
+// mode 2, followed by int32 has_limits, float lower[n_dof], upper[n_dof], float caps[F][8], int32 K, float d_act, float
+// spheres[K][4], int32 has_lists, [int32 offset[n_states + 1], int32 n_index, int32 index[n_index]] when has_lists (the table is
+// then the POOL, K <= RMP2_MAX_CONTACT_POOL), int32 has_planes, [int32 P, float planes[P][4]] when has_planes.  The form follows
+// the flags as the library's follows the entry point: no plane section runs Pl = NoPlanes, a plane section with P = 0 PlaneTable.
+// Output (argv[2]): float q, qd, qdd, tau, stop, contact [n_states][n_dof] each, float lambda[n_states][8], int32
+// pair[n_states][8], uint32 status[n_states].  The sphere table, the index array and the plane table are allocated at exactly
+// their sizes, so that a sanitizer build sees any read past them.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "rmp2_contacts.h"
@@ -20,32 +26,46 @@ struct Job {
   std::vector<rmp2::DevOp> ops;
   int n, B, drive, substeps, K;
   float dt, d_act;
-  std::vector<float> inert, acc, lim, lo, hi, caps, spheres, q, qd, u, qdd, tau, stop, contact, lambda;
-  std::vector<int32_t> pair;
+  std::vector<float> inert, acc, lim, lo, hi, caps, q, qd, u, qdd, tau, stop, contact, lambda;
+  std::unique_ptr<float[]> spheres;     // exactly [K][4]
+  std::unique_ptr<int32_t[]> index;     // exactly [n_index]
+  std::unique_ptr<float[]> planes;      // exactly [P][4]
+  int P = 0;
+  std::vector<int32_t> pair, offset;
   std::vector<uint32_t> status;
   bool has_lim, has_limits;
 };
 
-template <int N, int SLOTS>
+template <int N, int SLOTS, bool LIST, class Pl>
 static void run(Job& j) {
   const int n = j.n;
   std::vector<float> lds(rmp2::contact_words(N));
   for (int b = 0; b < j.B; ++b) {
     const size_t o = (size_t)b * n, c = (size_t)b * rmp2::kMaxContacts;
-    rmp2::dynamics_step_contacts_robot<N, SLOTS>(
+    int beg = 0, len = 0;
+    if (LIST) len = rmp2::contact_list_span(j.offset.data(), b, beg);
+    Pl pl{};
+    if constexpr (Pl::kOn) pl = {j.planes.get(), j.P, (int)j.ops.size()};
+    rmp2::dynamics_step_contacts_robot<N, SLOTS, LIST, Pl>(
         j.ops.data(), (int)j.ops.size(), n, j.inert.data(), j.acc.data(), j.q.data() + o, j.qd.data() + o, j.u.data() + o,
         j.drive == RMP2_DRIVE_ACCEL, j.has_lim ? j.lim.data() : nullptr, j.has_limits ? j.lo.data() : nullptr,
-        j.has_limits ? j.hi.data() : nullptr, j.caps.data(), j.spheres.data(), j.K, j.d_act, j.dt, j.substeps, j.qdd.data() + o,
-        j.tau.data() + o, j.stop.data() + o, j.contact.data() + o, j.lambda.data() + c, j.pair.data() + c, j.status.data() + b,
-        lds.data(), 1);
+        j.has_limits ? j.hi.data() : nullptr, j.caps.data(), j.spheres.get(), j.K, j.d_act, j.dt, j.substeps,
+        j.qdd.data() + o, j.tau.data() + o, j.stop.data() + o, j.contact.data() + o, j.lambda.data() + c, j.pair.data() + c,
+        j.status.data() + b, lds.data(), 1, LIST ? j.index.get() + beg : nullptr, len, pl);
   }
 }
 
+template <int N, int SLOTS>
+static void run_form(bool lists, bool planes, Job& j) {
+  if (lists) planes ? run<N, SLOTS, true, rmp2::PlaneTable>(j) : run<N, SLOTS, true, rmp2::NoPlanes>(j);
+  else planes ? run<N, SLOTS, false, rmp2::PlaneTable>(j) : run<N, SLOTS, false, rmp2::NoPlanes>(j);
+}
+
 template <int N>
-static void run_n(int slots, Job& j) {
-  if (slots == 0) run<N, 0>(j);
-  else if (slots == 1) run<N, 1>(j);
-  else run<N, 2>(j);
+static void run_n(int slots, bool lists, bool planes, Job& j) {
+  if (slots == 0) run_form<N, 0>(lists, planes, j);
+  else if (slots == 1) run_form<N, 1>(lists, planes, j);
+  else run_form<N, 2>(lists, planes, j);
 }
 
 int main(int argc, char** argv) {
@@ -80,13 +100,28 @@ int main(int argc, char** argv) {
       !rd(f, &has_limits, 1) || !rd(f, j.lo.data(), j.lo.size()) || !rd(f, j.hi.data(), j.hi.size()) ||
       !rd(f, j.caps.data(), j.caps.size()) || !rd(f, &K, 1) || !rd(f, &j.d_act, 1))
     return 8;
-  if (K < 0 || K > RMP2_MAX_CONTACT_SPHERES) return 5;
   j.K = K, j.has_limits = has_limits != 0;
-  j.spheres.resize((size_t)K * 4);
-  if (!rd(f, j.spheres.data(), j.spheres.size())) return 8;
+  if (K < 0 || K > RMP2_MAX_CONTACT_POOL) return 5;
+  j.spheres.reset(new float[(size_t)K * 4]);
+  int32_t has_lists = 0, n_index = 0, has_planes = 0, P = 0;
+  if (!rd(f, j.spheres.get(), (size_t)K * 4) || !rd(f, &has_lists, 1)) return 8;
+  if (!has_lists && K > RMP2_MAX_CONTACT_SPHERES) return 5;
+  if (has_lists) {
+    j.offset.resize((size_t)B + 1);
+    if (!rd(f, j.offset.data(), j.offset.size()) || !rd(f, &n_index, 1) || n_index < 0) return 8;
+    j.index.reset(new int32_t[n_index]);
+    if (!rd(f, j.index.get(), (size_t)n_index)) return 8;
+  }
+  if (!rd(f, &has_planes, 1)) return 8;
+  if (has_planes) {
+    if (!rd(f, &P, 1) || P < 0 || P > RMP2_MAX_CONTACT_PLANES) return 8;
+    j.P = P;
+    j.planes.reset(new float[(size_t)P * 4]);
+    if (!rd(f, j.planes.get(), (size_t)P * 4)) return 8;
+  }
   fclose(f);
-  if (n <= 2) run_n<2>(slots, j);
-  else run_n<9>(slots, j);
+  if (n <= 2) run_n<2>(slots, has_lists != 0, has_planes != 0, j);
+  else run_n<9>(slots, has_lists != 0, has_planes != 0, j);
   FILE* g = fopen(argv[2], "wb");
   if (!g) return 9;
   for (const auto* x : {&j.q, &j.qd, &j.qdd, &j.tau, &j.stop, &j.contact, &j.lambda}) fwrite(x->data(), sizeof(float), x->size(), g);

@@ -445,9 +445,11 @@ def step_brackets(ref, dt, substeps):
 # ---- the host driver's input -------------------------------------------------------------------------------------------------
 
 def write_driver_input(path, table, inert, caps, spheres, d_act, q, qd, u, drive, lim, limits, dt, substeps,
-                       gravity=(0.0, 0.0, -9.81)):
+                       gravity=(0.0, 0.0, -9.81), lists=None, planes=None):
     """Input file of tests/contacts_driver.cpp: forward_dynamics_reference.write_driver_input's (mode 2) followed by int32
-    has_limits, float lower[n_dof], upper[n_dof], float caps[F][8], int32 K, float d_act, float spheres[K][4]."""
+    has_limits, float lower[n_dof], upper[n_dof], float caps[F][8], int32 K, float d_act, float spheres[K][4], int32 has_lists,
+    [int32 offset [B + 1], int32 n_index, int32 index] with lists = (csr_offset, csr_index), int32 has_planes, [int32 P, float
+    planes [P][4]] with planes = an array (an empty one too: the plane form on no planes)."""
     FR.write_driver_input(path, table, inert, q, qd, u, 2, drive=drive, lim=lim, dt=dt, substeps=substeps, gravity=gravity)
     lo, hi = _limits(table, limits)
     sph = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
@@ -459,6 +461,18 @@ def write_driver_input(path, table, inert, caps, spheres, d_act, q, qd, u, drive
         np.array([len(sph)], np.int32).tofile(f)
         np.array([d_act], np.float32).tofile(f)
         sph.tofile(f)
+        np.array([0 if lists is None else 1], np.int32).tofile(f)
+        if lists is not None:
+            off, idx = (np.ascontiguousarray(x, np.int32) for x in lists)
+            assert len(off) == len(q) + 1
+            off.tofile(f)
+            np.array([len(idx)], np.int32).tofile(f)
+            idx.tofile(f)
+        np.array([0 if planes is None else 1], np.int32).tofile(f)
+        if planes is not None:
+            pl = np.ascontiguousarray(planes, np.float32).reshape(-1, 4)
+            np.array([len(pl)], np.int32).tofile(f)
+            pl.tofile(f)
 
 
 def read_driver_output(path, B, n):

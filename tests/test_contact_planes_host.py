@@ -1,6 +1,6 @@
 """Half-space obstacles beside the spheres (include/rmp2.h rmp2_dynamics_step_contacts_planes) on the host: the scenes of
 tests/contact_planes_scene.py meet their stated conditions; the fp32 envelope that the bounds are taken from; the plane form of
-the device routine of rmp2_contacts.h run on the CPU through tests/contact_planes_driver.cpp (also under the host sanitizers, as
+the device routine of rmp2_contacts.h run on the CPU through tests/contacts_driver.cpp (also under the host sanitizers, as
 a stand-alone program) against the fp64 reference of tests/contact_planes_reference.py, and BIT FOR BIT against the sphere, list
 and stops drivers where the contract promises it; pair indices, poisoning, the header and urdf.contact_planes.  No GPU.
 
@@ -38,23 +38,23 @@ def groups(golden_dir, tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def planes_driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_planes_driver.cpp", "contact_planes_driver")
-
-
-@pytest.fixture(scope="module")
-def planes_driver_san(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_planes_driver.cpp", "contact_planes_driver_san", SAN)
-
-
-@pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver")
 
 
 @pytest.fixture(scope="module")
-def lists_driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contacts_lists_driver.cpp", "contacts_lists_driver")
+def planes_driver(driver):
+    return driver
+
+
+@pytest.fixture(scope="module")
+def lists_driver(driver):
+    return driver
+
+
+@pytest.fixture(scope="module")
+def planes_driver_san(tmp_path_factory):
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver_san", SAN)
 
 
 @pytest.fixture(scope="module")
@@ -68,14 +68,10 @@ def whole_lists(B, K):
 
 
 def run_planes(exe, tmp_path, c, substeps=1, spheres=None, planes=None, lists=None, q=None, d_act=D_ACT):
-    """The plane driver on a group (fields replaced by the keywords): contacts_reference.read_driver_output's dict.  A sanitizer
-    report fails it: the exit status must be 0 and nothing may be written to stderr."""
-    q = c["q"] if q is None else q
-    path, out = str(tmp_path / "pin.bin"), str(tmp_path / "pout.bin")
-    PR.write_driver_input(path, c, q, c["qd"], c["u"], DT, substeps, d_act, spheres=spheres, planes=planes, lists=lists)
-    p = subprocess.run([exe, path, out], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
-    return CR.read_driver_output(out, len(q), c["t"].n_dof)
+    """The driver's plane form on a group (fields replaced by the keywords; test_contacts_host.run_driver).  planes = an empty
+    table still runs the plane form."""
+    return S.run_driver(exe, tmp_path, c, substeps=substeps, spheres=spheres, d_act=d_act, q=q, lists=lists,
+                        planes=c["planes"] if planes is None else planes)
 
 
 def same(a, b, what, pairs=True):

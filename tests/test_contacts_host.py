@@ -470,13 +470,18 @@ def plain_driver(tmp_path_factory):
     return _build(tmp_path_factory, "forward_dynamics_driver.cpp", "forward_dynamics_driver")
 
 
-def run_driver(exe, tmp_path, c, substeps=1, spheres=None, limits="case", d_act=D_ACT, q=None, qd=None, u=None, caps=None):
-    """The device routine on the CPU on a case (fields replaced by the keywords): contacts_reference.read_driver_output's dict."""
+def run_driver(exe, tmp_path, c, substeps=1, spheres=None, limits="case", d_act=D_ACT, q=None, qd=None, u=None, caps=None,
+               lists=None, planes=None):
+    """The device routine on the CPU on a case (fields replaced by the keywords): contacts_reference.read_driver_output's dict.
+    lists = (csr_offset, csr_index): the list form, spheres being the pool; planes = [P, 4] (P = 0 too): the plane form.  The one
+    runner of the contact host tests.  A sanitizer report fails it: the exit status must be 0 and nothing may be written to
+    stderr."""
     q, qd, u = (c[k] if x is None else x for k, x in (("q", q), ("qd", qd), ("u", u)))
     CR.write_driver_input(str(tmp_path / "in.bin"), c["t"], c["inert"], c["caps"] if caps is None else caps,
                           c["spheres"] if spheres is None else spheres, d_act, q, qd, u, c["drive"], c["lim"],
-                          c["limits"] if limits == "case" else limits, DT, substeps, c["g"])
-    subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], check=True, timeout=300)
+                          c["limits"] if limits == "case" else limits, DT, substeps, c["g"], lists=lists, planes=planes)
+    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
     return CR.read_driver_output(str(tmp_path / "out.bin"), len(q), c["t"].n_dof)
 
 

@@ -1,13 +1,12 @@
 """Per-robot obstacle lists over a shared pool (include/rmp2.h rmp2_dynamics_step_contacts_lists) on the host: the list form of
-the device routine of rmp2_contacts.h run on the CPU through tests/contacts_lists_driver.cpp, against the shared-table form of
-the same routine (tests/contacts_driver.cpp) BIT FOR BIT wherever the contract promises it, against the stops' driver on empty
+the device routine of rmp2_contacts.h run on the CPU through tests/contacts_driver.cpp, against the shared-table form of
+the same routine (the same driver) BIT FOR BIT wherever the contract promises it, against the stops' driver on empty
 lists, and against the fp64 reference of tests/contacts_reference.py applied to spheres[list] per robot within the bounds of
 tests/test_contacts_host.py, unchanged (K_RES, K_VEL, K_FORCE, K_GAP on the robots kept by contacts_scene.kept).  The invalid
 lists also run under the host sanitizers, on a pool allocated at exactly K records.  No GPU.  Helpers at the top are shared
 with tests/test_gpu_contacts_lists.py."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -88,13 +87,13 @@ def driver(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def lists_driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contacts_lists_driver.cpp", "contacts_lists_driver")
+def lists_driver(driver):
+    return driver
 
 
 @pytest.fixture(scope="module")
 def lists_driver_san(tmp_path_factory):
-    return S._build(tmp_path_factory, "contacts_lists_driver.cpp", "contacts_lists_driver_san",
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver_san",
                     ("-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all", "-g"))
 
 
@@ -104,21 +103,9 @@ def stops_driver(tmp_path_factory):
 
 
 def run_lists(exe, tmp_path, c, pool, off, idx, substeps=1, rows=slice(None)):
-    """The list driver on the case's robots `rows`: contacts_reference.read_driver_output's dict.  A sanitizer report fails it:
-    the exit status must be 0 and nothing may be written to stderr."""
-    q, qd, u = c["q"][rows], c["qd"][rows], c["u"][rows]
-    path = str(tmp_path / "lin.bin")
-    CR.write_driver_input(path, c["t"], c["inert"], c["caps"], pool, D_ACT, q, qd, u, c["drive"], c["lim"], c["limits"], DT,
-                          substeps, c["g"])
-    off, idx = np.ascontiguousarray(off, np.int32), np.ascontiguousarray(idx, np.int32)
-    assert len(off) == len(q) + 1
-    with open(path, "ab") as f:
-        off.tofile(f)
-        np.array([len(idx)], np.int32).tofile(f)
-        idx.tofile(f)
-    p = subprocess.run([exe, path, str(tmp_path / "lout.bin")], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
-    return CR.read_driver_output(str(tmp_path / "lout.bin"), len(q), c["t"].n_dof)
+    """The driver's list form on the case's robots `rows` (test_contacts_host.run_driver)."""
+    return S.run_driver(exe, tmp_path, c, substeps=substeps, spheres=pool, q=c["q"][rows], qd=c["qd"][rows], u=c["u"][rows],
+                        lists=(off, idx))
 
 
 @pytest.fixture(scope="module")

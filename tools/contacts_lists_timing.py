@@ -1,165 +1,47 @@
 """Time the plant's step with per-robot obstacle lists (include/rmp2.h rmp2_dynamics_step_contacts_lists) against the shared-table
-call on the same spheres, in the form of tools/contacts_timing.py: the Panda with the reference's inertials at 4 096 and 65 536
-robots, acceleration drive against the URDF's effort limits, the Panda's joint limits, 10 substeps of 0.01, d_act = 0.03; medians
-over `reps` timed repeats of `steps` launches after a warm-up, the stepped state reset before EVERY launch, outside the launch's
-own pair of HIP events.  Prints ONE JSON line (profiles/contacts_lists_timing.json).
-
-The fleet is tools/contacts_timing.py's (of every four robots three near a base state that touches two or three spheres of a
-table of 32, one clear of it; 4 096 states tiled to the fleet size).  Per fleet size:
-  (a) `shared_us`: rmp2_dynamics_step_contacts on the 32-sphere table -- the unchanged entry point.  With --parent-lib (a library
-      built from the parent commit) the measurement alternates between that library and this build, `rounds` times each, every
-      measurement in a process of its own (RMP2_LIB picks the library); `parent_us` / `this_us` list them in order.
+call on the same spheres, on the workload and by the method of tools/contact_timing_common.py (the fleet, the timing loop,
+--parent-lib and what it adds to every leg).  Prints ONE JSON line (profiles/contacts_lists_timing.json).  Per fleet size:
+  (a) `shared_us`: rmp2_dynamics_step_contacts on the 32-sphere table.
   (b) `lists_same_us`: the list call, every robot's list = 0 .. 31 over that same table: every lane gathers the same addresses.
   (c) `lists_own_us`: the list call, robot r's list = 32 r .. 32 r + 31 over a pool of R x 32 records (the same 32 spheres
       replicated): every lane gathers its own 512 bytes.
-`b_over_a`, `c_over_b`: the ratios of the medians.  The three legs compute the same numbers: `same_results` says that the final q
-of (b) and (c) had the bits of (a)'s.
+`b_over_a`, `c_over_b`: the ratios of the medians.  The three legs compute the same numbers: `same_results` says that the final
+state and status of (b) and (c) had the bits of (a)'s.
 usage: python tools/contacts_lists_timing.py [--parent-lib PATH] [--rounds N] [steps] [reps]"""
 import json
-import os
-import subprocess
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-args = sys.argv[1:]
-parent_lib, rounds, child = None, 3, None
-while args and args[0].startswith("--"):
-    flag = args.pop(0)
-    if flag == "--parent-lib":
-        parent_lib = os.path.abspath(args.pop(0))
-    elif flag == "--rounds":
-        rounds = int(args.pop(0))
-    elif flag == "--child":
-        child = args.pop(0)
-    else:
-        sys.exit(__doc__)
-steps = int(args[0]) if len(args) > 0 else 20
-reps = int(args[1]) if len(args) > 1 else 7
-SUBSTEPS, DT, SIZES, STATES, SPHERES, D_ACT = 10, 0.01, (4096, 65536), 4096, 32, 0.03
+import contact_timing_common as T
 
 
-def run_child(what, lib=None):
-    env = dict(os.environ)
-    if lib is not None:
-        env["RMP2_LIB"] = lib
-    done = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", what, str(steps), str(reps)], env=env,
-                          capture_output=True, text=True, timeout=900)
-    if done.returncode != 0:
-        sys.exit(f"measurement {what!r} (library: {lib or 'this build'}) failed with {done.returncode}:\n{done.stderr[-2000:]}")
-    return json.loads(done.stdout.strip().splitlines()[-1])
+def call(c, tab, lists=None):
+    c.eng.dynamics_step(c.qs, c.qds, c.u, T.DT, stop_out=c.stop, status_out=c.status, contacts=tab, d_act=T.D_ACT,
+                        **({} if lists is None else {"contact_lists": lists}), **c.step)
 
 
-def measure(what):
-    import numpy as np
+def shared(c):
+    c.time("shared_us", lambda: call(c, c.spheres))
+    c.final("shared_bits", lambda: call(c, c.spheres))
+    c.row["contact_fraction"] = round(float((c.status.cpu().numpy() & 4 != 0).mean()), 4)
+
+
+def lists(c, own):
     import torch
-    import joint_stops_reference as JR
-    from test_inverse_dynamics_host import fixture_inertials
-    from riemannian_motion_policies_amd import descriptor as D, urdf as U
-    from riemannian_motion_policies_amd.engine import Engine
-
-    dev = torch.device("cuda", 0)
-    table = U.panda_table()
-    inert = U.inertial_table(table, fixture_inertials(os.path.join(ROOT, "tests", "golden"), "panda"))
-    eng = Engine(D.build_desc(table, []), 0)
-    eng.set_inertials(inert)
-    effort = torch.from_numpy(U.read_effort_limits(U.PANDA_URDF, U.PANDA_ORDER)).to(dev)
-    lo, hi = (torch.from_numpy(x).to(dev) for x in JR.table_limits(table))
-    import test_contacts_host as S
-    caps = S.robot_capsules("panda")
-    eng.set_contact_capsules(caps)
-    q0, qd0, u0, spheres = S.contact_fleet(np.random.default_rng(600), table, inert, (0.0, 0.0, -9.81), caps, STATES, SPHERES)
-
-    def timed(fn, reset):
-        for _ in range(3):
-            reset()
-            fn()
-        torch.cuda.synchronize()
-        per = []
-        for _ in range(reps):
-            events = []
-            for _ in range(steps):
-                reset()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                events.append((e0, e1))
-            torch.cuda.synchronize()
-            per.append(sum(a.elapsed_time(b) for a, b in events) / steps * 1e3)
-        return round(float(np.median(per)), 2), [round(float(np.min(per)), 2), round(float(np.max(per)), 2)]
-
-    rows = []
-    for R in SIZES:
-        q, qd, u = (torch.from_numpy(np.tile(x, (R // STATES, 1))).to(dev) for x in (q0, qd0, u0))
-        qs, qds = q.clone(), qd.clone()
-
-        def reset():
-            qs.copy_(q)
-            qds.copy_(qd)
-
-        row = {"robots": R}
-        status = torch.zeros(R, dtype=torch.int32, device=dev)
-        stop = torch.empty_like(q)
-        sph = torch.from_numpy(spheres).to(dev)
-
-        def call(tab, lists=None):
-            eng.dynamics_step(qs, qds, u, DT, substeps=SUBSTEPS, tau_limit=effort, q_limits=(lo, hi), stop_out=stop,
-                              status_out=status, contacts=tab, d_act=D_ACT, **({} if lists is None else {"contact_lists": lists}))
-
-        def final(tab, lists=None):
-            reset()
-            call(tab, lists)
-            torch.cuda.synchronize()
-            return qs.clone(), status.clone()
-
-        if what == "shared":
-            row["shared_us"], row["shared_us_min_max"] = timed(lambda: call(sph), reset)
-        else:
-            off = torch.arange(R + 1, dtype=torch.int32, device=dev) * SPHERES
-            same = torch.arange(SPHERES, dtype=torch.int32, device=dev).repeat(R)
-            own = torch.arange(R * SPHERES, dtype=torch.int32, device=dev)
-            pool = sph.repeat(R, 1).contiguous()
-            row["lists_same_us"], row["lists_same_us_min_max"] = timed(lambda: call(sph, (off, same)), reset)
-            row["lists_own_us"], row["lists_own_us_min_max"] = timed(lambda: call(pool, (off, own)), reset)
-            qa, sa = final(sph)
-            qb, sb = final(sph, (off, same))
-            qc, sc = final(pool, (off, own))
-            row["same_results"] = bool(torch.equal(qa.view(torch.int32), qb.view(torch.int32)) and torch.equal(sa, sb)
-                                       and torch.equal(qa.view(torch.int32), qc.view(torch.int32)) and torch.equal(sa, sc))
-            st = sa.cpu().numpy()
-            row["contact_fraction"] = round(float((st & 4 != 0).mean()), 4)
-            row["list_invalid"] = int(((sb | sc).cpu().numpy() & 16 != 0).sum())
-            row["pool_bytes_own"] = int(pool.numel() * 4)
-        rows.append(row)
-    return rows
+    off = torch.arange(c.R + 1, dtype=torch.int32, device=c.dev) * T.SPHERES
+    if own:
+        idx, pool = torch.arange(c.R * T.SPHERES, dtype=torch.int32, device=c.dev), c.spheres.repeat(c.R, 1).contiguous()
+        c.row["pool_bytes_own"] = int(pool.numel() * 4)
+    else:
+        idx, pool = torch.arange(T.SPHERES, dtype=torch.int32, device=c.dev).repeat(c.R), c.spheres
+    key = "lists_own" if own else "lists_same"
+    c.time(key + "_us", lambda: call(c, pool, (off, idx)))
+    c.final(key + "_bits", lambda: call(c, pool, (off, idx)))
+    c.row[key + "_invalid"] = int((c.status.cpu().numpy() & 16 != 0).sum())
 
 
-if child is not None:
-    print(json.dumps(measure(child)))
-    sys.exit(0)
-
-result = {"tool": "contacts_lists_timing", "robot": "panda", "drive": "accel", "tau_limit": "urdf effort", "steps_per_repeat": steps,
-          "repeats": reps, "substeps": SUBSTEPS, "dt": DT, "spheres": SPHERES, "d_act": D_ACT, "parent_lib": bool(parent_lib),
-          "sizes": [{"robots": R} for R in SIZES]}
-runs = {"parent": [], "this": []}
-for _ in range(rounds if parent_lib else 1):
-    if parent_lib:
-        runs["parent"].append(run_child("shared", parent_lib))
-    runs["this"].append(run_child("shared"))
-lists = run_child("lists")
-for i, row in enumerate(result["sizes"]):
-    for who in ("parent", "this"):
-        if runs[who]:
-            row[f"{who}_us"] = [r[i]["shared_us"] for r in runs[who]]
-            row[f"{who}_us_min_max"] = [min(r[i]["shared_us_min_max"][0] for r in runs[who]),
-                                        max(r[i]["shared_us_min_max"][1] for r in runs[who])]
-    row["shared_us"] = sorted(row["this_us"])[len(row["this_us"]) // 2]
-    row.update({k: v for k, v in lists[i].items() if k != "robots"})
+result = T.main(__file__, "contacts_lists_timing",
+                {"shared": shared, "lists_same": lambda c: lists(c, False), "lists_own": lambda c: lists(c, True)}, __doc__)
+for row in result["sizes"]:
+    row["same_results"] = row["shared_bits"] == row["lists_same_bits"] == row["lists_own_bits"]
     row["b_over_a"] = round(row["lists_same_us"] / row["shared_us"], 3)
     row["c_over_b"] = round(row["lists_own_us"] / row["lists_same_us"], 3)
-    if parent_lib:
-        row["a_inside_parent_spread"] = bool(row["parent_us_min_max"][0] <= row["shared_us"] <= row["parent_us_min_max"][1])
 print(json.dumps(result))
