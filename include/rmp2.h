@@ -217,7 +217,13 @@ typedef struct rmp2_obstacles {
 } rmp2_obstacles;
 
 /* ---- outputs ----------------------------------------------------------------------- */
-#define RMP2_STATUS_NONFINITE 1u /* qdd contains NaN/Inf (e.g. JointVelocityCap pole, quirk Q4).  A robot fed a NaN / Inf in q or qd
+#define RMP2_STATUS_NONFINITE 1u /* qdd contains NaN/Inf.  A FINITE state reaches two poles of the reference: JointVelocityCap's (quirk
+                                  * Q4: a joint with |qd| == (max_velocity - velocity_damping_region) - velocity_damping_region in
+                                  * fp32, where the metric is w / (1 - 1)), and a distance leaf's control point ON its obstacle's
+                                  * surface or centre (the curvature term of the distance map divides by the surface distance, the
+                                  * normal by the distance to the centre).  Such a robot's SYSTEM is non-finite, and it resolves to
+                                  * NaN on EVERY joint with this bit, in every mapping and both resolves
+                                  * (tests/test_gpu_leaf_edges.py).  A robot fed a NaN / Inf in q or qd
                                   * resolves to NaN on EVERY joint with this bit: the non-finite dof's force is made non-finite by
                                   * construction, so that neither the culling (an out-of-range pair -- metric 0, acceleration NaN in
                                   * the reference: 0 * NaN -- is never evaluated here) nor a set that never reads the joint can return

@@ -248,7 +248,10 @@ class TaskmapJointFrame4x4ToDistance:
         pos_joint = T[:, :3, 3]
         rel = (self.pos_on_link - pos_joint).detach()  # tf.stop_gradient
         crit = pos_joint + rel
-        return torch.linalg.norm(crit - self.pos_on_obs, dim=-1)[:, None]
+        # tf.norm is sqrt(reduce_sum(x * x)), and so is its gradient: inf * 0 = NaN for a control point ON its obstacle point (a pole of
+        # the reference: J, xd and c of the pair are NaN).  torch.linalg.norm answers the subgradient 0 there, a finite system.
+        diff = crit - self.pos_on_obs
+        return torch.sqrt((diff * diff).sum(dim=-1))[:, None]
 
     def differentiate(self, q, qd):
         B = self.pos_on_link.shape[0]

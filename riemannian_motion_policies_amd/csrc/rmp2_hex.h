@@ -886,7 +886,7 @@ rmp2_step_hex_kernel(const uint4* __restrict__ blob, int blob16, QuadHdr hdr, co
         float mdiag, acc;
         if (kind == RMP2_LEAF_JOINT_DAMPING) {  // rmp2.py:127-137
           const float s2 = hex_sum(qdi * qdi);
-          const float nrm = s2 > 0.f ? s2 * rsq1(s2) : 0.f;
+          const float nrm = norm_from_square(s2);
           mdiag = P[1] * nrm + P[2];
           acc = -(P[0] * nrm) * qdi;
         } else if (kind == RMP2_LEAF_CSPACE_BIASING) {  // rmp2.py:212-226
@@ -933,7 +933,7 @@ rmp2_step_hex_kernel(const uint4* __restrict__ blob, int blob16, QuadHdr hdr, co
           const float zraw = row_ok ? qdi * iqd_max : 0.f;
           const float s2 = hex_sum(zraw * zraw);
           xdd_i = -P[0] * qi_ - P[1] * qdi;
-          const float nrm = s2 > 0.f ? s2 * rsq1(s2) : 0.f;
+          const float nrm = norm_from_square(s2);
           // soft norm h = |v| + (1/c) log(1 + exp(-2 c |v|)), c = 5   (helper/rmp_helper.py:62-65)
           const float hh = nrm + 0.2f * (0.693147182464599609375f * __builtin_amdgcn_logf(1.0f + exp1(-10.0f * nrm)));
           zeta_i = zraw * rcp1(hh);

@@ -95,6 +95,17 @@ __device__ __forceinline__ float rsq1(float x) {  // 1/sqrt(x), one Newton step 
   const float e = fmaf(-x * r, r, 1.0f);
   return fmaf(0.5f * e, r, r);
 }
+// |v| from s2 = |v|^2 >= 0.  v_rsq_f32 takes a DENORMAL s2 for 0 and answers inf, and the Newton step of rsq1 then forms inf - inf: a
+// joint creeping at 1e-20 rad/s on a robot otherwise at rest (s2 = 1e-40) made every joint of the robot NaN, where sqrtf -- the
+// lane-per-robot kernel, the reference -- gives 1e-20.  Such an s2 is scaled into the normal range by an exact power of two first
+// (tests/test_gpu_leaf_edges.py, the JointDamping fleet's rows at 1e-20).  This relies on the kernels' float mode keeping fp32
+// denormals (the default of these builds: v_mul_f32 then takes and gives them); with denormals flushed s2 would be 0 before it gets here.
+__device__ __forceinline__ float norm_from_square(float s2) {
+  const bool tiny = s2 < 0x1p-100f;
+  const float ss = tiny ? s2 * 0x1p+64f : s2;
+  const float n = ss > 0.f ? ss * rsq1(ss) : 0.f;
+  return tiny ? n * 0x1p-32f : n;
+}
 __device__ __forceinline__ float rcp0(float x) { return __builtin_amdgcn_rcpf(x); }   // 1 ulp
 __device__ __forceinline__ float rsq0(float x) { return __builtin_amdgcn_rsqf(x); }   // 1 ulp
 // |v| and 1 / |v| from d2 = |v|^2 where the norm goes into a CANCELLATION: x = |p - c| - r at millimetre clearances is 1e-3 of |p - c|,
@@ -185,7 +196,7 @@ __device__ __forceinline__ void target_attractor_fast(const float* P, const floa
 #pragma unroll
   for (int i = 0; i < 3; ++i) delta[i] = g[i] - x[i];
   const float d2 = delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2];
-  const float dn = d2 > 0.f ? d2 * rsq1(d2) : 0.f;
+  const float dn = norm_from_square(d2);
   const float isoft = rcp1(fmaxf(dn, eps / 10.0f));
   const float ipe = rcp1(dn + eps);
 #pragma unroll
@@ -1600,7 +1611,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
             float s2 = 0.f;
   #pragma unroll
             for (int j = 0; j < N; ++j) s2 += my_qd[j] * my_qd[j];
-            nrm = s2 > 0.f ? s2 * rsq1(s2) : 0.f;
+            nrm = norm_from_square(s2);
             mdiag = P[1] * nrm + P[2];
           } else if (lf.kind == RMP2_LEAF_CSPACE_BIASING) {  // rmp2.py:212-226
             float s2 = 0.f;
@@ -1705,7 +1716,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
               xdd_o[m] = -P[0] * qj - P[1] * qdj;
             }
             s2 = quad_sum(s2);
-            const float nrm = s2 > 0.f ? s2 * rsq1(s2) : 0.f;
+            const float nrm = norm_from_square(s2);
             // soft norm h = |v| + (1/c) log(1 + exp(-2 c |v|)), c = 5   (helper/rmp_helper.py:62-65)
             const float hh = nrm + 0.2f * (0.693147182464599609375f * __builtin_amdgcn_logf(1.0f + exp1(-10.0f * nrm)));
             const float ihh = rcp1(hh);
@@ -1824,7 +1835,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
         float s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < N; ++j) s2 += my_qd[j] * my_qd[j];
-        const float nrm = s2 > 0.f ? s2 * rsq1(s2) : 0.f;
+        const float nrm = norm_from_square(s2);
         const float mdiag = P[1] * nrm + P[2];
 #pragma unroll
         for (int m = 0; m < ROWS; ++m) {
