@@ -71,6 +71,11 @@ __device__ __forceinline__ double dppd(double v) {
   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
   return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
 }
+// "Defined, value immaterial" without an instruction: closes the live range of a value that is formed on some paths only and read on
+// those paths only.  (Left undefined, the compiler fills the register with 0 on the other paths: a v_mov_b32 each.)
+__device__ __forceinline__ void undefined3(float v[3]) {
+  asm volatile("" : "=v"(v[0]), "=v"(v[1]), "=v"(v[2]));
+}
 template <int S>
 __device__ __forceinline__ float bcast(float v) {
   return dpp<S * 0x55>(v);
@@ -78,6 +83,35 @@ __device__ __forceinline__ float bcast(float v) {
 template <int S>
 __device__ __forceinline__ double bcastd(double v) {
   return dppd<S * 0x55>(v);
+}
+// u . c[lane S of my quad]: the broadcast rides as the DPP operand of the multiply AND of the two multiply-adds, three
+// instructions.  (Written as `dot3(u, bcast<S>(c))` the compiler folds the broadcast into the multiply only -- the v_fmac's
+// destination is tied, its DPP combiner passes -- and emits a v_mov_b32_dpp for each of the other two components.)
+// The rounding sequence is the one the compiler's contraction gives dot3: fma(u2, c2, fma(u0, c0, u1 * c1)).
+// Hazard: a VGPR written by a VALU instruction must not be read through DPP within the next two wait states, and the
+// compiler's hazard recogniser does not look into an asm string: every use starts with its own `s_nop 1` (not a vector
+// instruction: the SIMD's other waves issue through it), and c is not written inside the string.  That `s_nop 1` covers THIS
+// hazard only.  The other one of DPP on gfx9 -- five wait states between a VALU write of EXEC (v_cmpx) and a DPP read -- is not
+// covered by the string: it does not arise because the compiler emits no v_cmpx for this target and every branch around the
+// uses is scalar (wave-uniform anc_mask tests); a use under a divergent, VALU-written EXEC would need `s_nop 4`.  A disabled
+// source lane (partial wave) reads as 0 (bound_ctrl), as through dpp<>.
+template <int S>
+__device__ __forceinline__ float dot3_bcast(const float u[3], const float c[3]) {
+  static_assert(S >= 0 && S < kQuad, "a lane of the quad");
+  float t;
+#define RMP2_DOT3_BCAST(QP)                                                                       \
+  asm("s_nop 1\n\t"                                                                               \
+      "v_mul_f32_dpp %0, %2, %5 quad_perm:" QP " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"     \
+      "v_fmac_f32_dpp %0, %1, %4 quad_perm:" QP " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"    \
+      "v_fmac_f32_dpp %0, %3, %6 quad_perm:" QP " row_mask:0xf bank_mask:0xf bound_ctrl:1"        \
+      : "=&v"(t)                                                                                  \
+      : "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(u[0]), "v"(u[1]), "v"(u[2]))
+  if constexpr (S == 0) RMP2_DOT3_BCAST("[0,0,0,0]");
+  else if constexpr (S == 1) RMP2_DOT3_BCAST("[1,1,1,1]");
+  else if constexpr (S == 2) RMP2_DOT3_BCAST("[2,2,2,2]");
+  else RMP2_DOT3_BCAST("[3,3,3,3]");
+#undef RMP2_DOT3_BCAST
+  return t;
 }
 __device__ __forceinline__ float quad_sum(float v) {
   v += dpp<kXor1>(v);
@@ -1330,6 +1364,11 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   // 3..9-dof template, which dispatch_solve never gives them (measured: the two wave-uniform branches per leaf frame and the
   // longer live ranges cost the headline kernel 2.5 %)
   constexpr bool kRank1 = FLAVOR != kPlainStep || N == 2;
+  // the pull-back of the FK leaves as one wave-uniform region per row block, its ladder on DPP operands (see there): the four-wave builds
+  // of the nine-dof template, which are bound by vector issue.  The two- and three-wave builds are bound by a wave's own dependent chain
+  // and LOSE with it (config 5: 28.24 -> 29.29 us, config 3l: 76.11 -> 76.91; profiles/quad_pullback_ab.txt); they keep the older form,
+  // and so do the attached-point builds (two waves at most) and the two-dof template (see there)
+  constexpr bool kRegionPullback = N == 9 && MINW >= 4 && !PT;
   const RolloutArgs ro = PLAIN ? RolloutArgs{1, 0, 0.f, nullptr, nullptr, 0} : ro_arg;
 #ifdef RMP2_STAMPS
   if (LEAN) out.M = nullptr;  // (diagnostic build: the stamps travel behind the f rows, so the plain build keeps that pointer)
@@ -2188,7 +2227,10 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
       float mycol[ROWS][3];
       if (MINW >= 4) {  // (as for the walk's state: an undefined value at loop entry is closed with the previous frame's columns,
 #pragma unroll       //  nine registers live through the pair loop; the 256-register build has them to spare)
-        for (int m = 0; m < ROWS; ++m) mycol[m][0] = mycol[m][1] = mycol[m][2] = 0.f;
+        for (int m = 0; m < ROWS; ++m) {
+          if constexpr (kRegionPullback) undefined3(mycol[m]);
+          else mycol[m][0] = mycol[m][1] = mycol[m][2] = 0.f;
+        }
       }
       for (int li = 0; li < op.leaf_count; ++li) {
         float S[6], h[3];
@@ -2418,8 +2460,12 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
         }
         RMP2_SEG(1);  // target leaf (S, h) / the quad sums of a distance leaf
         if (li == 0) {
-          // the columns of MY rows, z_i x (p - o_i) resp. z_i, from the row-joint records read once per pass; rows
-          // whose dof does not move the frame get a zero column, so everything below is branch-free
+          // the columns of MY rows, z_i x (p - o_i) resp. z_i, from the row-joint records read once per pass; inside a row block
+          // that is formed, a row whose dof does not move the frame gets a zero column (no per-lane branch below).
+          // INVARIANT of the kRegionPullback builds: mycol[m] of a row block NONE of whose dofs moves the frame is not formed at all --
+          // it holds whatever the registers held (undefined3), possibly NaN bits.  Every reader must re-test anc_mask first: the region
+          // loop skips a block whose four bits are 0, and column j is read (by any lane, through DPP) only where bit j is set, which
+          // implies that block j >> 2 was formed.  The other builds zero such a block instead.
           if (!kRowRecsInRegs && kBatchedRowRecs) {
             // (the 128-register build re-reads the row-joint records per frame: ALL rows' records first, one LDS round trip -- inside
             //  the per-row branches below every read sits in its own basic block with its own wait; a row block that does not move
@@ -2433,9 +2479,15 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
           }
 #pragma unroll
           for (int m = 0; m < ROWS; ++m) {
-            if (MINW >= 2 && ((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) {  // wave-uniform: no dof of this row block moves
-              mycol[m][0] = mycol[m][1] = mycol[m][2] = 0.f;                 // the frame (nor is its record used)
-              continue;
+            if constexpr (!kRegionPullback) {
+              if (MINW >= 2 && ((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) {  // wave-uniform: no dof of this row block moves
+                mycol[m][0] = mycol[m][1] = mycol[m][2] = 0.f;                 // the frame (nor is its record used)
+                continue;
+              }
+            } else {
+              // wave-uniform: no dof of this row block moves the frame -- neither its record nor its column is read then
+              undefined3(mycol[m]);
+              if (MINW >= 2 && ((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) continue;
             }
             // (bits >= n_dof are never set; bit 16 + j: the frame's origin lies on joint j's axis for every q, its column is
             //  exactly zero in the reference -- rmp2_hip.hip structural_lever_zeros -- and here too, instead of rounding noise)
@@ -2460,59 +2512,98 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
         RankOne r1;
         r1.on = false, r1.tr = 0.f, r1.n[0] = r1.n[1] = r1.n[2] = 0.f;
         if (kRank1 && hdr.rank1) r1 = rank_one_of(S);
-        float u[ROWS][3];
-        float myz[PT ? ROWS : 1][3], tz[PT ? ROWS : 1][3];   // (attached-point leaves: my rows' revolute axes, and Q z_i - c_i x rho)
-        if (PT) {
-#pragma unroll
-          for (int m = 0; m < ROWS; ++m) myz[m][0] = myz[m][1] = myz[m][2] = tz[m][0] = tz[m][1] = tz[m][2] = 0.f;
-        }
-#pragma unroll
-        for (int m = 0; m < ROWS; ++m) {
-          u[m][0] = u[m][1] = u[m][2] = 0.f;
-          if (((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) continue;  // wave-uniform: no row of this block moves the frame
-          if (kRank1 && hdr.rank1) {  // (wave-uniform) sets without an inertia leaf: componentwise accuracy matters there
-            metric_times_column(S, r1, mycol[m], u[m]);
-          } else {
-            u[m][0] = S[0] * mycol[m][0] + S[1] * mycol[m][1] + S[2] * mycol[m][2];
-            u[m][1] = S[1] * mycol[m][0] + S[3] * mycol[m][1] + S[4] * mycol[m][2];
-            u[m][2] = S[2] * mycol[m][0] + S[4] * mycol[m][1] + S[5] * mycol[m][2];
-          }
-          fv[m] += (double)dot3(mycol[m], h);
-          if (PT) {  // attached-point leaf:  A_ij += c_j . (W c_i - rho x z_i) + z_j . (Q z_i - c_i x rho),  f_i += z_i . tau
-            const bool actz = pt_leaf && rjrev[m] && ((op.anc_mask >> (sub + kQuad * m)) & 1u);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) myz[m][c] = actz ? rjz[m][c] : 0.f;
-            float rz[3], cr2[3];
-            cross3(ptRho, myz[m], rz);
-            cross3(mycol[m], ptRho, cr2);
-            u[m][0] -= rz[0], u[m][1] -= rz[1], u[m][2] -= rz[2];
-            tz[m][0] = ptQ[0] * myz[m][0] + ptQ[1] * myz[m][1] + ptQ[2] * myz[m][2] - cr2[0];
-            tz[m][1] = ptQ[1] * myz[m][0] + ptQ[3] * myz[m][1] + ptQ[4] * myz[m][2] - cr2[1];
-            tz[m][2] = ptQ[2] * myz[m][0] + ptQ[4] * myz[m][1] + ptQ[5] * myz[m][2] - cr2[2];
-            fv[m] += (double)dot3(myz[m], ptTau);
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-          if (!((op.anc_mask >> j) & 1u)) continue;  // wave-uniform: dof j does not move this frame (its column is 0)
-          float cj[3];
-#pragma unroll
-          for (int cc = 0; cc < 3; ++cc) {
-            const float v = mycol[j >> 2][cc];
-            cj[cc] = (j & 3) == 0 ? bcast<0>(v) : (j & 3) == 1 ? bcast<1>(v) : (j & 3) == 2 ? bcast<2>(v) : bcast<3>(v);
-          }
-          float zj[3] = {0.f, 0.f, 0.f};
+        if constexpr (!kRegionPullback) {
+          // (the form every build had; see kRegionPullback.  The two-dof template: what its builds make of S col differs from build to
+          //  build -- the two-wave ragged build multiplies c0 S0 first, the four-wave one c1 S1 -- and in the region form the first
+          //  became the second, an ulp on the TwoJoint half of config 5; a one-block ladder has no copies of u to lose)
+          float u[ROWS][3];
+          float myz[PT ? ROWS : 1][3], tz[PT ? ROWS : 1][3];   // (attached-point leaves: my rows' revolute axes, and Q z_i - c_i x rho)
           if (PT) {
 #pragma unroll
-            for (int cc = 0; cc < 3; ++cc) {
-              const float v = myz[j >> 2][cc];
-              zj[cc] = (j & 3) == 0 ? bcast<0>(v) : (j & 3) == 1 ? bcast<1>(v) : (j & 3) == 2 ? bcast<2>(v) : bcast<3>(v);
+            for (int m = 0; m < ROWS; ++m) myz[m][0] = myz[m][1] = myz[m][2] = tz[m][0] = tz[m][1] = tz[m][2] = 0.f;
+          }
+#pragma unroll
+          for (int m = 0; m < ROWS; ++m) {
+            u[m][0] = u[m][1] = u[m][2] = 0.f;
+            if (((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) continue;  // wave-uniform: no row of this block moves the frame
+            if (kRank1 && hdr.rank1) {  // (wave-uniform) sets without an inertia leaf: componentwise accuracy matters there
+              metric_times_column(S, r1, mycol[m], u[m]);
+            } else {
+              u[m][0] = S[0] * mycol[m][0] + S[1] * mycol[m][1] + S[2] * mycol[m][2];
+              u[m][1] = S[1] * mycol[m][0] + S[3] * mycol[m][1] + S[4] * mycol[m][2];
+              u[m][2] = S[2] * mycol[m][0] + S[4] * mycol[m][1] + S[5] * mycol[m][2];
+            }
+            fv[m] += (double)dot3(mycol[m], h);
+            if (PT) {  // attached-point leaf:  A_ij += c_j . (W c_i - rho x z_i) + z_j . (Q z_i - c_i x rho),  f_i += z_i . tau
+              const bool actz = pt_leaf && rjrev[m] && ((op.anc_mask >> (sub + kQuad * m)) & 1u);
+#pragma unroll
+              for (int c = 0; c < 3; ++c) myz[m][c] = actz ? rjz[m][c] : 0.f;
+              float rz[3], cr2[3];
+              cross3(ptRho, myz[m], rz);
+              cross3(mycol[m], ptRho, cr2);
+              u[m][0] -= rz[0], u[m][1] -= rz[1], u[m][2] -= rz[2];
+              tz[m][0] = ptQ[0] * myz[m][0] + ptQ[1] * myz[m][1] + ptQ[2] * myz[m][2] - cr2[0];
+              tz[m][1] = ptQ[1] * myz[m][0] + ptQ[3] * myz[m][1] + ptQ[4] * myz[m][2] - cr2[1];
+              tz[m][2] = ptQ[2] * myz[m][0] + ptQ[4] * myz[m][1] + ptQ[5] * myz[m][2] - cr2[2];
+              fv[m] += (double)dot3(myz[m], ptTau);
             }
           }
 #pragma unroll
-          for (int m = 0; m < ROWS; ++m)
-            if (kQuad * m <= j)  // (a row block without ancestors adds exact zeros)
-              A[m][j] += (double)(PT ? dot3(u[m], cj) + dot3(tz[m], zj) : dot3(u[m], cj));
+          for (int j = 0; j < N; ++j) {
+            if (!((op.anc_mask >> j) & 1u)) continue;  // wave-uniform: dof j does not move this frame (its column is 0)
+            float cj[3];
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) {
+              const float v = mycol[j >> 2][cc];
+              cj[cc] = (j & 3) == 0 ? bcast<0>(v) : (j & 3) == 1 ? bcast<1>(v) : (j & 3) == 2 ? bcast<2>(v) : bcast<3>(v);
+            }
+            float zj[3] = {0.f, 0.f, 0.f};
+            if (PT) {
+#pragma unroll
+              for (int cc = 0; cc < 3; ++cc) {
+                const float v = myz[j >> 2][cc];
+                zj[cc] = (j & 3) == 0 ? bcast<0>(v) : (j & 3) == 1 ? bcast<1>(v) : (j & 3) == 2 ? bcast<2>(v) : bcast<3>(v);
+              }
+            }
+#pragma unroll
+            for (int m = 0; m < ROWS; ++m)
+              if (kQuad * m <= j)  // (a row block without ancestors adds exact zeros)
+                A[m][j] += (double)(PT ? dot3(u[m], cj) + dot3(tz[m], zj) : dot3(u[m], cj));
+          }
+        } else {
+          // One wave-uniform region per row block: u = S col_i, f_i and the block's ladder entries are formed and consumed inside
+          // it, every value defined once.  (Formed as "zero, overwrite behind the anc_mask test, use in a column loop behind all
+          // row blocks" the three u lived in two register sets with nine copies per pull-back between them.)  A row block none
+          // of whose dofs moves the frame is skipped whole: its entries were 0 . c_j, an exact zero for every finite column.  (The
+          // one difference from the older form: that 0 . c_j carried a NaN or Inf of c_j into A[m][j].  A column is non-finite
+          // only on a robot whose state already is, and such a robot is resolved to NaN with the NONFINITE status whatever A holds.)
+          // S col and col . h stay the expressions they were, contracted by the compiler: it does not give them ONE sequence -- the
+          // fast pass of the headline build multiplies c1 first in every row block, its careful pass c0 first in row blocks 0 and 1
+          // and c1 first in block 2 -- and this shape keeps each of those choices (compared byte for byte, profiles/quad_pullback_ab.txt).
+#pragma unroll
+          for (int m = 0; m < ROWS; ++m) {
+            if (((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) continue;  // wave-uniform: no row of this block moves the frame
+            float u[3];
+            if (kRank1 && hdr.rank1) {  // (wave-uniform) sets without an inertia leaf: componentwise accuracy matters there
+              metric_times_column(S, r1, mycol[m], u);
+            } else {
+              u[0] = S[0] * mycol[m][0] + S[1] * mycol[m][1] + S[2] * mycol[m][2];
+              u[1] = S[1] * mycol[m][0] + S[3] * mycol[m][1] + S[4] * mycol[m][2];
+              u[2] = S[2] * mycol[m][0] + S[4] * mycol[m][1] + S[5] * mycol[m][2];
+            }
+            fv[m] += (double)dot3(mycol[m], h);
+#pragma unroll
+            for (int j = kQuad * m; j < N; ++j) {
+              if (!((op.anc_mask >> j) & 1u)) continue;  // wave-uniform: dof j does not move this frame (its column is 0)
+              const float* cj = mycol[j >> 2];           // (column j lives in lane j & 3 as its local row j >> 2)
+              float e;
+              if ((j & 3) == 0) e = dot3_bcast<0>(u, cj);
+              else if ((j & 3) == 1) e = dot3_bcast<1>(u, cj);
+              else if ((j & 3) == 2) e = dot3_bcast<2>(u, cj);
+              else e = dot3_bcast<3>(u, cj);
+              A[m][j] += (double)e;
+            }
+          }
         }
         RMP2_SEG(4);  // pull-back
       }
