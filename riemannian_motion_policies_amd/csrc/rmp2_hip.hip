@@ -2164,7 +2164,8 @@ int dispatch_solve(const rmp2_handle* h, const float* q, const float* qd, const 
       if (out.M || out.f)
         hipLaunchKernelGGL(rmp2_system_copy_kernel, dim3((R + kWave - 1) / kWave), dim3(kWave), 0, s, o2.M, o2.f, out.M, out.f, n, R);
       RMP2_STEP_LAUNCH(h, (rmp2_pinv_kernel<9>), dim3((R + kWave - 1) / kWave), dim3(kWave), 0, s, o2.M, o2.f, out.qdd, out.status, n, R);
-      h->last_kernel = "rmp2_step_quad_kernel up to (M, f) + rmp2_pinv_kernel (one lane per robot, Jacobi pseudo-inverse)";
+      hm->last_kernel_text = "rmp2_step_quad_kernel up to (M, f) + rmp2_pinv_kernel (one lane per robot, Jacobi pseudo-inverse) " + h->quad_build;
+      h->last_kernel = h->last_kernel_text.c_str();  // (the tag: the instantiation the quad half ran, rmp2_host.h quad_build_tag)
       return RMP2_OK;
     }
     return dispatch_slots<N, true>(h, q, qd, goal, gs, o, out, R, s);

@@ -98,7 +98,8 @@ struct rmp2_handle {
   float base_acc[3] = {0.f, 0.f, 9.81f};  // -g
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
   mutable bool quad_id_lean = false;       // the last quad launch ran the structured identity-leaf loop (launch_quad)
-  mutable std::string last_kernel_text;    // last_kernel with that loop named
+  mutable std::string last_kernel_text;    // last_kernel with that loop and the build tag named
+  mutable std::string quad_build;          // template arguments of the last quad launch (quad_build_tag below)
   mutable const char* last_kernel = "none";  // mapping the last control step / rollout was launched with (rmp2_last_kernel)
   std::string error;
 };
@@ -145,6 +146,18 @@ bool launch_quad_pair(const rmp2_handle* ha, const float* qa, const float* qda, 
 // solve = PINV handles whose strict step is ONE quad launch: an inertia leaf (else every robot is rank deficient and would take
 // the careful pass), <= 16 goal floats; symmetric sets are certified from the LDL^T of the elimination, the others from U and
 // the largest multiplier (rmp2_quad.h)
+// The instantiation of rmp2_step_quad_kernel a launch took, as text for rmp2_last_kernel: "[build n9 s1 w4 rollout ragged sym sph]" =
+// N, SLOTS, MINW, ("staged": STAGE,) FLAVOR, OBS, SYM (sym | gen), CAP (sph | cap)(, "pt": PT).  Formed from the template arguments at
+// the launch site, so that a test can tell which build it reached.
+inline std::string quad_build_tag(int n, int slots, int minw, bool stage, bool cap, bool sym, int obs, int flavor, bool pt) {
+  static const char* const kFlavor[] = {"general", "plain", "rollout"};
+  static const char* const kObs[] = {"any", "none", "explicit", "shared", "ragged", "shared-link", "explicit-stream"};
+  // (indexed by OBS + 1: rmp2_quad.h kObsAny = -1, the modes of include/rmp2.h, kObsSharedLink = 4, kObsExplicitStream = 5)
+  static_assert(RMP2_OBS_NONE == 0 && RMP2_OBS_EXPLICIT_PAIRS == 1 && RMP2_OBS_SHARED_SPHERES == 2 && RMP2_OBS_RAGGED_SPHERES == 3 &&
+                    kObsAny == -1 && kObsSharedLink == 4 && kObsExplicitStream == 5, "kObs");
+  return "[build n" + std::to_string(n) + " s" + std::to_string(slots) + " w" + std::to_string(minw) + (stage ? " staged " : " ") +
+         kFlavor[flavor] + " " + kObs[obs + 1] + (sym ? " sym" : " gen") + (cap ? " cap" : " sph") + (pt ? " pt]" : "]");
+}
 inline bool quad_certifies_strict(const rmp2_handle* h) {
   return h->strict && h->strict_certify && !h->likely_singular && h->n_template == 9 && h->goal_floats <= 16;
 }

@@ -70,8 +70,12 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
       bytes += sizeof(float) * (kGldsBuf + kGldsList);  // chunk image + the quads' in-range lists: 8 KiB, 18.4 KB per wave
     }
   }
+  // every launch below goes through RMP2_QUAD_KERNEL: the kernel's name and the build tag come from ONE list of template arguments
+#define RMP2_QUAD_KERNEL(MINW, STAGE, CAP, SYM, OBS, FLAVOR, PT)                                                         \
+  (h->quad_build = quad_build_tag(N, SLOTS, MINW, STAGE, CAP, SYM, OBS, FLAVOR, PT),                                    \
+   rmp2_step_quad_kernel<N, SLOTS, MINW, STAGE, CAP, SYM, OBS, FLAVOR, PT>)
 #define RMP2_QUAD_LAUNCH(MINW, STAGE, CAP, SYM, OBS, FLAVOR)                                                            \
-  RMP2_STEP_LAUNCH(h, (rmp2_step_quad_kernel<N, SLOTS, MINW, STAGE, CAP, SYM, OBS, FLAVOR>), dim3(blocks), dim3(kWave), bytes, s, \
+  RMP2_STEP_LAUNCH(h, (RMP2_QUAD_KERNEL(MINW, STAGE, CAP, SYM, OBS, FLAVOR, false)), dim3(blocks), dim3(kWave), bytes, s, \
                    h->d_prog, hdr, q, qd, goal, gs, og, out, ro, R)
   // the symmetric form (block-upper system through the identity leaves and the elimination) exists for the 3..9-dof
   // template with sphere tables (symk above); everything else takes the general form
@@ -140,7 +144,7 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
       const int lw = h->quad_minw == 2 ? 2 : 3;
 #define RMP2_QUAD_LINK(MINW, CAP, SYM)                                                                                   \
       do {                                                                                                              \
-        auto kern = rmp2_step_quad_kernel<N, SLOTS, MINW, false, CAP, SYM, kObsSharedLink, kPlainStep>;                  \
+        auto kern = RMP2_QUAD_KERNEL(MINW, false, CAP, SYM, kObsSharedLink, kPlainStep, false);                          \
         if (bytes > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); \
         RMP2_STEP_LAUNCH(h, kern, dim3(blocks), dim3(kWave), bytes, s, h->d_prog, hdr, q, qd, goal, gs, o, out, ro, R);  \
       } while (0)
@@ -177,9 +181,9 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
       stream = stream && (h->h_pair_begin[l] % 4) == 0 && h->h_pair_begin[l + 1] - h->h_pair_begin[l] == 32;
     if (stream) {
       lean_flavor();
-      if (symk) RMP2_STEP_LAUNCH(h, (rmp2_step_quad_kernel<N, SLOTS, 4, false, false, true, kObsExplicitStream, kPlainStep>), dim3(blocks),
+      if (symk) RMP2_STEP_LAUNCH(h, (RMP2_QUAD_KERNEL(4, false, false, true, kObsExplicitStream, kPlainStep, false)), dim3(blocks),
                                  dim3(kWave), lds_bytes, s, h->d_prog, hdr, q, qd, goal, gs, o, out, ro, R);
-      else RMP2_STEP_LAUNCH(h, (rmp2_step_quad_kernel<N, SLOTS, 4, false, false, false, kObsExplicitStream, kPlainStep>), dim3(blocks),
+      else RMP2_STEP_LAUNCH(h, (RMP2_QUAD_KERNEL(4, false, false, false, kObsExplicitStream, kPlainStep, false)), dim3(blocks),
                             dim3(kWave), lds_bytes, s, h->d_prog, hdr, q, qd, goal, gs, o, out, ro, R);
       h->last_kernel = quad_certifies_strict(h)
                            ? "rmp2_step_quad_kernel (4 lanes per robot; explicit pairs streamed by LDS-DMA, pair phase before the pull-back; "
@@ -196,9 +200,9 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
     };
 #define RMP2_QUAD_PT(MINW, STAGE, CAP, SYM)                                                                             \
     do {                                                                                                                \
-      raise(reinterpret_cast<const void*>(rmp2_step_quad_kernel<N, SLOTS, MINW, STAGE, CAP, SYM, kObsAny, kGeneral, true>)); \
-      RMP2_STEP_LAUNCH(h, (rmp2_step_quad_kernel<N, SLOTS, MINW, STAGE, CAP, SYM, kObsAny, kGeneral, true>), dim3(blocks), \
-                       dim3(kWave), bytes, s, h->d_prog, hdr, q, qd, goal, gs, o, out, ro, R);                          \
+      auto kern = RMP2_QUAD_KERNEL(MINW, STAGE, CAP, SYM, kObsAny, kGeneral, true);                                     \
+      raise(reinterpret_cast<const void*>(kern));                                                                       \
+      RMP2_STEP_LAUNCH(h, kern, dim3(blocks), dim3(kWave), bytes, s, h->d_prog, hdr, q, qd, goal, gs, o, out, ro, R);   \
     } while (0)
 #define RMP2_QUAD_PT_SYM(MINW, STAGE, CAP)                                                                              \
     do {                                                                                                                \
@@ -225,6 +229,7 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
 #undef RMP2_QUAD_PLAIN_SYM
 #undef RMP2_QUAD_BY_CAP
 #undef RMP2_QUAD_LAUNCH
+#undef RMP2_QUAD_KERNEL
 }
 
 }  // namespace
@@ -234,10 +239,10 @@ void launch_quad(const rmp2_handle* h, const float* q, const float* qd, const fl
 bool RMP2_CAT(launch_quad_n, RMP2_TU_N, _s, RMP2_TU_SLOTS)(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs,
                                                             const ObsArgs& o, const OutArgs& out, const RolloutArgs& ro, int R, hipStream_t s) {
   launch_quad<RMP2_TU_N, RMP2_TU_SLOTS>(h, q, qd, goal, gs, o, out, ro, R, s);
-  if (h->quad_id_lean) {
-    h->last_kernel_text = std::string(h->last_kernel) + " [identity leaves: structured loop, full width]";
-    h->last_kernel = h->last_kernel_text.c_str();
-  }
+  // the name, then the structured identity-leaf loop where the build ran it, then the instantiation (rmp2_host.h quad_build_tag)
+  h->last_kernel_text = std::string(h->last_kernel) + (h->quad_id_lean ? " [identity leaves: structured loop, full width]" : "") + " " +
+                        h->quad_build;
+  h->last_kernel = h->last_kernel_text.c_str();
   return true;
 }
 
