@@ -801,6 +801,43 @@ int rmp2_dynamics_step_contacts_planes(rmp2_handle *h, float *q, float *qd, cons
                                        float *contact_out, float *contact_lambda, int32_t *contact_pair, uint32_t *status_out,
                                        int32_t R, void *stream);
 
+/* ---- capsule obstacles (posts, bars) beside the spheres and the half-spaces ------------------------------------------------------
+ * rmp2_dynamics_step_contacts_capsules is rmp2_dynamics_step_contacts_planes (with or without csr_offset / csr_index) with a table
+ * of capsule obstacles shared by the fleet: obstacle_capsules, device [C][8] fp32 = (a.xyz, radius, b.xyz, 0), 16-byte aligned,
+ * 0 <= C <= RMP2_MAX_OBSTACLE_CAPSULES -- the record of RMP2_PRIM_CAPSULE tables.  There are no per-robot capsule lists.
+ * For each frame f with a link capsule (world segment A, A + D, radius r_f) and each obstacle c = (C_0, r_c, C_1):
+ *     (s, t) = the parameters of the nearest points of the two segments (A, A + D) and (C_0, C_1) -- the clamped 2 x 2 normal
+ *              equations; parallel axes: the link's end s = 0 first --;   Y = C_0 + t (C_1 - C_0);
+ *     from there the pair IS the sphere pair of rmp2_dynamics_step_contacts with centre Y and radius r_c, expression for expression:
+ *     X = the point of the link's segment nearest Y, n = (X - Y) / |X - Y| (+z where they coincide: crossing axes),
+ *     gap g = |X - Y| - r_c - r_f, the row J and the bound b = -max(g, 0) / dt as there.
+ * One row per pair.  A capsule with a == b exactly is the sphere (a, radius).  Capsule rows compete for the RMP2_MAX_CONTACTS slots
+ * with sphere and plane rows by the same rule.  The PAIR INDEX of a capsule row is F K + 2 F P + f C + c (F the robot's frame
+ * count, K the sphere count -- the pool's size in the list form --, P the plane count): after every sphere and plane pair, so that
+ * a tie goes to the earlier kind; at most 32 * 2^24 + 512 + 1024, within int32.  The RMP2_CONTACT_PAIR_CAPSULE_* macros take a
+ * capsule pair apart, RMP2_CONTACT_PAIR_KIND3 tells the three kinds apart.
+ * C == 0 is the planes call;  C == 0 and P == 0 the sphere or list call;  all of K, P, C zero the stops' step.  A non-finite value
+ * anywhere in a capsule record makes every robot's outputs NaN (contact_pair -1), as for spheres and planes.
+ * Limits: one row per pair -- a link lying ALONG a post (parallel axes) is held at one point per substep, the s = 0 end's
+ * nearest point; flat-capped cylinders enter as capsules (urdf.cylinders_as_capsules on the Python side, with its stated bound).
+ * Stream-ordered, no allocation, no read-back: capturable.  Refusals: those of rmp2_dynamics_step_contacts_planes, and C < 0,
+ * C > RMP2_MAX_OBSTACLE_CAPSULES, a null or misaligned capsule table with C > 0: RMP2_ERR_INVALID_ARGUMENT. */
+#define RMP2_MAX_OBSTACLE_CAPSULES 32
+#define RMP2_CONTACT_KIND_CAPSULE 2
+/* contact_pair (>= 0) of a call with C capsules -> kind; frame and record of a CAPSULE pair (the other kinds: the macros above) */
+#define RMP2_CONTACT_PAIR_CAPSULE_BASE(F, K, P) ((int64_t)(F) * (K) + 2 * (int64_t)(F) * (P))
+#define RMP2_CONTACT_PAIR_KIND3(pair, F, K, P) \
+  ((int64_t)(pair) >= RMP2_CONTACT_PAIR_CAPSULE_BASE(F, K, P) ? RMP2_CONTACT_KIND_CAPSULE : RMP2_CONTACT_PAIR_KIND(pair, F, K))
+#define RMP2_CONTACT_PAIR_CAPSULE_FRAME(pair, F, K, P, C) ((int32_t)(((int64_t)(pair) - RMP2_CONTACT_PAIR_CAPSULE_BASE(F, K, P)) / (C)))
+#define RMP2_CONTACT_PAIR_CAPSULE_RECORD(pair, F, K, P, C) ((int32_t)(((int64_t)(pair) - RMP2_CONTACT_PAIR_CAPSULE_BASE(F, K, P)) % (C)))
+int rmp2_dynamics_step_contacts_capsules(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
+                                         const float *q_lower, const float *q_upper, const float *spheres, int32_t K,
+                                         const int32_t *csr_offset, const int32_t *csr_index, const float *planes, int32_t P,
+                                         const float *obstacle_capsules /* device [C][8] */, int32_t C, float d_act, float dt,
+                                         int32_t substeps, float *qdd_out, float *tau_out, float *stop_out, float *contact_out,
+                                         float *contact_lambda, int32_t *contact_pair, uint32_t *status_out, int32_t R,
+                                         void *stream);
+
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,
  * plain steps on shared or ragged sphere tables, both fleets beyond 8 192 robots -- the two steps are ONE grid (the first

@@ -99,6 +99,8 @@ def lib():
             l.rmp2_dynamics_step_contacts_lists.argtypes = head + lists + tail
         if hasattr(l, "rmp2_dynamics_step_contacts_planes"):   # (likewise for a diagnostic RMP2_LIB built before the planes)
             l.rmp2_dynamics_step_contacts_planes.argtypes = head + lists + [C.c_void_p, C.c_int32] + tail
+        if hasattr(l, "rmp2_dynamics_step_contacts_capsules"):   # (likewise for a diagnostic RMP2_LIB built before the capsules)
+            l.rmp2_dynamics_step_contacts_capsules.argtypes = head + lists + [C.c_void_p, C.c_int32] * 2 + tail
     l.rmp2_differentiate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_differentiate_euler.argtypes = l.rmp2_differentiate.argtypes

@@ -36,6 +36,8 @@
 // or none (rmp2_dynamics_step_contacts_planes; NoPlanes / PlaneTable).  All four are dynamics_step_contacts_robot<N, SLOTS, LIST,
 // Pl>, one body with the differences under `if constexpr`, behind ONE kernel, rmp2_dynamics_step_contacts_kernel<N, SLOTS, LIST,
 // PLANES> at the end of this file, which rmp2_contacts_tu.hip instantiates once per form (a code object each).
+// A third switch, capsule obstacles beside both (rmp2_dynamics_step_contacts_capsules; NoCapsules / CapsuleTable), is the same
+// body again with planes and capsules on, behind a kernel of its own (rmp2_dynamics_step_contacts_capsules_kernel<N, SLOTS, LIST>).
 #pragma once
 #include <type_traits>
 
@@ -185,6 +187,20 @@ struct PlaneTable {
   static constexpr bool kOn = true;
 };
 
+// Capsule obstacles beside the spheres and the planes (rmp2_dynamics_step_contacts_capsules), a defaulted template parameter like
+// the planes: with NoCapsules each `if constexpr (Cp::kOn)` is discarded.  CapsuleTable: the fleet's records [C][8] = (a, radius,
+// b, 0), read like the shared sphere table; F and P, the robot's frame count and the call's plane count, place the capsule rows'
+// pair indices after the spheres' and the planes': F K + 2 F P + f C + c.  A capsule pair is the sphere pair (Y, radius), Y the
+// point of the obstacle's axis nearest the link's axis (segment_segment): the sphere trip runs on it, there is no other row code.
+struct NoCapsules {
+  static constexpr bool kOn = false;
+};
+struct CapsuleTable {
+  const float* capsules;
+  int C, F, P;
+  static constexpr bool kOn = true;
+};
+
 // The slot of a qualifying candidate (gap g, pair index idx) among the kept ones: a free slot, or the kept candidate of largest
 // (gap, index) when the new one is smaller, or -1.  The rule of the sphere trip below, which keeps its own inline statement of it
 // (its code is not to change); the plane trip calls this.
@@ -217,11 +233,11 @@ __host__ __device__ inline int contact_slot(float g, int idx, int& count, float 
 // The candidate search and the rows of one robot at q.  caps: [n_frames][8] (a, radius, b, 0) in frame coordinates, read at
 // uniform addresses; src: the robot's spheres (above).  Jr: the rows' storage.  cgap / cidx: gap and pair index per slot (cidx
 // -1: empty).  Returns the number of candidates kept; excess: how many more qualified.
-template <int N, int SLOTS, class Src, class Pl = NoPlanes>
+template <int N, int SLOTS, class Src, class Pl = NoPlanes, class Cp = NoCapsules>
 __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_ops, const float* caps, Src src,
                                                        float d_act, const float (&q)[N], float* Jr, int stride,
                                                        float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess,
-                                                       Pl pl = Pl{}) {
+                                                       Pl pl = Pl{}, Cp oc = Cp{}) {
   const int K = src.count();   // the robot's records (the pair index is made of src.pool())
   float ax[N][3], org[N][3];
 #pragma unroll
@@ -265,7 +281,7 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     const float* cp = caps + (size_t)op.frame * 8;
     bool has = false;
     for (int i = 0; i < 8; ++i) has = has || cp[i] != 0.f;
-    if constexpr (Pl::kOn) {   // (a frame without spheres still meets the planes)
+    if constexpr (Pl::kOn || Cp::kOn) {   // (a frame without spheres still meets the planes and the capsules)
       if (!has) continue;
     } else {
       if (!has || K <= 0) continue;
@@ -316,10 +332,24 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     }
     SphereList::Cursor cursor;
     if constexpr (Src::kList) cursor.begin(src);
-    for (int s = 0; s < K; ++s) {
+    int trips = K;   // with capsules: the robot's K spheres, then the C capsules, through the one trip body
+    if constexpr (Cp::kOn) trips += oc.C;
+    for (int s = 0; s < trips; ++s) {
       float c[3], rs;
       int sk = s;   // the record's index in the pool
-      if constexpr (Src::kList) {
+      bool capsule = false;
+      if constexpr (Cp::kOn) capsule = s >= K;
+      if (capsule) {
+        if constexpr (Cp::kOn) {   // the sphere (Y, radius): Y the point of the obstacle's axis nearest the link's axis
+          const float* rec = oc.capsules + 8 * (size_t)(s - K);
+          const float C0[3] = {rec[0], rec[1], rec[2]}, C1[3] = {rec[4], rec[5], rec[6]};
+          const float B[3] = {A[0] + D[0], A[1] + D[1], A[2] + D[2]};
+          float sl, to;
+          segment_segment(A, B, C0, C1, sl, to);
+          for (int i = 0; i < 3; ++i) c[i] = C0[i] + to * (C1[i] - C0[i]);
+          rs = rec[3];
+        }
+      } else if constexpr (Src::kList) {
         sk = cursor.next(src, s, c, rs);
       } else {
         c[0] = src.spheres[4 * s + 0], c[1] = src.spheres[4 * s + 1], c[2] = src.spheres[4 * s + 2];
@@ -338,7 +368,8 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
       const float g = dn - rs - rf;
       if (!(g <= d_act)) continue;   // (also a NaN gap)
       ++total;
-      const int idx = op.frame * src.pool() + sk;
+      int idx = op.frame * src.pool() + sk;
+      if constexpr (Cp::kOn) idx = capsule ? oc.F * (src.pool() + 2 * oc.P) + op.frame * oc.C + (s - K) : idx;
       int put = -1;
       if (count < kMaxContacts) {
         put = count++;
@@ -636,7 +667,7 @@ __host__ __device__ inline auto contact_source(const float* spheres, int K, cons
 // / pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats.  The spheres are scanned
 // once, before the substeps: a non-finite record makes the robot NaN, an invalid list NaN with the status word
 // RMP2_CONTACT_LIST_INVALID alone (its substeps run on no spheres, and nothing is read through its entries).
-template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes>
+template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes, class Cp = NoCapsules>
 __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, int n_ops, int n_dof, const float* inert,
                                                              const float base_acc[3], float* q_io, float* qd_io,
                                                              const float* u_in, bool accel, const float* lim, const float* qlo,
@@ -644,7 +675,8 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
                                                              float d_act, float dt, int substeps, float* qdd_out, float* tau_out,
                                                              float* stop_out, float* contact_out, float* lambda_out,
                                                              int32_t* pair_out, uint32_t* status_out, float* lds, int stride,
-                                                             const int32_t* list = nullptr, int list_len = 0, Pl pl = Pl{}) {
+                                                             const int32_t* list = nullptr, int list_len = 0, Pl pl = Pl{},
+                                                             Cp oc = Cp{}) {
   auto src = contact_source<LIST>(spheres, K, list, list_len);
   float* Ms = lds;
   float* Jr = Ms + (size_t)fd_tri(N) * stride;
@@ -671,6 +703,9 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
   if constexpr (Pl::kOn) {   // a non-finite plane value: every robot NaN
     for (int s = 0; s < 4 * pl.P; ++s) table_poison += pl.planes[s] * 0.f;
   }
+  if constexpr (Cp::kOn) {   // a non-finite capsule value: every robot NaN
+    for (int s = 0; s < 8 * oc.C; ++s) table_poison += oc.capsules[s] * 0.f;
+  }
   uint32_t status = 0u;
   int most = 0;
   for (int s = 0; s < substeps; ++s) {
@@ -693,7 +728,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
       cont[j] = 0.f;
     }
     int excess = 0;
-    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess, pl);
+    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess, pl, oc);
     if (excess > 0) status |= RMP2_CONTACT_OVERFLOW;
 #pragma unroll
     for (int c = 0; c < kMaxContacts; ++c) lamc[c] = 0.f;
@@ -820,6 +855,44 @@ rmp2_dynamics_step_contacts_kernel(const DevProgram* __restrict__ prog, const fl
       dt, substeps, qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
       contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
       status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, pl);
+}
+
+// The capsule forms (rmp2_dynamics_step_contacts_capsules): the same robot routine with planes AND capsules on, behind a kernel
+// of their own, so that the argument list of the kernel above -- and with it the register allocation of its instantiations -- is
+// what it was.  capsules [C][8] beside the planes; P == 0 and C == 0 run it too.
+template <int N, int SLOTS, bool LIST>
+__global__ void __launch_bounds__(kWave)
+rmp2_dynamics_step_contacts_capsules_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
+                                            float az, float* q, float* qd, const float* __restrict__ u, int accel,
+                                            const float* __restrict__ lim, const float* __restrict__ qlo,
+                                            const float* __restrict__ qhi, const float* __restrict__ caps,
+                                            const float* __restrict__ spheres, int K, const int32_t* __restrict__ csr_offset,
+                                            const int32_t* __restrict__ csr_index, const float* __restrict__ planes, int P,
+                                            const float* __restrict__ capsules, int C, int F, float d_act, float dt, int substeps,
+                                            float* __restrict__ qdd_out, float* __restrict__ tau_out, float* __restrict__ stop_out,
+                                            float* __restrict__ contact_out, float* __restrict__ lambda_out,
+                                            int32_t* __restrict__ pair_out, uint32_t* __restrict__ status_out, int R) {
+  static_assert(contact_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
+  __shared__ float lds[contact_words(N) * kWave];
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const size_t crow = (size_t)robot * kMaxContacts;
+  const float base_acc[3] = {ax, ay, az};
+  const int32_t* list = nullptr;
+  int len = 0;
+  if constexpr (LIST) {
+    int beg;
+    len = contact_list_span(csr_offset, robot, beg);
+    list = csr_index + beg;
+  }
+  dynamics_step_contacts_robot<N, SLOTS, LIST, PlaneTable, CapsuleTable>(
+      prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim, qlo, qhi, caps, spheres, K, d_act,
+      dt, substeps, qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
+      contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
+      status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, PlaneTable{planes, P, F},
+      CapsuleTable{capsules, C, F, P});
 }
 #endif
 

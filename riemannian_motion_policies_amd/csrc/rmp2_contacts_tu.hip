@@ -1,6 +1,8 @@
 // rmp2_contacts_tu.hip -- the instantiations of rmp2_dynamics_step_contacts_kernel (rmp2_contacts.h) of one form and their launcher.
 // Compiled four times, RMP2_TU_LIST = 0 (the shared sphere table) or 1 (per-robot lists over a pool) by RMP2_TU_PLANES = 0 or 1
 // (half-spaces beside the spheres), each a code object of its own: a form's device code does not depend on the others' being there.
+// With RMP2_TU_CAPSULES = 1 (and RMP2_TU_PLANES = 1) the unit holds the capsule forms instead -- planes and capsule obstacles on,
+// rmp2_dynamics_step_contacts_capsules_kernel -- two more code objects, RMP2_TU_LIST = 0 and 1.
 #include <cfloat>
 #include <cmath>
 
@@ -10,9 +12,35 @@
 #if !defined(RMP2_TU_LIST) || !defined(RMP2_TU_PLANES)
 #error "RMP2_TU_LIST and RMP2_TU_PLANES must each be 0 or 1"
 #endif
+#ifndef RMP2_TU_CAPSULES
+#define RMP2_TU_CAPSULES 0
+#endif
+#if RMP2_TU_CAPSULES && !RMP2_TU_PLANES
+#error "the capsule forms run with the planes on"
+#endif
 
 namespace rmp2 {
 
+#if RMP2_TU_CAPSULES
+#if RMP2_TU_LIST
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_capsules) {
+#else
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_capsules) {
+#endif
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  auto launch = [&](auto N) {
+    with_slots(h->n_slots_full, [&](auto S) {
+      hipLaunchKernelGGL((rmp2_dynamics_step_contacts_capsules_kernel<N, S, RMP2_TU_LIST != 0>), grid, block, 0, s, h->d_prog_full,
+                         h->d_inert, a[0], a[1], a[2], q, qd, u, accel, lim, qlo, qhi, h->d_contact_caps, spheres, K, csr_offset,
+                         csr_index, planes, P, capsules, C, h->n_frames, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
+                         lambda_out, pair_out, status_out, R);
+    });
+  };
+  if (h->n_template == 2) launch(std::integral_constant<int, 2>());
+  else launch(std::integral_constant<int, 9>());
+}
+#else
 #if RMP2_TU_LIST && RMP2_TU_PLANES
 RMP2_DECL_CONTACTS(launch_contacts_lists_planes) {
 #elif RMP2_TU_LIST
@@ -36,5 +64,6 @@ RMP2_DECL_CONTACTS(launch_contacts_table) {
   if (h->n_template == 2) launch(std::integral_constant<int, 2>());
   else launch(std::integral_constant<int, 9>());
 }
+#endif
 
 }  // namespace rmp2

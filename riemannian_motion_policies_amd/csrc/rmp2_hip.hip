@@ -2411,22 +2411,28 @@ void launch_dynamics_step_stops(const rmp2_handle* h, float* q, float* qd, const
 // The contact step's launchers (rmp2_contacts_tu.hip; the kernel and its routines are rmp2_contacts.h): [LIST][PLANES]
 constexpr decltype(&launch_contacts_table) kLaunchContacts[2][2] = {{launch_contacts_table, launch_contacts_table_planes},
                                                                     {launch_contacts_lists, launch_contacts_lists_planes}};
+// ... and with capsule obstacles (planes on): [LIST]
+constexpr decltype(&launch_contacts_table_capsules) kLaunchContactsCapsules[2] = {launch_contacts_table_capsules,
+                                                                                  launch_contacts_lists_capsules};
 
-// The host path of the three contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
+// The host path of the four contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
 // each entry point keeps its `what` and its own rules (table: K <= RMP2_MAX_CONTACT_SPHERES; lists: both CSR arrays, the pool
-// aligned; planes: the CSR arrays both set or both null, P and the plane table).  The planes entry always runs a PLANES kernel,
-// P == 0 included.
-enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes };
+// aligned; planes: the CSR arrays both set or both null, P and the plane table; capsules: the planes' rules, C and the capsule
+// table).  The planes entry always runs a PLANES kernel, P == 0 included; the capsules entry always a capsule kernel (planes and
+// capsules on), P == 0 and C == 0 included.
+enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules };
 
 int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float* q, float* qd, const float* u, int32_t drive,
                        const float* tau_limit, const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
-                       const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P, float d_act, float dt,
-                       int32_t substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
-                       int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
+                       const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
+                       const float* capsules, int32_t C, float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out,
+                       float* stop_out, float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
+                       int32_t R, void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   const std::string w = what;
   if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
-  const bool with_planes = form == kContactsPlanes;
+  const bool with_capsules = form == kContactsCapsules;
+  const bool with_planes = form == kContactsPlanes || with_capsules;
   if (with_planes && (csr_offset != nullptr) != (csr_index != nullptr))
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": csr_offset and csr_index go together (both null: the shared table)");
   const bool lists = form == kContactsLists || (with_planes && csr_offset);
@@ -2443,6 +2449,14 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
     if (P > 0 && ((uintptr_t)planes & 15u))
       return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the plane table must be 16-byte aligned");
   }
+  if (with_capsules) {
+    if (C < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": C < 0");
+    if (C > RMP2_MAX_OBSTACLE_CAPSULES)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": C > " + std::to_string(RMP2_MAX_OBSTACLE_CAPSULES));
+    if (C > 0 && !capsules) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null capsule table with C > 0");
+    if (C > 0 && ((uintptr_t)capsules & 15u))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the capsule table must be 16-byte aligned");
+  }
   if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": d_act must be finite and >= 0");
   if (h->contact_n == 0)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
@@ -2455,9 +2469,14 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
   if (int rc = step_rows_check(h, what, q, qd, u, others_ok, R, launch)) return rc;
   if (!launch) return RMP2_OK;
   // (N in {2, 9} by the handle's template size, SLOTS by its program)
-  kLaunchContacts[lists][with_planes](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
-                                      csr_index, planes, P, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
-                                      contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
+  if (with_capsules)
+    kLaunchContactsCapsules[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
+                                   csr_index, planes, P, capsules, C, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
+                                   contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
+  else
+    kLaunchContacts[lists][with_planes](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
+                                        csr_index, planes, P, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
+                                        contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }
@@ -4021,7 +4040,7 @@ int rmp2_dynamics_step_contacts(rmp2_handle* h, float* q, float* qd, const float
                                 int32_t substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,
                                 float* contact_lambda, int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
   return contacts_step_impl(h, "dynamics step with contacts", kContactsTable, q, qd, u, drive, tau_limit, q_lower, q_upper, spheres, K,
-                            nullptr, nullptr, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
+                            nullptr, nullptr, nullptr, 0, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
                             contact_lambda, contact_pair, status_out, R, stream);
 }
 
@@ -4031,7 +4050,7 @@ int rmp2_dynamics_step_contacts_lists(rmp2_handle* h, float* q, float* qd, const
                                       float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
                                       int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
   return contacts_step_impl(h, "dynamics step with contact lists", kContactsLists, q, qd, u, drive, tau_limit, q_lower, q_upper,
-                            spheres, K, csr_offset, csr_index, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                            spheres, K, csr_offset, csr_index, nullptr, 0, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out,
                             contact_out, contact_lambda, contact_pair, status_out, R, stream);
 }
 
@@ -4042,8 +4061,19 @@ int rmp2_dynamics_step_contacts_planes(rmp2_handle* h, float* q, float* qd, cons
                                        float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
                                        int32_t R, void* stream) {
   return contacts_step_impl(h, "dynamics step with contact planes", kContactsPlanes, q, qd, u, drive, tau_limit, q_lower, q_upper,
-                            spheres, K, csr_offset, csr_index, planes, P, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                            spheres, K, csr_offset, csr_index, planes, P, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out,
                             contact_out, contact_lambda, contact_pair, status_out, R, stream);
+}
+
+int rmp2_dynamics_step_contacts_capsules(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
+                                         const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
+                                         const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
+                                         const float* obstacle_capsules, int32_t C, float d_act, float dt, int32_t substeps,
+                                         float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
+                                         int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
+  return contacts_step_impl(h, "dynamics step with contact capsules", kContactsCapsules, q, qd, u, drive, tau_limit, q_lower,
+                            q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps,
+                            qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream);
 }
 
 }  // extern "C"

@@ -188,4 +188,12 @@ RMP2_DECL_CONTACTS(launch_contacts_table);
 RMP2_DECL_CONTACTS(launch_contacts_table_planes);
 RMP2_DECL_CONTACTS(launch_contacts_lists);
 RMP2_DECL_CONTACTS(launch_contacts_lists_planes);
+// the capsule forms (rmp2_dynamics_step_contacts_capsules): planes and capsule obstacles on, [LIST]; two more objects
+#define RMP2_DECL_CONTACTS_CAPSULES(NAME)                                                                                         \
+  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
+            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
+            int P, const float* capsules, int C, float d_act, float dt, int substeps, float* qdd_out, float* tau_out,             \
+            float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_capsules);
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_capsules);
 }  // namespace rmp2

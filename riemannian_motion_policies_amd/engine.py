@@ -13,6 +13,7 @@ import torch
 
 from . import _native
 from . import descriptor as D
+from .urdf import MAX_OBSTACLE_CAPSULES   # include/rmp2.h RMP2_MAX_OBSTACLE_CAPSULES: capsules of dynamics_step(contact_obstacle_capsules=)
 
 MAX_CONTACTS = 8   # include/rmp2.h RMP2_MAX_CONTACTS
 MAX_CONTACT_LIST = 256        # include/rmp2.h RMP2_MAX_CONTACT_LIST: entries per robot of dynamics_step(contact_lists=)
@@ -20,18 +21,23 @@ MAX_CONTACT_POOL = 1 << 24    # include/rmp2.h RMP2_MAX_CONTACT_POOL: records in
 CONTACT_LIST_INVALID = 16     # include/rmp2.h RMP2_CONTACT_LIST_INVALID: status_out of a robot whose list was refused
 MAX_CONTACT_PLANES = 8        # include/rmp2.h RMP2_MAX_CONTACT_PLANES: half-spaces of dynamics_step(contact_planes=)
 CONTACT_KIND_SPHERE, CONTACT_KIND_PLANE = 0, 1
+CONTACT_KIND_CAPSULE = 2
 
 
-def contact_pair_split(pair: int, n_frames: int, K: int, P: int):
+def contact_pair_split(pair: int, n_frames: int, K: int, P: int, C: int = 0):
     """(kind, frame, record, end) of a contact_pair value of dynamics_step (include/rmp2.h RMP2_CONTACT_PAIR_* macros): kind is
-    CONTACT_KIND_SPHERE (record: the sphere's index in the table or pool, end 0) or CONTACT_KIND_PLANE (record: the plane, end: 0
-    or 1, the capsule's end point).  n_frames: the robot's frame count; K, P: the call's sphere and plane counts.  None for an
-    empty slot (-1)."""
+    CONTACT_KIND_SPHERE (record: the sphere's index in the table or pool, end 0), CONTACT_KIND_PLANE (record: the plane, end: 0
+    or 1, the capsule's end point) or CONTACT_KIND_CAPSULE (record: the obstacle capsule, end 0).  n_frames: the robot's frame
+    count; K, P, C: the call's sphere, plane and obstacle-capsule counts.  None for an empty slot (-1)."""
     pair, base = int(pair), int(n_frames) * int(K)
     if pair < 0:
         return None
-    if pair >= base + 2 * int(n_frames) * int(P):
-        raise ValueError(f"contact pair {pair} is outside the range of {n_frames} frames, {K} spheres and {P} planes")
+    cbase = base + 2 * int(n_frames) * int(P)
+    if pair >= cbase + int(n_frames) * int(C):
+        raise ValueError(f"contact pair {pair} is outside the range of {n_frames} frames, {K} spheres and {P} planes"
+                         + (f" and {C} capsules" if C else ""))
+    if pair >= cbase:
+        return CONTACT_KIND_CAPSULE, (pair - cbase) // C, (pair - cbase) % C, 0
     if pair < base:
         return CONTACT_KIND_SPHERE, pair // K, pair % K, 0
     r = pair - base
@@ -644,7 +650,8 @@ class Engine:
                       q_limits=None, stop_out: Optional[torch.Tensor] = None, status_out: Optional[torch.Tensor] = None,
                       contacts: Optional[torch.Tensor] = None, d_act: float = 0.0, contact_out: Optional[torch.Tensor] = None,
                       contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None,
-                      contact_lists=None, contact_planes: Optional[torch.Tensor] = None) -> None:
+                      contact_lists=None, contact_planes: Optional[torch.Tensor] = None,
+                      contact_obstacle_capsules: Optional[torch.Tensor] = None) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
@@ -670,7 +677,13 @@ class Engine:
         n . x >= d; urdf.contact_planes / urdf.floor build them): a floor or walls beside the spheres, with or without contacts=
         and contact_lists= (include/rmp2.h rmp2_dynamics_step_contacts_planes; needs set_contact_capsules).  Every capsule gives
         two rows per plane, one per end point; contact_pair_out holds n_frames * K + 2 * (frame * P + plane) + end for them
-        (contact_pair_split takes a value apart).  Without contact_planes= the call takes the routes above, unchanged."""
+        (contact_pair_split takes a value apart).  Without contact_planes= the call takes the routes above, unchanged.
+        contact_obstacle_capsules = capsule obstacles [C, 8] fp32 = (a, radius, b, 0) on the engine's device (C <=
+        MAX_OBSTACLE_CAPSULES; urdf.capsule_obstacles / urdf.cylinders_as_capsules build them): posts and bars shared by the fleet,
+        with or without contacts=, contact_lists= and contact_planes= (include/rmp2.h rmp2_dynamics_step_contacts_capsules; needs
+        set_contact_capsules, which sets the LINK capsules).  One row per link capsule and obstacle, at the nearest points of the
+        two axes; contact_pair_out holds n_frames * (K + 2 P) + frame * C + capsule for them.  Without it the call takes the
+        routes above, unchanged."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
@@ -689,8 +702,17 @@ class Engine:
                                   or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
 
-        if contacts is not None or contact_planes is not None:
-            P = 0
+        if contacts is not None or contact_planes is not None or contact_obstacle_capsules is not None:
+            P = C = 0
+            if contact_obstacle_capsules is not None:
+                oc = contact_obstacle_capsules
+                _require_resident(self.device, contact_obstacle_capsules=oc)
+                if oc.dim() != 2 or oc.shape[1] != 8 or oc.dtype != torch.float32 or not oc.is_contiguous():
+                    raise ValueError("contact_obstacle_capsules must be a contiguous fp32 [C, 8] tensor (a, radius, b, 0), got "
+                                     f"{list(oc.shape)}")
+                C = int(oc.shape[0])
+                if C > MAX_OBSTACLE_CAPSULES:
+                    raise ValueError(f"contact_obstacle_capsules holds {C} capsules, at most {MAX_OBSTACLE_CAPSULES}")
             if contact_planes is not None:
                 _require_resident(self.device, contact_planes=contact_planes)
                 if (contact_planes.dim() != 2 or contact_planes.shape[1] != 4 or contact_planes.dtype != torch.float32
@@ -732,7 +754,10 @@ class Engine:
             tail = (float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), ptr(stop_out), ptr(contact_out),
                     ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s)
             lists = (ptr(csr_offset), ptr(csr_index))
-            if contact_planes is not None:
+            if contact_obstacle_capsules is not None:
+                rc = self._lib.rmp2_dynamics_step_contacts_capsules(*head, *lists, contact_planes.data_ptr() if P else None, P,
+                                                                    contact_obstacle_capsules.data_ptr() if C else None, C, *tail)
+            elif contact_planes is not None:
                 rc = self._lib.rmp2_dynamics_step_contacts_planes(*head, *lists, contact_planes.data_ptr() if P else None, P, *tail)
             elif contact_lists is not None:
                 rc = self._lib.rmp2_dynamics_step_contacts_lists(*head, *lists, *tail)

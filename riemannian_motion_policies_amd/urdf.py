@@ -460,6 +460,59 @@ def floor(z: float = 0.0) -> np.ndarray:
     return contact_planes([[0.0, 0.0, 1.0, float(z)]])
 
 
+MAX_OBSTACLE_CAPSULES = 32   # include/rmp2.h RMP2_MAX_OBSTACLE_CAPSULES
+
+
+def capsule_obstacles(rows) -> np.ndarray:
+    """Capsule obstacles [C, 8] float32 = (a.xyz, radius, b.xyz, 0) for Engine.dynamics_step(contact_obstacle_capsules=)
+    (include/rmp2.h rmp2_dynamics_step_contacts_capsules) from host rows of 7 or 8 values -- the record of RMP2_PRIM_CAPSULE tables
+    and configs.sample_capsules; the unused eighth word is zeroed.  Refused: a non-finite value, a negative radius, more than
+    MAX_OBSTACLE_CAPSULES rows."""
+    a = np.asarray(rows, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 8), np.float32)
+    if a.ndim != 2 or a.shape[1] not in (7, 8):
+        raise ValueError(f"capsule obstacles must be rows (ax, ay, az, radius, bx, by, bz[, 0]), got shape {list(a.shape)}")
+    if len(a) > MAX_OBSTACLE_CAPSULES:
+        raise ValueError(f"{len(a)} capsule obstacles, at most {MAX_OBSTACLE_CAPSULES}")
+    if not np.isfinite(a[:, :7]).all():
+        raise ValueError("capsule obstacles: a value is not finite")
+    if (a[:, 3] < 0).any():
+        raise ValueError(f"capsule obstacles: row {int(np.argmax(a[:, 3] < 0))} has a negative radius")
+    out = np.zeros((len(a), 8), np.float32)
+    out[:, :7] = a[:, :7]
+    if not np.isfinite(out).all():
+        raise ValueError("capsule obstacles: a value is not finite in float32")
+    return out
+
+
+def cylinders_as_capsules(cylinders, mode: str = "covering") -> np.ndarray:
+    """configs.cylinder_record rows [C, 8] = (centre c, radius r, unit axis u, half-height h) -- the reference's flat-capped
+    cylinders -- as capsule_obstacles records, for the plant's contacts (which know capsules only):
+      "covering":  end points c -+ h u, radius r.  Contains the cylinder; overshoots each cap by at most r (on the axis).
+      "inscribed": end points c -+ max(h - r, 0) u, radius r.  Lies inside the cylinder whenever h >= r; misses the rim by at most
+                   (sqrt 2 - 1) r.
+    The end points are formed in float64 and rounded once."""
+    if mode not in ("covering", "inscribed"):
+        raise ValueError(f"mode must be 'covering' or 'inscribed', got {mode!r}")
+    a = np.asarray(cylinders, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 8), np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"cylinders must be rows (cx, cy, cz, radius, ux, uy, uz, half_height), got shape {list(a.shape)}")
+    if not np.isfinite(a).all():
+        raise ValueError("cylinders: a value is not finite")
+    c, r, u, h = a[:, 0:3], a[:, 3], a[:, 4:7], a[:, 7]
+    if (r < 0).any() or (h < 0).any():
+        raise ValueError("cylinders: a negative radius or half-height")
+    length = np.linalg.norm(u, axis=1)
+    if (length == 0).any():
+        raise ValueError(f"cylinders: row {int(np.argmax(length == 0))} has a zero axis")
+    u = u / length[:, None]
+    reach = h if mode == "covering" else np.maximum(h - r, 0.0)
+    return capsule_obstacles(np.concatenate([c - reach[:, None] * u, r[:, None], c + reach[:, None] * u], axis=1))
+
+
 # ---- convex-hull link geometry (simulation.py:462-484: PyBullet loads each .obj collision mesh as its convex hull) ------------
 
 MAX_HULL_VERTICES = 512   # include/rmp2.h RMP2_MAX_HULL_VERTICES

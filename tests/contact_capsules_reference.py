@@ -1,0 +1,179 @@
+"""fp64 restatement, and fp32 envelope, of the contact step with capsule obstacles beside the spheres and the half-spaces
+(include/rmp2.h rmp2_dynamics_step_contacts_capsules), built on tests/contact_planes_reference.py the way that one is built on
+tests/contacts_reference.py: its sphere and plane rows followed by the capsule rows, its candidate rule, its QP, its landing and
+its brackets.
+
+Capsule rows, per frame f with a non-zero link capsule row (world segment A, A + D, radius r_f) and obstacle c = (C0, r_c, C1):
+    (s, t) = segment_segment(A, A + D, C0, C1)  (rmp2_device.h: the clamped 2 x 2 normal equations, its cases as they are -- both
+             points, either a point, parallel axes s = 0 first, then the re-clamp of s where t left [0, 1]);
+    Y = C0 + t (C1 - C0);   from there contacts_reference.pair_rows' sphere pair on (Y, r_c): X the point of the link's segment
+    nearest Y, n = (X - Y) / |X - Y| (+z where they coincide), g = |X - Y| - r_c - r_f, the row J, b = -max(g, 0) / dt;
+pair index F K + 2 F P + f C + c (F frames, K spheres, P planes), after every sphere and plane pair."""
+from __future__ import annotations
+
+import numpy as np
+
+import contact_planes_reference as PR
+import contacts_reference as CR
+import forward_dynamics_reference as FR
+from riemannian_motion_policies_amd import urdf as U
+
+SPHERE, PLANE, CAPSULE = 0, 1, 2
+_plane_rows = PR.pair_rows
+
+
+def pair_index(F, K, P, C, f, c):
+    return F * K + 2 * F * P + f * C + c
+
+
+def split_pair(pair, F, K, P, C):
+    """(kind, frame, record, end) of a pair index; None for -1."""
+    pair = int(pair)
+    if pair < 0:
+        return None
+    base = F * K + 2 * F * P
+    if pair < base:
+        return PR.split_pair(pair, F, K, P)
+    assert pair < base + F * C, (pair, F, K, P, C)
+    return CAPSULE, (pair - base) // C, (pair - base) % C, 0
+
+
+def segment_segment(p1, q1, p2, q2, dtype=np.float64):
+    """rmp2_device.h segment_segment on arrays [B, 3] in `dtype`: (s, t) [B]."""
+    dtype = np.dtype(dtype)
+    zero, one = dtype.type(0), dtype.type(1)
+    dot = lambda x, y: (x * y).sum(-1, dtype=dtype)
+    clip = lambda x: np.clip(x, zero, one)
+    with np.errstate(all="ignore"):
+        d1, d2, r = (q1 - p1).astype(dtype), (q2 - p2).astype(dtype), (p1 - p2).astype(dtype)
+        d1, d2, r = np.broadcast_arrays(d1, d2, r)
+        a, e, f, c, b = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
+        safe = lambda x: np.where(x > 0, x, one)
+        denom = (a * e - b * b).astype(dtype)
+        s = np.where(denom > 0, clip((b * f - c * e) / safe(denom)), zero).astype(dtype)
+        t = ((b * s + f) / safe(e)).astype(dtype)
+        s = np.where(t < 0, clip(-c / safe(a)), np.where(t > 1, clip((b - c) / safe(a)), s))
+        t = clip(t)
+        # the degenerate cases
+        first, second = ~(a > 0), ~(e > 0)
+        s = np.where(first, zero, np.where(second, clip(-c / safe(a)), s))
+        t = np.where(second, zero, np.where(first, clip(f / safe(e)), t))
+    return s.astype(dtype), t.astype(dtype)
+
+
+def capsule_rows(table, caps, capsules, K, P, q, dtype=np.float64, detail=False):
+    """The capsule rows of a fleet, contacts_reference.pair_rows' dict (idx, gap, J, X, n) in `dtype`; detail: also s, t [B, rows]
+    (segment_segment's parameters) and Y [B, rows, 3]."""
+    dtype = np.dtype(dtype)
+    q = np.atleast_2d(np.asarray(q, dtype))
+    B, n = q.shape
+    caps = np.asarray(caps, dtype)
+    oc = np.asarray(capsules, dtype).reshape(-1, 8)
+    C, F = len(oc), table.n_frames
+    R, p, z = CR.poses(table, q, dtype)
+    zero, one = dtype.type(0), dtype.type(1)
+    idx, gaps, rows, Xs, ns, ss, ts, Ys = [], [], [], [], [], [], [], []
+    for f in CR.capsule_frames(caps):
+        A = FR._mv(R[f], np.broadcast_to(caps[f, 0:3], (B, 3))) + p[f]
+        D = FR._mv(R[f], np.broadcast_to(caps[f, 4:7] - caps[f, 0:3], (B, 3)))
+        dd = (D * D).sum(-1)
+        inv = np.where(dd > 0, one / np.where(dd > 0, dd, one), zero).astype(dtype)
+        anc, g = [], f
+        while g >= 0:
+            jt, j = int(table.joint_type[g]), int(table.q_index[g])
+            if jt != U.JOINT_FIXED and j >= 0:
+                anc.append((j, g, jt))
+            g = int(table.parent[g])
+        for k in range(C):
+            C0, rk, C1 = oc[k, 0:3], oc[k, 3], oc[k, 4:7]
+            with np.errstate(invalid="ignore"):
+                s, t = segment_segment(A, (A + D).astype(dtype), np.broadcast_to(C0, (B, 3)), np.broadcast_to(C1, (B, 3)), dtype)
+                Y = (C0 + t[:, None] * (C1 - C0)).astype(dtype)
+                tl = np.clip(((Y - A) * D).sum(-1) * inv, zero, one)
+                X = A + tl[:, None] * D
+                nv = X - Y
+                dn = np.sqrt((nv * nv).sum(-1))
+                cross = dn == 0
+                nv = np.where(cross[:, None], np.array([0, 0, 1], dtype), nv)
+                nu = nv / np.where(cross, one, dn)[:, None]
+                gap = dn - rk - caps[f, 3]
+            J = np.zeros((B, n), dtype)
+            for (j, gfr, jt) in anc:
+                J[:, j] = (nu * FR._cross(z[gfr], X - p[gfr])).sum(-1) if jt == U.JOINT_REVOLUTE else (nu * z[gfr]).sum(-1)
+            idx.append(pair_index(F, K, P, C, f, k))
+            gaps.append(gap.astype(dtype))
+            rows.append(J)
+            Xs.append(X.astype(dtype))
+            ns.append(nu.astype(dtype))
+            ss.append(s), ts.append(t), Ys.append(Y)
+    if not idx:
+        out = dict(idx=np.zeros(0, int), gap=np.zeros((B, 0), dtype), J=np.zeros((B, 0, n), dtype), X=np.zeros((B, 0, 3), dtype),
+                   n=np.zeros((B, 0, 3), dtype))
+        return dict(out, s=np.zeros((B, 0), dtype), t=np.zeros((B, 0), dtype), Y=np.zeros((B, 0, 3), dtype)) if detail else out
+    out = dict(idx=np.array(idx), gap=np.stack(gaps, 1), J=np.stack(rows, 1), X=np.stack(Xs, 1), n=np.stack(ns, 1))
+    return dict(out, s=np.stack(ss, 1), t=np.stack(ts, 1), Y=np.stack(Ys, 1)) if detail else out
+
+
+def pair_rows(table, caps, spheres, planes, capsules, q, dtype=np.float64):
+    """contact_planes_reference.pair_rows' sphere and plane rows followed by the capsule rows."""
+    sph = np.asarray(spheres, np.float64).reshape(-1, 4)
+    pl = np.asarray(planes, np.float64).reshape(-1, 4)
+    a = _plane_rows(table, caps, sph, pl, q, dtype)
+    b = capsule_rows(table, caps, capsules, len(sph), len(pl), q, dtype)
+    return {k: np.concatenate([a[k], b[k]], 0 if k == "idx" else 1) for k in a}
+
+
+class _rows_with:
+    """Within the block contacts_reference forms its rows with `planes` and `capsules` as well: its substep -- candidates,
+    solve_qp, landing -- runs on the concatenated rows, unchanged."""
+
+    def __init__(self, planes, capsules):
+        self.planes, self.capsules = planes, capsules
+
+    def __enter__(self):
+        self.saved = CR.pair_rows
+        CR.pair_rows = lambda table, caps, spheres, q, dtype=np.float64: pair_rows(table, caps, spheres, self.planes, self.capsules,
+                                                                                   q, dtype)
+
+    def __exit__(self, *exc):
+        CR.pair_rows = self.saved
+
+
+def substep(table, inert, caps, spheres, planes, capsules, d_act, q, qd, u, drive, dt, lim, limits, gravity=(0.0, 0.0, -9.81),
+            envelope=False):
+    """contacts_reference.substep with planes and capsules: the same dict."""
+    with _rows_with(planes, capsules):
+        return CR.substep(table, inert, caps, spheres, d_act, q, qd, u, drive, dt, lim, limits, gravity, envelope)
+
+
+def dynamics_step(table, inert, caps, spheres, planes, capsules, d_act, q, qd, u, drive, dt, substeps, lim, limits,
+                  gravity=(0.0, 0.0, -9.81), envelope=False):
+    """contacts_reference.dynamics_step with planes and capsules: the same dict."""
+    with _rows_with(planes, capsules):
+        return CR.dynamics_step(table, inert, caps, spheres, d_act, q, qd, u, drive, dt, substeps, lim, limits, gravity, envelope)
+
+
+def linearised_gaps(c, got_qd, pair, dt):
+    """contact_planes_reference.linearised_gaps over sphere, plane and capsule pairs."""
+    pr = pair_rows(c["t"], c["caps"], c["spheres"], c["planes"], c["capsules"], c["q"])
+    pos = {int(i): k for k, i in enumerate(pr["idx"])}
+    out, jn = np.full(pair.shape, np.nan), np.zeros(pair.shape)
+    for r in range(len(pair)):
+        for s in range(pair.shape[1]):
+            if pair[r, s] >= 0:
+                k = pos[int(pair[r, s])]
+                out[r, s] = max(pr["gap"][r, k], 0.0) + dt * (pr["J"][r, k] @ np.asarray(got_qd[r], np.float64))
+                jn[r, s] = np.abs(pr["J"][r, k]).sum()
+    return out, jn
+
+
+def write_driver_input(path, c, substeps, dt, d_act, lists=None, **over):
+    """Input file of tests/contact_capsules_driver.cpp: contacts_reference.write_driver_input's (always with a plane section),
+    followed by int32 C, float capsules[C][8].  over: fields of the group replaced."""
+    g = dict(c, **{k: v for k, v in over.items() if v is not None})
+    CR.write_driver_input(path, g["t"], g["inert"], g["caps"], g["spheres"], d_act, g["q"], g["qd"], g["u"], g["drive"], g["lim"],
+                          g["limits"], dt, substeps, g["g"], lists=lists, planes=g["planes"])
+    oc = np.ascontiguousarray(g["capsules"], np.float32).reshape(-1, 8)
+    with open(path, "ab") as f:
+        np.array([len(oc)], np.int32).tofile(f)
+        oc.tofile(f)
