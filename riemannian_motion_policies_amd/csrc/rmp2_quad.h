@@ -1369,6 +1369,12 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   // and LOSE with it (config 5: 28.24 -> 29.29 us, config 3l: 76.11 -> 76.91; profiles/quad_pullback_ab.txt); they keep the older form,
   // and so do the attached-point builds (two waves at most) and the two-dof template (see there)
   constexpr bool kRegionPullback = N == 9 && MINW >= 4 && !PT;
+  // the walk with its fetches ahead of their use: {axis, ctl} two frames ahead, the records in an even / odd rotation (see there).  The
+  // same builds as the region pull-back -- four waves per SIMD, all of them walking at the same moment right after launch --: only
+  // those were timed with it (profiles/quad_walk_ab.txt); every other build keeps the older loop, its listing unchanged.  (The staged
+  // builds read {axis, ctl} from LDS into vector registers: a rotation there costs moves.)  The symmetric form only: config 2 at 65 536
+  // robots -- the general form, one FK leaf behind the walk -- LOST with it, 25.50 -> 25.89 us, every run slower than every parent run.
+  constexpr bool kWalkAhead = N == 9 && MINW >= 4 && !PT && !STAGE && SYM;
   const RolloutArgs ro = PLAIN ? RolloutArgs{1, 0, 0.f, nullptr, nullptr, 0} : ro_arg;
 #ifdef RMP2_STAMPS
   if (LEAN) out.M = nullptr;  // (diagnostic build: the stamps travel behind the f rows, so the plain build keeps that pointer)
@@ -2007,6 +2013,102 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
       nla = lc0[0], nlb = lc0[1];
     }
     int t_leaf = 0;  // (wave-uniform) ordinal of the frame among the leaf-bearing frames: its segment slot
+    if constexpr (kWalkAhead) {
+      // No wait inside a frame, no copy of a record.  {axis, ctl} runs TWO frames ahead: at the top of frame k the control word of
+      // frame k + 1 is in hand, so the joint velocity of frame k + 1 is read together with its record, and everything frame k itself
+      // uses was issued a whole frame earlier -- the one wait of a frame stands at its top.  (One frame ahead, the scalar fetch of
+      // the next {axis, ctl} was still in flight where z * qd needs the LDS read of qd, and scalar loads return out of order: the
+      // wait there was for everything, the fetched-ahead record included, on the kernel's only serial chain.)  The records and joint
+      // velocities live in two register sets, even and odd frames: a frame reads one and fills the other, nothing is copied; the
+      // two {axis, ctl} rotate through scalar registers.  Every index is clamped to the program: the fetches past the last frame
+      // read frame n_ops - 1 again, qd[0] where the frame has no dof.
+      static_assert(!LINKSEG, "link segments: two- and three-wave builds");
+      float4 e0 = n0, e1 = n1, e2 = n2, o0 = n0, o1 = n1, o2 = n2;
+      float4 ac = nac, ac1 = *reinterpret_cast<const float4*>(ops[min(1, n_ops - 1)].axis);
+      float qe = wqd[max(((__float_as_int(ac.w) >> 6) & 31) - 1, 0)], qo = 0.f;
+      auto half = [&](const int k, const float4& r0_, const float4& r1_, const float4& r2_, const float qdv, float4& m0, float4& m1,
+                      float4& m2, float& qn) __attribute__((always_inline)) {
+        const float4 ack = ac;
+        const int ctl = __float_as_int(ack.w), ctl1 = __float_as_int(ac1.w);
+        // the frame's one wait, IN FRONT of the fetches for the next frame: the last LDS read and the scalar load of the previous
+        // frame are "used" here.  (Left to the compiler the wait stands at the first use of the record, behind the new fetches, and
+        // with a scalar load in flight it is a wait for everything -- the new fetches' round trip, every frame.)
+        asm volatile("" ::"v"(qdv), "s"(ctl1) : "memory");
+        const float4* rn = reinterpret_cast<const float4*>(wloc + kSlot * min(k + 1, n_ops - 1));
+        m0 = rn[0];
+        m1 = rn[1];
+        m2 = rn[2];
+        qn = wqd[max(((ctl1 >> 6) & 31) - 1, 0)];
+        ac = ac1;
+        ac1 = *reinterpret_cast<const float4*>(ops[min(k + 2, n_ops - 1)].axis);
+        // (from here on the frame as the loop below has it, expression for expression, less what these builds do not have: link
+        // segments, rotation records, the staged program)
+        const int c_restore = (ctl & 3) - 2, c_save = ((ctl >> 2) & 3) - 1, c_jtype = (ctl >> 4) & 3;
+        const int qi = ((ctl >> 6) & 31) - 1;
+        const float f_rev = (c_jtype == RMP2_JOINT_REVOLUTE && qi >= 0) ? 1.0f : 0.0f;
+        const float f_pri = (c_jtype == RMP2_JOINT_PRISMATIC && qi >= 0) ? 1.0f : 0.0f;
+        const float Rl[9] = {r0_.x, r0_.y, r0_.z, r0_.w, r1_.x, r1_.y, r1_.z, r1_.w, r2_.x};
+        const float tl[3] = {r2_.y, r2_.z, r2_.w};
+        if (c_restore != -1) {
+          if (c_restore == -2) {
+            int sb = sub;
+            asm volatile("" : "+v"(sb));
+#pragma unroll
+            for (int m = 0; m < 3; ++m) cur.R[m] = (m == sb) ? 1.0f : 0.0f;
+            cur.p = cur.w = cur.al = cur.v = cur.a = 0.f;
+          } else if (SLOTS > 0) {
+#pragma unroll
+            for (int s2 = 0; s2 < SLOTS; ++s2)
+              if (c_restore == s2) cur = slot[s2];
+          }
+        }
+        // (the three sums of products with their contraction written out: the loop below leaves it to the compiler, which takes
+        // the first product as the multiply in Rn and pn and the middle one in z; in this loop shape it took the middle one
+        // in all three, and q-double-dot of nearly every robot moved by an ulp)
+        float Rn[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Rn[c] = fmaf(cur.R[2], Rl[6 + c], fmaf(cur.R[1], Rl[3 + c], cur.R[0] * Rl[c]));
+        const float pn = fmaf(cur.R[2], tl[2], fmaf(cur.R[1], tl[1], cur.R[0] * tl[0])) + cur.p;
+        const float rr = pn - cur.p;
+        const float z = fmaf(Rn[2], ack.z, fmaf(Rn[0], ack.x, Rn[1] * ack.y));
+        const float w1 = dpp<kRot1>(cur.w), w2 = dpp<kRot2>(cur.w);
+        const float r1 = dpp<kRot1>(rr), r2 = dpp<kRot2>(rr);
+        const float a1 = dpp<kRot1>(cur.al), a2 = dpp<kRot2>(cur.al);
+        const float t1 = w1 * r2 - w2 * r1;
+        const float t2 = a1 * r2 - a2 * r1;
+        const float t1a = dpp<kRot1>(t1), t1b = dpp<kRot2>(t1);
+        const float t3 = w1 * t1b - w2 * t1a;
+        const float zq = z * qdv;
+        const float zq1 = dpp<kRot1>(zq), zq2 = dpp<kRot2>(zq);
+        const float t4 = w1 * zq2 - w2 * zq1;
+        const float wn = fmaf(f_rev, zq, cur.w), aln = fmaf(f_rev, t4, cur.al);
+        const float vn = fmaf(f_pri, zq, cur.v + t1), an = fmaf(2.0f * f_pri, t4, cur.a + t2 + t3);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cur.R[c] = Rn[c];
+        cur.p = pn;
+        cur.w = wn;
+        cur.al = aln;
+        cur.v = vn;
+        cur.a = an;
+        if (sub < 3) {
+          float* fr = wloc + kSlot * k;
+          fr[sub] = pn;
+          fr[3 + sub] = vn;
+          fr[6 + sub] = an;
+          fr[9 + sub] = z;
+        }
+        if (SLOTS > 0 && c_save >= 0) {
+#pragma unroll
+          for (int s2 = 0; s2 < SLOTS; ++s2)
+            if (c_save == s2) slot[s2] = cur;
+        }
+      };
+      for (int k = 0; k < n_ops; k += 2) {
+        half(k, e0, e1, e2, qe, o0, o1, o2, qo);
+        if (k + 1 >= n_ops) break;
+        half(k + 1, o0, o1, o2, qo, e0, e1, e2, qe);
+      }
+    } else {
     for (int k = 0; k < n_ops; ++k) {
       const float4 r0_ = n0, r1_ = n1, r2_ = n2, ac = nac;
       const float4 la4 = nla, lb4 = nlb;
@@ -2104,6 +2206,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
           if (c_save == s2) slot[s2] = cur;
       }
       if (LINKSEG) t_leaf += (ctl >> 11) & 1;  // (the frame carries leaves: the next leaf-bearing frame takes the next slot)
+    }
     }
   }
   RMP2_STAMP();  // 2: walk done
