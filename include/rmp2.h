@@ -714,8 +714,8 @@ int rmp2_dynamics_step_stops(rmp2_handle *h, float *q, float *qd, const float *u
  * rmp2_dynamics_step's.  K == 0 is the stops call.  The block above's edge behaviour holds; a non-finite sphere record makes
  * every robot's outputs NaN.  Stream-ordered, no allocation, capturable.  Refusals as for the stops call (q_lower and q_upper
  * both given or both NULL), and: no capsules set, K < 0, K > 256, a null table with K > 0, d_act not finite or < 0; a robot
- * of more than 9 dofs: RMP2_ERR_UNSUPPORTED.  Friction, restitution, penetration recovery, self contacts and moving obstacles
- * are not modelled; parity with PyBullet's solver is UNPINNED, as for the rest of the plant. */
+ * of more than 9 dofs: RMP2_ERR_UNSUPPORTED.  Friction, restitution, penetration recovery and moving obstacles are not
+ * modelled (self contacts between the robot's own link capsules: rmp2_dynamics_step_contacts_self below); parity with PyBullet's solver is UNPINNED, as for the rest of the plant. */
 #define RMP2_MAX_CONTACTS 8
 #define RMP2_MAX_CONTACT_SPHERES 256
 #define RMP2_CONTACT_ACTIVE 4u     /* some contact carried force in some substep */
@@ -837,6 +837,49 @@ int rmp2_dynamics_step_contacts_capsules(rmp2_handle *h, float *q, float *qd, co
                                          int32_t substeps, float *qdd_out, float *tau_out, float *stop_out, float *contact_out,
                                          float *contact_lambda, int32_t *contact_pair, uint32_t *status_out, int32_t R,
                                          void *stream);
+
+/* ---- self contacts: the robot's own link capsules against each other -----------------------------------------------------------
+ * rmp2_set_contact_self_pairs holds a list of unordered frame pairs {i, j} on the handle (host int32 [n_pairs][2]; n_pairs == 0:
+ * self contacts off), like the link capsules of rmp2_set_contact_capsules and in any order against it; synchronous.
+ * rmp2_dynamics_step_contacts_self is rmp2_dynamics_step_contacts_capsules -- its argument list, its refusals -- with one more
+ * kind of row, one per pair.  Write anc(x) for the set of dofs that move frame x.  Of a pair the frame that the handle's full
+ * program visits LATER (op order) is the link f, the other the partner e.  With the world segments (A_f, A_f + D_f, r_f) and
+ * (A_e, A_e + D_e, r_e) of the two link capsules the pair IS the capsule pair above, expression for expression, the partner's
+ * segment standing where the obstacle (C_0, C_1, r_c) stood:
+ *     (s, t) = segment_segment(A_f, A_f + D_f, A_e, A_e + D_e);   Y = A_e + t D_e (formed from the segment's two ends);
+ *     X = the point of f's segment nearest Y;   n = (X - Y) / |X - Y| (+z where they coincide);   g = |X - Y| - r_e - r_f;
+ *     b = -max(g, 0) / dt;   a candidate when g <= d_act, competing for the RMP2_MAX_CONTACTS slots by the same rule.
+ * The row:  J[j] = n . (z_j x (X - o_j)) (revolute; n . z_j prismatic) for j in anc(f) \ anc(e);
+ *           J[j] = -n . (z_j x (Y - o_j)) (revolute; -n . z_j prismatic) for j in anc(e) \ anc(f);
+ *           J[j] = 0 exactly for every other j, the dofs common to both links included (they move the pair rigidly).
+ * On a serial chain anc(e) is a subset of anc(f): the one-body capsule row under the mask anc(f) & ~anc(e).
+ * The PAIR INDEX of a self row is F K + 2 F P + F C + f F + e: after every sphere, plane and capsule pair, so that a tie goes
+ * sphere, plane, capsule, self; at most 32 * 2^24 + 512 + 1024 + 1024 < 2^31.  The RMP2_CONTACT_PAIR_SELF_* macros take a self pair apart,
+ * RMP2_CONTACT_PAIR_KIND4 tells the four kinds apart.
+ * A pair on a frame whose link-capsule row is all zero is never a candidate, as for spheres.  With no pairs set the call is the
+ * capsules call; with K = P = C = 0 as well the stops' step.
+ * The setter refuses with RMP2_ERR_INVALID_ARGUMENT (the handle keeps the list it had): a frame out of range, i == j, a pair
+ * given twice in either order, a pair with anc(i) == anc(j) (rigidly connected: its row would be identically zero), more than
+ * RMP2_MAX_CONTACT_SELF_FRAMES distinct partner frames (the kernel keeps each partner's segment per robot: 22 x 6 words lie over
+ * the solver's 135 words of a 9-dof robot, which are free during the search).
+ * Limits: the static base link takes no part (its frame is not in the program); capsule against capsule, not hull against hull;
+ * one row per pair -- parallel links are held at one point per substep; frictionless, inelastic, no position recovery; robots of
+ * at most 9 dofs; no rollout fusion.  Stream-ordered, no allocation, no read-back: capturable. */
+#define RMP2_MAX_CONTACT_SELF_FRAMES 22
+#define RMP2_CONTACT_KIND_SELF 3
+#define RMP2_CONTACT_PAIR_SELF_BASE(F, K, P, C) (RMP2_CONTACT_PAIR_CAPSULE_BASE(F, K, P) + (int64_t)(F) * (C))
+#define RMP2_CONTACT_PAIR_KIND4(pair, F, K, P, C) \
+  ((int64_t)(pair) >= RMP2_CONTACT_PAIR_SELF_BASE(F, K, P, C) ? RMP2_CONTACT_KIND_SELF : RMP2_CONTACT_PAIR_KIND3(pair, F, K, P))
+#define RMP2_CONTACT_PAIR_SELF_LINK(pair, F, K, P, C) ((int32_t)(((int64_t)(pair) - RMP2_CONTACT_PAIR_SELF_BASE(F, K, P, C)) / (F)))
+#define RMP2_CONTACT_PAIR_SELF_PARTNER(pair, F, K, P, C) ((int32_t)(((int64_t)(pair) - RMP2_CONTACT_PAIR_SELF_BASE(F, K, P, C)) % (F)))
+int rmp2_set_contact_self_pairs(rmp2_handle *h, int32_t n_pairs, const int32_t *pairs /* host [n_pairs][2] */);
+int rmp2_dynamics_step_contacts_self(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
+                                     const float *q_lower, const float *q_upper, const float *spheres, int32_t K,
+                                     const int32_t *csr_offset, const int32_t *csr_index, const float *planes, int32_t P,
+                                     const float *obstacle_capsules /* device [C][8] */, int32_t C, float d_act, float dt,
+                                     int32_t substeps, float *qdd_out, float *tau_out, float *stop_out, float *contact_out,
+                                     float *contact_lambda, int32_t *contact_pair, uint32_t *status_out, int32_t R,
+                                     void *stream);
 
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,

@@ -38,6 +38,8 @@
 // PLANES> at the end of this file, which rmp2_contacts_tu.hip instantiates once per form (a code object each).
 // A third switch, capsule obstacles beside both (rmp2_dynamics_step_contacts_capsules; NoCapsules / CapsuleTable), is the same
 // body again with planes and capsules on, behind a kernel of its own (rmp2_dynamics_step_contacts_capsules_kernel<N, SLOTS, LIST>).
+// A fourth, self contacts between the robot's own link capsules (rmp2_dynamics_step_contacts_self; NoSelfPairs / SelfPairs), is the
+// body with planes, capsules and self pairs on, behind rmp2_dynamics_step_contacts_self_kernel<N, SLOTS, LIST>.
 #pragma once
 #include <type_traits>
 
@@ -201,6 +203,37 @@ struct CapsuleTable {
   static constexpr bool kOn = true;
 };
 
+// Self contacts between the robot's own link capsules (rmp2_dynamics_step_contacts_self), a defaulted template parameter like the
+// capsules: with NoSelfPairs each `if constexpr (Sp::kOn)` is discarded.  SelfPairs: the handle's pair list as three int32 tables,
+// constants of the program formed on the host (rmp2_set_contact_self_pairs) and read at uniform addresses.  Of a pair {i, j} the
+// frame the walk visits later is the LINK f, the other the PARTNER e.  slot [n_ops]: the partner slot of op k's frame, or -1;
+// begin [n_ops + 1]: op k's pairs (its frame in the link role) are the records begin[k] .. begin[k + 1] - 1;  rec [n][4] =
+// (the partner's slot, the partner's frame e, anc(f) & ~anc(e), anc(e) & ~anc(f)).  When the walk passes a partner frame it stores
+// the world segment's two ends in the slot (6 words per lane at seg, word w of the lane at seg[w * stride]); at a link frame each
+// pair is one more trip after the spheres and the obstacle capsules: the capsule trip with the stored segment (A_e, A_e + D_e, r_e)
+// where the obstacle (C_0, C_1, r_c) stood.  The row's entries are the one-body row's under the first mask and, across a branch,
+// -n . (z_j x (Y - o_j)) (revolute; -n . z_j prismatic) under the second; dofs common to both links are exactly 0.  Pair index:
+// F (K + 2 P + C) + f F + e.  n == 0: no pairs, nothing is read.
+struct NoSelfPairs {
+  static constexpr bool kOn = false;
+};
+struct SelfPairs {
+  const int32_t* slot;
+  const int32_t* begin;
+  const int32_t* rec;
+  int n, F;
+  float* seg;   // (set by dynamics_step_contacts_robot: the solver's columns, free during the search)
+  static constexpr bool kOn = true;
+};
+constexpr int kMaxSelfFrames = RMP2_MAX_CONTACT_SELF_FRAMES;
+// words per lane of the self forms: the partner segments lie over Y, the Gram factor and the multipliers, which only the solver
+// writes, after the search of the same substep.  N = 9: 6 * 22 = 132 of those 135 words, no word more than contact_words(9);
+// N = 2: that region has 9 words, the segments reach past it.
+constexpr int contact_self_words(int n) {
+  const int need = fd_tri(n) + kMaxContacts * n + 6 * kMaxSelfFrames;
+  return need > contact_words(n) ? need : contact_words(n);
+}
+
 // The slot of a qualifying candidate (gap g, pair index idx) among the kept ones: a free slot, or the kept candidate of largest
 // (gap, index) when the new one is smaller, or -1.  The rule of the sphere trip below, which keeps its own inline statement of it
 // (its code is not to change); the plane trip calls this.
@@ -233,11 +266,12 @@ __host__ __device__ inline int contact_slot(float g, int idx, int& count, float 
 // The candidate search and the rows of one robot at q.  caps: [n_frames][8] (a, radius, b, 0) in frame coordinates, read at
 // uniform addresses; src: the robot's spheres (above).  Jr: the rows' storage.  cgap / cidx: gap and pair index per slot (cidx
 // -1: empty).  Returns the number of candidates kept; excess: how many more qualified.
-template <int N, int SLOTS, class Src, class Pl = NoPlanes, class Cp = NoCapsules>
+template <int N, int SLOTS, class Src, class Pl = NoPlanes, class Cp = NoCapsules, class Sp = NoSelfPairs>
 __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_ops, const float* caps, Src src,
                                                        float d_act, const float (&q)[N], float* Jr, int stride,
                                                        float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess,
-                                                       Pl pl = Pl{}, Cp oc = Cp{}) {
+                                                       Pl pl = Pl{}, Cp oc = Cp{}, Sp sp = Sp{}) {
+  static_assert(!Sp::kOn || (Pl::kOn && Cp::kOn), "the self forms run with the planes and the capsules on");
   const int K = src.count();   // the robot's records (the pair index is made of src.pool())
   float ax[N][3], org[N][3];
 #pragma unroll
@@ -296,6 +330,19 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     const float dd = id_dot(D, D);
     const float inv_dd = dd > 0.f ? 1.f / dd : 0.f;
     const uint32_t mask = op.anc_mask;
+    int self_begin = 0, self_trips = 0;   // the pairs with this frame in the link role
+    if constexpr (Sp::kOn) {
+      if (sp.n > 0) {
+        const int sl = sp.slot[k];
+        if (sl >= 0)   // a partner of frames to come: its world segment's ends, per lane
+          for (int i = 0; i < 3; ++i) {
+            sp.seg[(size_t)(6 * sl + i) * stride] = A[i];
+            sp.seg[(size_t)(6 * sl + 3 + i) * stride] = A[i] + D[i];
+          }
+        self_begin = sp.begin[k];
+        self_trips = sp.begin[k + 1] - self_begin;
+      }
+    }
     if constexpr (Pl::kOn) {
       // the planes: one row per end of the segment (a zero-length capsule: the end 0 only), the normal the plane's as given
       const int ends = (D[0] == 0.f && D[1] == 0.f && D[2] == 0.f) ? 1 : 2;
@@ -334,12 +381,37 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     if constexpr (Src::kList) cursor.begin(src);
     int trips = K;   // with capsules: the robot's K spheres, then the C capsules, through the one trip body
     if constexpr (Cp::kOn) trips += oc.C;
+    if constexpr (Sp::kOn) trips += self_trips;   // ... then its self pairs
     for (int s = 0; s < trips; ++s) {
       float c[3], rs;
       int sk = s;   // the record's index in the pool
       bool capsule = false;
       if constexpr (Cp::kOn) capsule = s >= K;
-      if (capsule) {
+      bool self = false;
+      int se = 0;               // the partner's frame
+      uint32_t mf = 0u, me = 0u;   // the dofs that move the link alone, the partner alone
+      if constexpr (Sp::kOn) {
+        self = s >= K + oc.C;
+        capsule = capsule && !self;
+      }
+      if (self) {
+        if constexpr (Sp::kOn) {   // the capsule trip on the partner's stored segment
+          const int32_t* pr = sp.rec + 4 * (size_t)(self_begin + (s - K - oc.C));
+          se = pr[1];
+          mf = (uint32_t)pr[2], me = (uint32_t)pr[3];
+          const float* ce = caps + (size_t)se * 8;
+          bool ehas = false;
+          for (int i = 0; i < 8; ++i) ehas = ehas || ce[i] != 0.f;
+          if (!ehas) continue;   // (a partner without a capsule: its slot was never written)
+          const float* sg = sp.seg + (size_t)(6 * pr[0]) * stride;
+          const float C0[3] = {sg[0], sg[stride], sg[2 * stride]}, C1[3] = {sg[3 * stride], sg[4 * stride], sg[5 * stride]};
+          const float B[3] = {A[0] + D[0], A[1] + D[1], A[2] + D[2]};
+          float sl, to;
+          segment_segment(A, B, C0, C1, sl, to);
+          for (int i = 0; i < 3; ++i) c[i] = C0[i] + to * (C1[i] - C0[i]);
+          rs = ce[3];
+        }
+      } else if (capsule) {
         if constexpr (Cp::kOn) {   // the sphere (Y, radius): Y the point of the obstacle's axis nearest the link's axis
           const float* rec = oc.capsules + 8 * (size_t)(s - K);
           const float C0[3] = {rec[0], rec[1], rec[2]}, C1[3] = {rec[4], rec[5], rec[6]};
@@ -370,6 +442,7 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
       ++total;
       int idx = op.frame * src.pool() + sk;
       if constexpr (Cp::kOn) idx = capsule ? oc.F * (src.pool() + 2 * oc.P) + op.frame * oc.C + (s - K) : idx;
+      if constexpr (Sp::kOn) idx = self ? oc.F * (src.pool() + 2 * oc.P + oc.C) + op.frame * sp.F + se : idx;
       int put = -1;
       if (count < kMaxContacts) {
         put = count++;
@@ -395,10 +468,12 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
       const float inv = 1.f / len;
       const float nu[3] = {n[0] * inv, n[1] * inv, n[2] * inv};
       float* row = Jr + (size_t)put * N * stride;
+      uint32_t lmask = mask;   // a self pair: the dofs that move the link and not the partner
+      if constexpr (Sp::kOn) lmask = self ? mf : mask;
 #pragma unroll
       for (int j = 0; j < N; ++j) {
         float val = 0.f;
-        if ((mask >> j) & 1u) {
+        if ((lmask >> j) & 1u) {
           if ((revolute >> j) & 1u) {
             const float d[3] = {X[0] - org[j][0], X[1] - org[j][1], X[2] - org[j][2]};
             float zx[3];
@@ -406,6 +481,18 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
             val = id_dot(nu, zx);
           } else {
             val = id_dot(nu, ax[j]);
+          }
+        }
+        if constexpr (Sp::kOn) {   // the second body, across a branch: the dofs that move the partner and not the link
+          if (self && ((me >> j) & 1u)) {
+            if ((revolute >> j) & 1u) {
+              const float d[3] = {c[0] - org[j][0], c[1] - org[j][1], c[2] - org[j][2]};
+              float zx[3];
+              id_cross(ax[j], d, zx);
+              val = -id_dot(nu, zx);
+            } else {
+              val = -id_dot(nu, ax[j]);
+            }
           }
         }
         row[j * stride] = val;
@@ -664,10 +751,11 @@ __host__ __device__ inline auto contact_source(const float* spheres, int K, cons
 // rmp2_dynamics_step_contacts of one robot, and with LIST rmp2_dynamics_step_contacts_lists of one robot: the same routine, the
 // robot's spheres being the table spheres [K][4] itself or the list_len records spheres[list[i]] of it (contact_list_span gives
 // list and list_len from csr_offset / csr_index).  qlo / qhi: [n_dof] or both null (no limits).  contact_out [n_dof], lambda_out
-// / pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats.  The spheres are scanned
+// / pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats (with SelfPairs:
+// contact_self_words(N)).  The spheres are scanned
 // once, before the substeps: a non-finite record makes the robot NaN, an invalid list NaN with the status word
 // RMP2_CONTACT_LIST_INVALID alone (its substeps run on no spheres, and nothing is read through its entries).
-template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes, class Cp = NoCapsules>
+template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes, class Cp = NoCapsules, class Sp = NoSelfPairs>
 __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, int n_ops, int n_dof, const float* inert,
                                                              const float base_acc[3], float* q_io, float* qd_io,
                                                              const float* u_in, bool accel, const float* lim, const float* qlo,
@@ -676,13 +764,14 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
                                                              float* stop_out, float* contact_out, float* lambda_out,
                                                              int32_t* pair_out, uint32_t* status_out, float* lds, int stride,
                                                              const int32_t* list = nullptr, int list_len = 0, Pl pl = Pl{},
-                                                             Cp oc = Cp{}) {
+                                                             Cp oc = Cp{}, Sp sp = Sp{}) {
   auto src = contact_source<LIST>(spheres, K, list, list_len);
   float* Ms = lds;
   float* Jr = Ms + (size_t)fd_tri(N) * stride;
   float* Yw = Jr + (size_t)kMaxContacts * N * stride;
   float* Lw = Yw + (size_t)N * N * stride;
   float* mu = Lw + (size_t)fd_tri(N) * stride;
+  if constexpr (Sp::kOn) sp.seg = Yw;   // (lds: room for contact_self_words(N) floats)
   float q[N], qd[N], u[N], qdd[N], tapp[N], stop[N], cont[N], lamc[kMaxContacts];
   int cidx[kMaxContacts];
   float poison = 0.f;
@@ -728,7 +817,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
       cont[j] = 0.f;
     }
     int excess = 0;
-    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess, pl, oc);
+    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess, pl, oc, sp);
     if (excess > 0) status |= RMP2_CONTACT_OVERFLOW;
 #pragma unroll
     for (int c = 0; c < kMaxContacts; ++c) lamc[c] = 0.f;
@@ -893,6 +982,46 @@ rmp2_dynamics_step_contacts_capsules_kernel(const DevProgram* __restrict__ prog,
       contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
       status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, PlaneTable{planes, P, F},
       CapsuleTable{capsules, C, F, P});
+}
+
+// The self forms (rmp2_dynamics_step_contacts_self): the same robot routine with planes, capsules AND self pairs on, behind a
+// kernel of its own like the capsule forms.  self_slot / self_begin / self_rec: the handle's pair tables (SelfPairs), n_self pairs;
+// n_self == 0 reads none of them.
+template <int N, int SLOTS, bool LIST>
+__global__ void __launch_bounds__(kWave)
+rmp2_dynamics_step_contacts_self_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
+                                        float az, float* q, float* qd, const float* __restrict__ u, int accel,
+                                        const float* __restrict__ lim, const float* __restrict__ qlo,
+                                        const float* __restrict__ qhi, const float* __restrict__ caps,
+                                        const float* __restrict__ spheres, int K, const int32_t* __restrict__ csr_offset,
+                                        const int32_t* __restrict__ csr_index, const float* __restrict__ planes, int P,
+                                        const float* __restrict__ capsules, int C, const int32_t* __restrict__ self_slot,
+                                        const int32_t* __restrict__ self_begin, const int32_t* __restrict__ self_rec, int n_self,
+                                        int F, float d_act, float dt, int substeps, float* __restrict__ qdd_out,
+                                        float* __restrict__ tau_out, float* __restrict__ stop_out, float* __restrict__ contact_out,
+                                        float* __restrict__ lambda_out, int32_t* __restrict__ pair_out,
+                                        uint32_t* __restrict__ status_out, int R) {
+  static_assert(contact_self_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
+  __shared__ float lds[contact_self_words(N) * kWave];
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const size_t crow = (size_t)robot * kMaxContacts;
+  const float base_acc[3] = {ax, ay, az};
+  const int32_t* list = nullptr;
+  int len = 0;
+  if constexpr (LIST) {
+    int beg;
+    len = contact_list_span(csr_offset, robot, beg);
+    list = csr_index + beg;
+  }
+  dynamics_step_contacts_robot<N, SLOTS, LIST, PlaneTable, CapsuleTable, SelfPairs>(
+      prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim, qlo, qhi, caps, spheres, K, d_act,
+      dt, substeps, qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
+      contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
+      status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, PlaneTable{planes, P, F},
+      CapsuleTable{capsules, C, F, P}, SelfPairs{self_slot, self_begin, self_rec, n_self, F, nullptr});
 }
 #endif
 

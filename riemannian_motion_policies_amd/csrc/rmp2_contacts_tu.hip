@@ -2,7 +2,8 @@
 // Compiled four times, RMP2_TU_LIST = 0 (the shared sphere table) or 1 (per-robot lists over a pool) by RMP2_TU_PLANES = 0 or 1
 // (half-spaces beside the spheres), each a code object of its own: a form's device code does not depend on the others' being there.
 // With RMP2_TU_CAPSULES = 1 (and RMP2_TU_PLANES = 1) the unit holds the capsule forms instead -- planes and capsule obstacles on,
-// rmp2_dynamics_step_contacts_capsules_kernel -- two more code objects, RMP2_TU_LIST = 0 and 1.
+// rmp2_dynamics_step_contacts_capsules_kernel -- two more code objects, RMP2_TU_LIST = 0 and 1.  With RMP2_TU_SELF = 1 (and the
+// other two) it holds the self forms -- the handle's self pairs on as well, rmp2_dynamics_step_contacts_self_kernel -- two more.
 #include <cfloat>
 #include <cmath>
 
@@ -18,10 +19,40 @@
 #if RMP2_TU_CAPSULES && !RMP2_TU_PLANES
 #error "the capsule forms run with the planes on"
 #endif
+#ifndef RMP2_TU_SELF
+#define RMP2_TU_SELF 0
+#endif
+#if RMP2_TU_SELF && !RMP2_TU_CAPSULES
+#error "the self forms run with the planes and the capsules on"
+#endif
 
 namespace rmp2 {
 
-#if RMP2_TU_CAPSULES
+#if RMP2_TU_SELF
+#if RMP2_TU_LIST
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_self) {
+#else
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_self) {
+#endif
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  // the handle's pair tables (rmp2_set_contact_self_pairs); without pairs the kernel reads none of them
+  const int n_ops = (int)h->full_op_frame.size(), n_self = h->contact_self_n;
+  const int32_t* slot = n_self ? h->d_contact_self : nullptr;
+  const int32_t* begin = n_self ? slot + n_ops : nullptr;
+  const int32_t* rec = n_self ? begin + n_ops + 1 : nullptr;
+  auto launch = [&](auto N) {
+    with_slots(h->n_slots_full, [&](auto S) {
+      hipLaunchKernelGGL((rmp2_dynamics_step_contacts_self_kernel<N, S, RMP2_TU_LIST != 0>), grid, block, 0, s, h->d_prog_full,
+                         h->d_inert, a[0], a[1], a[2], q, qd, u, accel, lim, qlo, qhi, h->d_contact_caps, spheres, K, csr_offset,
+                         csr_index, planes, P, capsules, C, slot, begin, rec, n_self, h->n_frames, d_act, dt, substeps, qdd_out,
+                         tau_out, stop_out, contact_out, lambda_out, pair_out, status_out, R);
+    });
+  };
+  if (h->n_template == 2) launch(std::integral_constant<int, 2>());
+  else launch(std::integral_constant<int, 9>());
+}
+#elif RMP2_TU_CAPSULES
 #if RMP2_TU_LIST
 RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_capsules) {
 #else

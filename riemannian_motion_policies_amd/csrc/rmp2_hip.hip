@@ -2414,13 +2414,16 @@ constexpr decltype(&launch_contacts_table) kLaunchContacts[2][2] = {{launch_cont
 // ... and with capsule obstacles (planes on): [LIST]
 constexpr decltype(&launch_contacts_table_capsules) kLaunchContactsCapsules[2] = {launch_contacts_table_capsules,
                                                                                   launch_contacts_lists_capsules};
+// ... and with the handle's self pairs as well: [LIST]
+constexpr decltype(&launch_contacts_table_self) kLaunchContactsSelf[2] = {launch_contacts_table_self, launch_contacts_lists_self};
 
-// The host path of the four contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
+// The host path of the five contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
 // each entry point keeps its `what` and its own rules (table: K <= RMP2_MAX_CONTACT_SPHERES; lists: both CSR arrays, the pool
 // aligned; planes: the CSR arrays both set or both null, P and the plane table; capsules: the planes' rules, C and the capsule
-// table).  The planes entry always runs a PLANES kernel, P == 0 included; the capsules entry always a capsule kernel (planes and
-// capsules on), P == 0 and C == 0 included.
-enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules };
+// table; self: the capsules' rules, the pairs are the handle's).  The planes entry always runs a PLANES kernel, P == 0 included;
+// the capsules entry always a capsule kernel (planes and capsules on), P == 0 and C == 0 included; the self entry always a self
+// kernel (planes, capsules and self on), no pairs set included.
+enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules, kContactsSelf };
 
 int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float* q, float* qd, const float* u, int32_t drive,
                        const float* tau_limit, const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
@@ -2431,7 +2434,8 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   const std::string w = what;
   if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
-  const bool with_capsules = form == kContactsCapsules;
+  const bool with_self = form == kContactsSelf;   // (the capsules' rules; always a self kernel, no pairs set included)
+  const bool with_capsules = form == kContactsCapsules || with_self;
   const bool with_planes = form == kContactsPlanes || with_capsules;
   if (with_planes && (csr_offset != nullptr) != (csr_index != nullptr))
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": csr_offset and csr_index go together (both null: the shared table)");
@@ -2469,7 +2473,11 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
   if (int rc = step_rows_check(h, what, q, qd, u, others_ok, R, launch)) return rc;
   if (!launch) return RMP2_OK;
   // (N in {2, 9} by the handle's template size, SLOTS by its program)
-  if (with_capsules)
+  if (with_self)
+    kLaunchContactsSelf[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index,
+                               planes, P, capsules, C, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda,
+                               contact_pair, status_out, R, (hipStream_t)stream);
+  else if (with_capsules)
     kLaunchContactsCapsules[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
                                    csr_index, planes, P, capsules, C, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
                                    contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
@@ -2717,6 +2725,10 @@ int rmp2_create(const rmp2_desc* desc, int device, rmp2_handle** out) {
   if (e == hipSuccess) e = hipMemcpy(h->d_prog, &P, sizeof(DevProgram), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&h->d_prog_full, sizeof(DevProgram));
   if (e == hipSuccess) e = hipMemcpy(h->d_prog_full, &Pfull, sizeof(DevProgram), hipMemcpyHostToDevice);
+  for (int k = 0; k < Pfull.n_ops; ++k) {   // (rmp2_set_contact_self_pairs: roles by op order, masks by ancestor dofs)
+    h->full_op_frame.push_back(Pfull.ops[k].frame);
+    h->full_op_anc.push_back(Pfull.ops[k].anc_mask & 0xffffu);   // (the dof set alone: bits 16 + j are structural_lever_zeros')
+  }
   {
     // hex kernel: one contiguous blob = [HexCtl | HexOp | leaves in execution order | leaf-frame records | jump | op_anc]
     std::vector<unsigned char> blob;
@@ -2779,6 +2791,7 @@ int rmp2_destroy(rmp2_handle* h) {
   if (h->d_shull) (void)hipFree(h->d_shull);
   if (h->d_inert) (void)hipFree(h->d_inert);
   if (h->d_contact_caps) (void)hipFree(h->d_contact_caps);
+  if (h->d_contact_self) (void)hipFree(h->d_contact_self);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
   return RMP2_OK;
@@ -4035,6 +4048,62 @@ int rmp2_set_contact_capsules(rmp2_handle* h, int32_t n_frames, const float* cap
   return RMP2_OK;
 }
 
+int rmp2_set_contact_self_pairs(rmp2_handle* h, int32_t n_pairs, const int32_t* pairs) {
+  if (!h) return RMP2_ERR_INVALID_ARGUMENT;
+  if (n_pairs < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact self pairs: n_pairs < 0");
+  if (n_pairs == 0) {   // off: rmp2_dynamics_step_contacts_self is the capsules call again
+    h->contact_self_n = 0;
+    return RMP2_OK;
+  }
+  if (!pairs) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact self pairs: null pair list with n_pairs > 0");
+  const int n_ops = (int)h->full_op_frame.size();
+  std::vector<int> op_of(h->n_frames, -1);   // the op that visits each frame
+  for (int k = 0; k < n_ops; ++k)
+    if (h->full_op_frame[k] >= 0 && h->full_op_frame[k] < h->n_frames) op_of[h->full_op_frame[k]] = k;
+  const int max_pairs = RMP2_MAX_FRAMES * (RMP2_MAX_FRAMES - 1) / 2;
+  if (n_pairs > max_pairs) return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact self pairs: more pairs than there are frame pairs");
+  std::vector<std::vector<int>> partners(n_ops);   // per link op: its partners' ops, in the caller's order
+  std::vector<int32_t> slot(n_ops, -1);
+  std::vector<char> seen((size_t)h->n_frames * h->n_frames, 0);
+  int n_slots = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    const int i = pairs[2 * p], j = pairs[2 * p + 1];
+    const std::string at = "contact self pairs: pair " + std::to_string(p);
+    if (i < 0 || i >= h->n_frames || j < 0 || j >= h->n_frames || op_of[i] < 0 || op_of[j] < 0)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, at + ": a frame is out of range");
+    if (i == j) return fail(h, RMP2_ERR_INVALID_ARGUMENT, at + ": a frame against itself");
+    if (seen[(size_t)i * h->n_frames + j]) return fail(h, RMP2_ERR_INVALID_ARGUMENT, at + ": given twice");
+    seen[(size_t)i * h->n_frames + j] = seen[(size_t)j * h->n_frames + i] = 1;
+    const int kf = std::max(op_of[i], op_of[j]), ke = std::min(op_of[i], op_of[j]);
+    if (h->full_op_anc[kf] == h->full_op_anc[ke])
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, at + ": the two frames are rigidly connected (the same dofs move both)");
+    if (slot[ke] < 0) slot[ke] = n_slots++;
+    partners[kf].push_back(ke);
+  }
+  if (n_slots > RMP2_MAX_CONTACT_SELF_FRAMES)
+    return fail(h, RMP2_ERR_INVALID_ARGUMENT, "contact self pairs: " + std::to_string(n_slots) + " distinct partner frames, at most " +
+                                                  std::to_string(RMP2_MAX_CONTACT_SELF_FRAMES));
+  std::vector<int32_t> tab(slot);   // slot [n_ops] | begin [n_ops + 1] | rec [n_pairs][4]
+  int at = 0;
+  for (int k = 0; k < n_ops; ++k) {
+    tab.push_back(at);
+    at += (int)partners[k].size();
+  }
+  tab.push_back(at);
+  for (int k = 0; k < n_ops; ++k)
+    for (int ke : partners[k]) {
+      const uint32_t af = h->full_op_anc[k], ae = h->full_op_anc[ke];
+      tab.insert(tab.end(), {slot[ke], h->full_op_frame[ke], (int32_t)(af & ~ae), (int32_t)(ae & ~af)});
+    }
+  if (int rc = use_device(h)) return rc;
+  if (!h->d_contact_self)
+    HIP_TRY(h, hipMalloc(&h->d_contact_self, sizeof(int32_t) * (2 * RMP2_MAX_FRAMES + 1 + 4 * max_pairs)));
+  // (a synchronous copy: no launch still reads the old tables)
+  HIP_TRY(h, hipMemcpy(h->d_contact_self, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice));
+  h->contact_self_n = n_pairs;
+  return RMP2_OK;
+}
+
 int rmp2_dynamics_step_contacts(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
                                 const float* q_lower, const float* q_upper, const float* spheres, int32_t K, float d_act, float dt,
                                 int32_t substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,
@@ -4074,6 +4143,17 @@ int rmp2_dynamics_step_contacts_capsules(rmp2_handle* h, float* q, float* qd, co
   return contacts_step_impl(h, "dynamics step with contact capsules", kContactsCapsules, q, qd, u, drive, tau_limit, q_lower,
                             q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps,
                             qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream);
+}
+
+int rmp2_dynamics_step_contacts_self(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
+                                     const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
+                                     const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
+                                     const float* obstacle_capsules, int32_t C, float d_act, float dt, int32_t substeps,
+                                     float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
+                                     int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
+  return contacts_step_impl(h, "dynamics step with self contacts", kContactsSelf, q, qd, u, drive, tau_limit, q_lower, q_upper,
+                            spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps, qdd_out,
+                            tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream);
 }
 
 }  // extern "C"

@@ -96,6 +96,11 @@ struct rmp2_handle {
   int contact_n = 0;
   float* d_contact_caps = nullptr;      // [n_frames][8] link capsules in frame coordinates
   float base_acc[3] = {0.f, 0.f, 9.81f};  // -g
+  // self contacts (rmp2_set_contact_self_pairs): off while contact_self_n == 0
+  int contact_self_n = 0;
+  int32_t* d_contact_self = nullptr;    // SelfPairs' tables back to back: slot [n_ops], begin [n_ops + 1], rec [contact_self_n][4]
+  std::vector<int32_t> full_op_frame;   // the unpruned program's frames in op order, and the dofs that move each
+  std::vector<uint32_t> full_op_anc;
   mutable bool quad_skip_resolve = false;  // set around that quad launch (dispatch_solve)
   mutable bool quad_id_lean = false;       // the last quad launch ran the structured identity-leaf loop (launch_quad)
   mutable std::string last_kernel_text;    // last_kernel with that loop and the build tag named
@@ -196,4 +201,7 @@ RMP2_DECL_CONTACTS(launch_contacts_lists_planes);
             float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
 RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_capsules);
 RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_capsules);
+// the self forms (rmp2_dynamics_step_contacts_self): planes, capsule obstacles and the handle's self pairs on, [LIST]; two more
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_self);
+RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_self);
 }  // namespace rmp2

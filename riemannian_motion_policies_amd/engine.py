@@ -22,17 +22,26 @@ CONTACT_LIST_INVALID = 16     # include/rmp2.h RMP2_CONTACT_LIST_INVALID: status
 MAX_CONTACT_PLANES = 8        # include/rmp2.h RMP2_MAX_CONTACT_PLANES: half-spaces of dynamics_step(contact_planes=)
 CONTACT_KIND_SPHERE, CONTACT_KIND_PLANE = 0, 1
 CONTACT_KIND_CAPSULE = 2
+CONTACT_KIND_SELF = 3          # include/rmp2.h RMP2_CONTACT_KIND_SELF: a pair of the robot's own link capsules
+MAX_CONTACT_SELF_FRAMES = 22   # include/rmp2.h RMP2_MAX_CONTACT_SELF_FRAMES: distinct partner frames of set_contact_self_pairs
 
 
-def contact_pair_split(pair: int, n_frames: int, K: int, P: int, C: int = 0):
+def contact_pair_split(pair: int, n_frames: int, K: int, P: int, C: int = 0, self_pairs: bool = False):
     """(kind, frame, record, end) of a contact_pair value of dynamics_step (include/rmp2.h RMP2_CONTACT_PAIR_* macros): kind is
     CONTACT_KIND_SPHERE (record: the sphere's index in the table or pool, end 0), CONTACT_KIND_PLANE (record: the plane, end: 0
     or 1, the capsule's end point) or CONTACT_KIND_CAPSULE (record: the obstacle capsule, end 0).  n_frames: the robot's frame
-    count; K, P, C: the call's sphere, plane and obstacle-capsule counts.  None for an empty slot (-1)."""
+    count; K, P, C: the call's sphere, plane and obstacle-capsule counts.  None for an empty slot (-1).  self_pairs: the value
+    comes from dynamics_step(contact_self=True), whose self rows are (CONTACT_KIND_SELF, link frame, partner frame, 0)."""
     pair, base = int(pair), int(n_frames) * int(K)
     if pair < 0:
         return None
     cbase = base + 2 * int(n_frames) * int(P)
+    sbase = cbase + int(n_frames) * int(C)
+    if self_pairs and pair >= sbase:
+        if pair >= sbase + int(n_frames) ** 2:
+            raise ValueError(f"contact pair {pair} is outside the range of {n_frames} frames, {K} spheres, {P} planes, {C} capsules "
+                             "and the self pairs")
+        return CONTACT_KIND_SELF, (pair - sbase) // int(n_frames), (pair - sbase) % int(n_frames), 0
     if pair >= cbase + int(n_frames) * int(C):
         raise ValueError(f"contact pair {pair} is outside the range of {n_frames} frames, {K} spheres and {P} planes"
                          + (f" and {C} capsules" if C else ""))
@@ -548,6 +557,13 @@ class Engine:
         if self._empty_index is None:   # (here, not in the step: dynamics_step allocates nothing and can be captured)
             self._empty_index = torch.zeros(1, dtype=torch.int32, device=self.device)
 
+    def set_contact_self_pairs(self, pairs) -> None:
+        """Self contacts of dynamics_step(contact_self=True): host pairs [n, 2] of frames whose link capsules (set_contact_capsules)
+        may touch each other (urdf.contact_self_pairs builds them); None or an empty list switches them off (include/rmp2.h
+        rmp2_set_contact_self_pairs, which states what is refused).  Synchronous; in any order against set_contact_capsules."""
+        p = np.zeros((0, 2), np.int32) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        _native.check(self._lib.rmp2_set_contact_self_pairs(self._h, len(p), p.ctypes.data if len(p) else None), self._h)
+
     def inverse_dynamics(self, q: torch.Tensor, qd: torch.Tensor, qdd: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Joint torques tau [R, n] = M(q) qdd + C(q, qd) qd + G(q) (include/rmp2.h rmp2_inverse_dynamics) on the current stream;
         q, qd, qdd [R, n] on the engine's device.  Needs set_inertials."""
@@ -651,7 +667,7 @@ class Engine:
                       contacts: Optional[torch.Tensor] = None, d_act: float = 0.0, contact_out: Optional[torch.Tensor] = None,
                       contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None,
                       contact_lists=None, contact_planes: Optional[torch.Tensor] = None,
-                      contact_obstacle_capsules: Optional[torch.Tensor] = None) -> None:
+                      contact_obstacle_capsules: Optional[torch.Tensor] = None, contact_self: bool = False) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
@@ -683,7 +699,11 @@ class Engine:
         with or without contacts=, contact_lists= and contact_planes= (include/rmp2.h rmp2_dynamics_step_contacts_capsules; needs
         set_contact_capsules, which sets the LINK capsules).  One row per link capsule and obstacle, at the nearest points of the
         two axes; contact_pair_out holds n_frames * (K + 2 P) + frame * C + capsule for them.  Without it the call takes the
-        routes above, unchanged."""
+        routes above, unchanged.
+        contact_self=True: the robot's own link capsules against each other, the pairs of set_contact_self_pairs, with or without
+        any of the obstacle arguments (include/rmp2.h rmp2_dynamics_step_contacts_self; needs set_contact_capsules).  One row per
+        pair; contact_pair_out holds n_frames * (K + 2 P + C) + link * n_frames + partner for them (contact_pair_split(...,
+        self_pairs=True)).  With no pairs set it is the call without the flag."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
@@ -702,7 +722,7 @@ class Engine:
                                   or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
 
-        if contacts is not None or contact_planes is not None or contact_obstacle_capsules is not None:
+        if contacts is not None or contact_planes is not None or contact_obstacle_capsules is not None or contact_self:
             P = C = 0
             if contact_obstacle_capsules is not None:
                 oc = contact_obstacle_capsules
@@ -754,7 +774,10 @@ class Engine:
             tail = (float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), ptr(stop_out), ptr(contact_out),
                     ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s)
             lists = (ptr(csr_offset), ptr(csr_index))
-            if contact_obstacle_capsules is not None:
+            if contact_self:
+                rc = self._lib.rmp2_dynamics_step_contacts_self(*head, *lists, contact_planes.data_ptr() if P else None, P,
+                                                                contact_obstacle_capsules.data_ptr() if C else None, C, *tail)
+            elif contact_obstacle_capsules is not None:
                 rc = self._lib.rmp2_dynamics_step_contacts_capsules(*head, *lists, contact_planes.data_ptr() if P else None, P,
                                                                     contact_obstacle_capsules.data_ptr() if C else None, C, *tail)
             elif contact_planes is not None:

@@ -429,6 +429,25 @@ def contact_capsules(urdf_filepath: str, table: KinematicTable, default_radius: 
     return np.ascontiguousarray(self_collision_capsules(urdf_filepath, table, default_radius=default_radius, fitted=fitted)[:table.n_frames])
 
 
+def contact_self_pairs(table: KinematicTable, n_neighbors: int = 3) -> np.ndarray:
+    """Frame pairs [n, 2] int32 (i < j) for Engine.set_contact_self_pairs (include/rmp2.h rmp2_set_contact_self_pairs): every two
+    frames with a collision shape that are not within `n_neighbors` parent hops of each other, in either direction
+    (self_collision_pairs' rule), each unordered pair once; pairs that the same dofs move (rigidly connected: nothing can change
+    their gap) are left out.  The static base link takes no part."""
+    def dofs(f):
+        out = set()
+        while f >= 0:
+            if int(table.joint_type[f]) != JOINT_FIXED and int(table.q_index[f]) >= 0:
+                out.add(int(table.q_index[f]))
+            f = int(table.parent[f])
+        return out
+
+    frames = [f for f in range(table.n_frames) if table.has_collision[f]]
+    out = [(a, b) for k, a in enumerate(frames) for b in frames[k + 1:]
+           if not _within_neighborhood(table, a, b, n_neighbors) and dofs(a) != dofs(b)]
+    return np.asarray(out, dtype=np.int32).reshape(-1, 2)
+
+
 MAX_CONTACT_PLANES = 8   # include/rmp2.h RMP2_MAX_CONTACT_PLANES
 
 
