@@ -60,6 +60,17 @@ def test_product_never_imports_oracle():
                 assert "import oracle" not in text and "oracle/" not in text.replace("oracle/ ", ""), f
 
 
+def test_every_header_is_in_the_staleness_hash():
+    """Every csrc/*.h is named in HIP_HEADERS (kernel_src_hash and rmp2_hip's stamp read that list), and every name there is a file:
+    a header left out would let a stale library pass for current."""
+    import __graft_entry__ as g
+    on_disk = {f for f in os.listdir(g.CSRC) if f.endswith(".h")}
+    assert on_disk and on_disk == set(g.HIP_HEADERS), (sorted(on_disk - set(g.HIP_HEADERS)), sorted(set(g.HIP_HEADERS) - on_disk))
+    assert len(g.HIP_HEADERS) == len(set(g.HIP_HEADERS))
+    for _, _, _, headers in g.HIP_UNITS:
+        assert set(headers) <= on_disk
+
+
 def test_descriptor_compiler_layout_and_validation():
     t, d = Cf.config3()
     assert d.n_leaves == 12 and d.goal_floats == 3

@@ -142,7 +142,7 @@ def test_scenes_are_what_they_claim(torch_mod):
 @pytest.mark.parametrize("live", list(S.LIVE))
 def test_stage_and_explicit_pair_step(torch_mod, live, R):
     """Routes 1 and 2.  eng.closest_points(q, table, link_capsules=) in its default form (rmp2_closest_wave_kernel, a lane per pair)
-    and under RMP2_KERNEL=lane (rmp2_closest_kernel, a lane per robot): the pairs against numpy fp64 at 2e-6, the two forms within
+    and under RMP2_KERNEL=lane (rmp2_closest_kernel, a lane per robot; both in csrc/rmp2_stages.h): the pairs against numpy fp64 at 2e-6, the two forms within
     1e-6 of each other; then those pairs fed to the explicit-pair step, against the oracle on the fp64 pairs at 1e-5."""
     torch = torch_mod
     s = _scene("gantry", "auto", R)
@@ -290,8 +290,9 @@ def test_rollout(torch_mod, solve, R):
 @pytest.mark.parametrize("live", list(S.LIVE))
 def test_self_collision_handle(torch_mod, live, R):
     """Route 8.  A handle with set_self_collision (each leaf's link against a base capsule that stays 40 m away) stepping on
-    (table, link_capsules): rmp2_self_stage_kernel<OBS, LINK> forms each leaf's [K obstacle pairs | 1 self pair] -- its obstacle
-    rows are the combined stage's own statement of the closed form -- and the explicit-pair step takes them (stage_self in
+    (table, link_capsules): rmp2_self_stage_kernel<OBS, LINK> (csrc/rmp2_stages.h) forms each leaf's [K obstacle pairs | 1 self
+    pair] -- its obstacle rows are obstacle_pair_points, the closed form it shares with rmp2_closest_wave_kernel -- and the
+    explicit-pair step takes them (stage_self in
     rmp2_hip.hip: a handle with self collision never takes the fused form; last_kernel names the step's kernel only)."""
     torch = torch_mod
     s = _scene("gantry", "auto", R)

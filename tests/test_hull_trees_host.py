@@ -152,7 +152,7 @@ def test_list_scenes_are_what_they_claim():
 
 # ---- sensitivity: the stage's own walk, restated, with three planted faults ---------------------------------------------------
 def _walk(t, q, fault=None):
-    """rmp2_hip.hip walk_frame_position over the unpruned depth-first program with its save / restore slots, in fp64: frames
+    """rmp2_stages.h walk_frame_position over the unpruned depth-first program with its save / restore slots, in fp64: frames
     [R, F, 4, 4].  fault: "ut_signs" (the x and y components of the skew matrix negated), "product_order" (Tc Rv formed as Rv Tc),
     "wrong_slot" (slot 1 restored where slot 0 was saved)."""
     from riemannian_motion_policies_amd import urdf as U
