@@ -881,6 +881,53 @@ int rmp2_dynamics_step_contacts_self(rmp2_handle *h, float *q, float *qd, const 
                                      float *contact_lambda, int32_t *contact_pair, uint32_t *status_out, int32_t R,
                                      void *stream);
 
+/* ---- exact flat-capped cylinder obstacles beside the capsules -------------------------------------------------------------------
+ * rmp2_dynamics_step_contacts_cylinders is rmp2_dynamics_step_contacts_self -- its argument list, its refusals -- with a table of
+ * finite CYLINDERS and a flag: cylinders [Y][8] = (centre xyz, radius, unit axis xyz, half height), fp32, on the device, 16-byte
+ * aligned, 0 <= Y <= RMP2_MAX_OBSTACLE_CYLINDERS, shared by the fleet -- the record of RMP2_PRIM_CYLINDER tables, so that the table
+ * that steers the robots (rmp2_obstacles) also simulates them.  The axis is used as given: a unit axis is the caller's contract.
+ * self_pairs is 0 or 1: with 0 the handle's self pairs are ignored and nothing of them is read.
+ * Per frame f with a link capsule (world segment A, A + D, radius r_f) and cylinder y:
+ *     (X, Yp, n, sd) = segment_cylinder(record, A, D): the sign of n(s) . D at s = 0 and s = 1 (the distance grows from A on, or the
+ *     segment is a point: s = 0; still falling at the far end: s = 1), else 24 halvings of [0, 1] on that sign and one evaluation
+ *     at the last midpoint.  X = A + s D is the point on the link's axis, Yp the nearest point of the cylinder's SURFACE, n the
+ *     outward unit normal of the surface there, sd the signed distance (X = Yp + sd n), negative where the axis runs inside the
+ *     solid; there n is the normal of the nearer of side and cap.  A point on the cylinder's axis takes a fixed perpendicular of the
+ *     axis for its radial direction (the cross product with the coordinate axis the cylinder's axis is least aligned with); half
+ *     height 0 is a disc.
+ *     gap g = sd - r_f;   J[j] = n . (z_j x (X - o_j)) (revolute ancestor dof j; n . z_j prismatic; 0 otherwise);   b = -max(g, 0) / dt.
+ * This is NOT the sphere pair at Yp: the normal is the surface's, not (X - Yp) / |X - Yp|, which flips in penetration and is
+ * undefined at g = 0.  One row per pair; where the minimum is flat (a link parallel to the side, or lying over a cap) the point is
+ * the bisection's choice, and with the slope exactly 0 at s = 0 it is the A end.
+ * Cylinder rows compete for the RMP2_MAX_CONTACTS slots by the rule above (g <= d_act, smallest gaps first, ties to the lower pair
+ * index, the excess reported as RMP2_CONTACT_OVERFLOW).  The PAIR INDEX of a cylinder row is
+ *     RMP2_CONTACT_PAIR_SELF_BASE(F, K, P, C) + F F + f Y + y:
+ * the self block of F F values is always reserved, whether or not self pairs are on, and the cylinder pairs follow it, so that a tie
+ * goes sphere, plane, capsule, self, cylinder; at most 32 * 2^24 + 512 + 1024 + 1024 + 1024 < 2^31, within int32.  The
+ * RMP2_CONTACT_PAIR_CYLINDER_* macros take a cylinder pair apart, RMP2_CONTACT_PAIR_KIND5 tells the five kinds apart.
+ * Y == 0 with self_pairs 1 is the self call; Y == 0 with self_pairs 0 the capsules call; and so on down to the stops' step.
+ * A non-finite value anywhere in a cylinder record makes every robot NaN.  Beyond the self call's refusals: Y < 0,
+ * Y > RMP2_MAX_OBSTACLE_CYLINDERS, a null or misaligned cylinder table with Y > 0, self_pairs outside {0, 1}:
+ * RMP2_ERR_INVALID_ARGUMENT.  Robots of at most 9 dofs (RMP2_ERR_UNSUPPORTED beyond).  Stream-ordered, no allocation, no
+ * read-back: capturable. */
+#define RMP2_MAX_OBSTACLE_CYLINDERS 32
+#define RMP2_CONTACT_KIND_CYLINDER 4
+#define RMP2_CONTACT_PAIR_CYLINDER_BASE(F, K, P, C) (RMP2_CONTACT_PAIR_SELF_BASE(F, K, P, C) + (int64_t)(F) * (F))
+#define RMP2_CONTACT_PAIR_KIND5(pair, F, K, P, C) \
+  ((int64_t)(pair) >= RMP2_CONTACT_PAIR_CYLINDER_BASE(F, K, P, C) ? RMP2_CONTACT_KIND_CYLINDER : RMP2_CONTACT_PAIR_KIND4(pair, F, K, P, C))
+#define RMP2_CONTACT_PAIR_CYLINDER_FRAME(pair, F, K, P, C, Y) \
+  ((int32_t)(((int64_t)(pair) - RMP2_CONTACT_PAIR_CYLINDER_BASE(F, K, P, C)) / (Y)))
+#define RMP2_CONTACT_PAIR_CYLINDER_RECORD(pair, F, K, P, C, Y) \
+  ((int32_t)(((int64_t)(pair) - RMP2_CONTACT_PAIR_CYLINDER_BASE(F, K, P, C)) % (Y)))
+int rmp2_dynamics_step_contacts_cylinders(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive, const float *tau_limit,
+                                          const float *q_lower, const float *q_upper, const float *spheres, int32_t K,
+                                          const int32_t *csr_offset, const int32_t *csr_index, const float *planes, int32_t P,
+                                          const float *obstacle_capsules /* device [C][8] */, int32_t C,
+                                          const float *cylinders /* device [Y][8] */, int32_t Y, int32_t self_pairs, float d_act,
+                                          float dt, int32_t substeps, float *qdd_out, float *tau_out, float *stop_out,
+                                          float *contact_out, float *contact_lambda, int32_t *contact_pair, uint32_t *status_out,
+                                          int32_t R, void *stream);
+
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,
  * plain steps on shared or ragged sphere tables, both fleets beyond 8 192 robots -- the two steps are ONE grid (the first

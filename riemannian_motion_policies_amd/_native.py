@@ -104,6 +104,9 @@ def lib():
         if hasattr(l, "rmp2_dynamics_step_contacts_self"):   # (likewise for a diagnostic RMP2_LIB built before the self contacts)
             l.rmp2_dynamics_step_contacts_self.argtypes = head + lists + [C.c_void_p, C.c_int32] * 2 + tail
             l.rmp2_set_contact_self_pairs.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        if hasattr(l, "rmp2_dynamics_step_contacts_cylinders"):   # (likewise for a diagnostic RMP2_LIB built before the cylinders)
+            # ... planes, P, obstacle capsules, C, cylinders, Y, self_pairs
+            l.rmp2_dynamics_step_contacts_cylinders.argtypes = head + lists + [C.c_void_p, C.c_int32] * 3 + [C.c_int32] + tail
     l.rmp2_differentiate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_differentiate_euler.argtypes = l.rmp2_differentiate.argtypes

@@ -40,6 +40,8 @@
 // body again with planes and capsules on, behind a kernel of its own (rmp2_dynamics_step_contacts_capsules_kernel<N, SLOTS, LIST>).
 // A fourth, self contacts between the robot's own link capsules (rmp2_dynamics_step_contacts_self; NoSelfPairs / SelfPairs), is the
 // body with planes, capsules and self pairs on, behind rmp2_dynamics_step_contacts_self_kernel<N, SLOTS, LIST>.
+// A fifth, exact flat-capped cylinder obstacles (rmp2_dynamics_step_contacts_cylinders; NoCylinders / CylinderTable), is the body
+// with all of those on and the cylinder trips after the self trips, behind rmp2_dynamics_step_contacts_cylinders_kernel<N, SLOTS, LIST>.
 #pragma once
 #include <type_traits>
 
@@ -234,6 +236,26 @@ constexpr int contact_self_words(int n) {
   return need > contact_words(n) ? need : contact_words(n);
 }
 
+// Flat-capped cylinder obstacles beside all of the above (rmp2_dynamics_step_contacts_cylinders), a defaulted template parameter
+// like the self pairs: with NoCylinders each `if constexpr (Cy::kOn)` is discarded.  CylinderTable: the fleet's records [Y][8] =
+// (centre, radius, unit axis, half height) -- the RMP2_PRIM_CYLINDER record the policy reads --, read like the shared sphere table;
+// F, P and C place the cylinder rows' pair indices after the self block: F (K + 2 P + C) + F F + f Y + y.  A cylinder pair is NOT a
+// sphere pair at the nearest point: segment_cylinder (rmp2_device.h) gives the point X of the link's axis, the outward normal n of
+// the cylinder's surface at its nearest point and the signed distance sd, and the trip hands (X, n, g = sd - r_f) to the one
+// keep-and-write statement as they are -- the surface's normal does not flip in penetration and is defined at g = 0.
+// The cull in front of the bisection: the solid lies inside the ball (centre, rho = sqrt(r^2 + h^2)), so with X_c the point of the
+// link's segment nearest the centre every point of the segment has g >= L = |X_c - centre| - rho - r_f; a trip with
+// L > d_act + 1e-4 (1 + |X_c - centre| + rho) (a hundred times the rounding of L) cannot qualify and is skipped; a NaN L does not
+// skip.  -DRMP2_CYLINDER_NO_CULL (tests/contact_cylinders_driver.cpp and tools/contact_cylinders_timing.py only) leaves it out.
+struct NoCylinders {
+  static constexpr bool kOn = false;
+};
+struct CylinderTable {
+  const float* cylinders;
+  int Y, F, P, C;
+  static constexpr bool kOn = true;
+};
+
 // The slot of a qualifying candidate (gap g, pair index idx) among the kept ones: a free slot, or the kept candidate of largest
 // (gap, index) when the new one is smaller, or -1.  The rule of the sphere trip below, which keeps its own inline statement of it
 // (its code is not to change); the plane trip calls this.
@@ -266,12 +288,13 @@ __host__ __device__ inline int contact_slot(float g, int idx, int& count, float 
 // The candidate search and the rows of one robot at q.  caps: [n_frames][8] (a, radius, b, 0) in frame coordinates, read at
 // uniform addresses; src: the robot's spheres (above).  Jr: the rows' storage.  cgap / cidx: gap and pair index per slot (cidx
 // -1: empty).  Returns the number of candidates kept; excess: how many more qualified.
-template <int N, int SLOTS, class Src, class Pl = NoPlanes, class Cp = NoCapsules, class Sp = NoSelfPairs>
+template <int N, int SLOTS, class Src, class Pl = NoPlanes, class Cp = NoCapsules, class Sp = NoSelfPairs, class Cy = NoCylinders>
 __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_ops, const float* caps, Src src,
                                                        float d_act, const float (&q)[N], float* Jr, int stride,
                                                        float (&cgap)[kMaxContacts], int (&cidx)[kMaxContacts], int& excess,
-                                                       Pl pl = Pl{}, Cp oc = Cp{}, Sp sp = Sp{}) {
+                                                       Pl pl = Pl{}, Cp oc = Cp{}, Sp sp = Sp{}, Cy cy = Cy{}) {
   static_assert(!Sp::kOn || (Pl::kOn && Cp::kOn), "the self forms run with the planes and the capsules on");
+  static_assert(!Cy::kOn || (Pl::kOn && Cp::kOn && Sp::kOn), "the cylinder forms run with the planes, the capsules and the self pairs on");
   const int K = src.count();   // the robot's records (the pair index is made of src.pool())
   float ax[N][3], org[N][3];
 #pragma unroll
@@ -382,19 +405,24 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     int trips = K;   // with capsules: the robot's K spheres, then the C capsules, through the one trip body
     if constexpr (Cp::kOn) trips += oc.C;
     if constexpr (Sp::kOn) trips += self_trips;   // ... then its self pairs
+    const int cyl_first = trips;                  // ... then the Y cylinders
+    if constexpr (Cy::kOn) trips += cy.Y;
     for (int s = 0; s < trips; ++s) {
       float c[3], rs;
       int sk = s;   // the record's index in the pool
+      bool cylinder = false;
+      if constexpr (Cy::kOn) cylinder = s >= cyl_first;
       bool capsule = false;
-      if constexpr (Cp::kOn) capsule = s >= K;
+      if constexpr (Cp::kOn) capsule = s >= K && !cylinder;
       bool self = false;
       int se = 0;               // the partner's frame
       uint32_t mf = 0u, me = 0u;   // the dofs that move the link alone, the partner alone
       if constexpr (Sp::kOn) {
-        self = s >= K + oc.C;
+        self = s >= K + oc.C && !cylinder;
         capsule = capsule && !self;
       }
-      if (self) {
+      if (cylinder) {   // (the record is read where the trip forms X, n and g, below)
+      } else if (self) {
         if constexpr (Sp::kOn) {   // the capsule trip on the partner's stored segment
           const int32_t* pr = sp.rec + 4 * (size_t)(self_begin + (s - K - oc.C));
           se = pr[1];
@@ -427,22 +455,47 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
         c[0] = src.spheres[4 * s + 0], c[1] = src.spheres[4 * s + 1], c[2] = src.spheres[4 * s + 2];
         rs = src.spheres[4 * s + 3];
       }
-      const float rel[3] = {c[0] - A[0], c[1] - A[1], c[2] - A[2]};
-      float t = id_dot(rel, D) * inv_dd;
-      t = fminf(fmaxf(t, 0.f), 1.f);
-      float X[3], n[3];
-      for (int i = 0; i < 3; ++i) {
-        X[i] = A[i] + t * D[i];
-        n[i] = X[i] - c[i];
+      float X[3], n[3], len, g;   // the point on the link's axis, the normal (of length len) and the gap
+      if (cylinder) {
+        if constexpr (Cy::kOn) {   // X, the surface's unit normal and the signed distance, from segment_cylinder as they are
+          const float* rec = cy.cylinders + 8 * (size_t)(s - cyl_first);
+          const float4 ra = make_float4(rec[0], rec[1], rec[2], rec[3]), rb = make_float4(rec[4], rec[5], rec[6], rec[7]);
+#ifndef RMP2_CYLINDER_NO_CULL
+          {   // the solid lies in the ball (centre, rho): no point of the segment is nearer than L (see CylinderTable)
+            const float relc[3] = {ra.x - A[0], ra.y - A[1], ra.z - A[2]};
+            float tc = id_dot(relc, D) * inv_dd;
+            tc = fminf(fmaxf(tc, 0.f), 1.f);
+            const float dv[3] = {A[0] + tc * D[0] - ra.x, A[1] + tc * D[1] - ra.y, A[2] + tc * D[2] - ra.z};
+            const float dist = sqrtf(id_dot(dv, dv));
+            const float rho = sqrtf(ra.w * ra.w + rb.w * rb.w);
+            const float L = dist - rho - rf;
+            if (L > d_act + 1e-4f * (1.f + dist + rho)) continue;   // (a NaN L goes on)
+          }
+#endif
+          float Yp[3], sd;
+          segment_cylinder(ra, rb, A, D, X, Yp, n, sd);
+          len = 1.f;
+          g = sd - rf;
+        }
+      } else {
+        const float rel[3] = {c[0] - A[0], c[1] - A[1], c[2] - A[2]};
+        float t = id_dot(rel, D) * inv_dd;
+        t = fminf(fmaxf(t, 0.f), 1.f);
+        for (int i = 0; i < 3; ++i) {
+          X[i] = A[i] + t * D[i];
+          n[i] = X[i] - c[i];
+        }
+        const float dn = sqrtf(id_dot(n, n));
+        len = link_normal_length(n);   // (+z and 1 where the centre lies on the axis)
+        g = dn - rs - rf;
       }
-      const float dn = sqrtf(id_dot(n, n));
-      const float len = link_normal_length(n);   // (+z and 1 where the centre lies on the axis)
-      const float g = dn - rs - rf;
       if (!(g <= d_act)) continue;   // (also a NaN gap)
       ++total;
       int idx = op.frame * src.pool() + sk;
       if constexpr (Cp::kOn) idx = capsule ? oc.F * (src.pool() + 2 * oc.P) + op.frame * oc.C + (s - K) : idx;
       if constexpr (Sp::kOn) idx = self ? oc.F * (src.pool() + 2 * oc.P + oc.C) + op.frame * sp.F + se : idx;
+      if constexpr (Cy::kOn)   // after the self block, which is reserved whether or not self pairs are on
+        idx = cylinder ? cy.F * (src.pool() + 2 * cy.P + cy.C) + cy.F * cy.F + op.frame * cy.Y + (s - cyl_first) : idx;
       int put = -1;
       if (count < kMaxContacts) {
         put = count++;
@@ -755,7 +808,7 @@ __host__ __device__ inline auto contact_source(const float* spheres, int K, cons
 // contact_self_words(N)).  The spheres are scanned
 // once, before the substeps: a non-finite record makes the robot NaN, an invalid list NaN with the status word
 // RMP2_CONTACT_LIST_INVALID alone (its substeps run on no spheres, and nothing is read through its entries).
-template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes, class Cp = NoCapsules, class Sp = NoSelfPairs>
+template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes, class Cp = NoCapsules, class Sp = NoSelfPairs, class Cy = NoCylinders>
 __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, int n_ops, int n_dof, const float* inert,
                                                              const float base_acc[3], float* q_io, float* qd_io,
                                                              const float* u_in, bool accel, const float* lim, const float* qlo,
@@ -764,7 +817,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
                                                              float* stop_out, float* contact_out, float* lambda_out,
                                                              int32_t* pair_out, uint32_t* status_out, float* lds, int stride,
                                                              const int32_t* list = nullptr, int list_len = 0, Pl pl = Pl{},
-                                                             Cp oc = Cp{}, Sp sp = Sp{}) {
+                                                             Cp oc = Cp{}, Sp sp = Sp{}, Cy cy = Cy{}) {
   auto src = contact_source<LIST>(spheres, K, list, list_len);
   float* Ms = lds;
   float* Jr = Ms + (size_t)fd_tri(N) * stride;
@@ -795,6 +848,9 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
   if constexpr (Cp::kOn) {   // a non-finite capsule value: every robot NaN
     for (int s = 0; s < 8 * oc.C; ++s) table_poison += oc.capsules[s] * 0.f;
   }
+  if constexpr (Cy::kOn) {   // a non-finite cylinder value: every robot NaN
+    for (int s = 0; s < 8 * cy.Y; ++s) table_poison += cy.cylinders[s] * 0.f;
+  }
   uint32_t status = 0u;
   int most = 0;
   for (int s = 0; s < substeps; ++s) {
@@ -817,7 +873,7 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
       cont[j] = 0.f;
     }
     int excess = 0;
-    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess, pl, oc, sp);
+    const int nc = contact_candidates_from<N, SLOTS>(ops, n_ops, caps, src, d_act, q, Jr, stride, cgap, cidx, excess, pl, oc, sp, cy);
     if (excess > 0) status |= RMP2_CONTACT_OVERFLOW;
 #pragma unroll
     for (int c = 0; c < kMaxContacts; ++c) lamc[c] = 0.f;
@@ -1022,6 +1078,48 @@ rmp2_dynamics_step_contacts_self_kernel(const DevProgram* __restrict__ prog, con
       contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
       status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, PlaneTable{planes, P, F},
       CapsuleTable{capsules, C, F, P}, SelfPairs{self_slot, self_begin, self_rec, n_self, F, nullptr});
+}
+
+// The cylinder forms (rmp2_dynamics_step_contacts_cylinders): the same robot routine with planes, capsules, self pairs AND the
+// cylinder table on, behind a kernel of its own like the self forms.  cylinders [Y][8] (CylinderTable); Y == 0 reads nothing of it.
+// n_self == 0 (no pairs set, or the call's self_pairs flag 0) reads none of the pair tables.  No LDS beyond the self forms'.
+template <int N, int SLOTS, bool LIST>
+__global__ void __launch_bounds__(kWave)
+rmp2_dynamics_step_contacts_cylinders_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
+                                             float az, float* q, float* qd, const float* __restrict__ u, int accel,
+                                             const float* __restrict__ lim, const float* __restrict__ qlo,
+                                             const float* __restrict__ qhi, const float* __restrict__ caps,
+                                             const float* __restrict__ spheres, int K, const int32_t* __restrict__ csr_offset,
+                                             const int32_t* __restrict__ csr_index, const float* __restrict__ planes, int P,
+                                             const float* __restrict__ capsules, int C, const int32_t* __restrict__ self_slot,
+                                             const int32_t* __restrict__ self_begin, const int32_t* __restrict__ self_rec,
+                                             int n_self, const float* __restrict__ cylinders, int Y, int F, float d_act, float dt,
+                                             int substeps, float* __restrict__ qdd_out, float* __restrict__ tau_out,
+                                             float* __restrict__ stop_out, float* __restrict__ contact_out,
+                                             float* __restrict__ lambda_out, int32_t* __restrict__ pair_out,
+                                             uint32_t* __restrict__ status_out, int R) {
+  static_assert(contact_self_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
+  __shared__ float lds[contact_self_words(N) * kWave];
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const size_t crow = (size_t)robot * kMaxContacts;
+  const float base_acc[3] = {ax, ay, az};
+  const int32_t* list = nullptr;
+  int len = 0;
+  if constexpr (LIST) {
+    int beg;
+    len = contact_list_span(csr_offset, robot, beg);
+    list = csr_index + beg;
+  }
+  dynamics_step_contacts_robot<N, SLOTS, LIST, PlaneTable, CapsuleTable, SelfPairs, CylinderTable>(
+      prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim, qlo, qhi, caps, spheres, K, d_act,
+      dt, substeps, qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
+      contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
+      status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, PlaneTable{planes, P, F},
+      CapsuleTable{capsules, C, F, P}, SelfPairs{self_slot, self_begin, self_rec, n_self, F, nullptr},
+      CylinderTable{cylinders, Y, F, P, C});
 }
 #endif
 

@@ -166,7 +166,7 @@ struct ObsArgs {
 // (clamp the axial coordinate to [-h, h] and the radial one to [0, r]: side, cap or rim); inside, the nearer of the side and the
 // cap.  On the axis the radial direction is undefined: a fixed perpendicular of the axis is taken (only the rim and the inside-side
 // cases use it there; distance and position are unaffected).
-__device__ __forceinline__ void point_cylinder(const float4 ra, const float4 rb, const float p[3], float Y[3], float n[3], float& sd) {
+__host__ __device__ __forceinline__ void point_cylinder(const float4 ra, const float4 rb, const float p[3], float Y[3], float n[3], float& sd) {
   const float u[3] = {rb.x, rb.y, rb.z};
   const float r = ra.w, h = rb.w;
   const float w[3] = {p[0] - ra.x, p[1] - ra.y, p[2] - ra.z};
@@ -210,9 +210,10 @@ __device__ __forceinline__ void point_cylinder(const float4 ra, const float4 rb,
 // Nearest points of a link segment A + s D (s in [0, 1]) and a cylinder: the signed distance of a point to a convex body is a convex
 // function of the point, so it is convex in s, and its derivative along the segment is n(s) . D with n the outward normal of the
 // nearest surface point -- monotone in s.  Bisection on its sign (24 halvings: the parameter to 6e-8) after the two end tests; every
-// step is one point_cylinder.  (No closed form: the rim case is a quartic.)
-__device__ __forceinline__ void segment_cylinder(const float4 ra, const float4 rb, const float A[3], const float D[3], float X[3],
-                                                 float Y[3], float n[3], float& sd) {
+// step is one point_cylinder.  (No closed form: the rim case is a quartic.)  Host-compilable, like point_cylinder: the contact
+// step's cylinder trip (rmp2_contacts.h) runs it on the CPU in tests/contact_cylinders_driver.cpp.
+__host__ __device__ __forceinline__ void segment_cylinder(const float4 ra, const float4 rb, const float A[3], const float D[3],
+                                                          float X[3], float Y[3], float n[3], float& sd) {
   auto at = [&](float s) {
     X[0] = fmaf(s, D[0], A[0]), X[1] = fmaf(s, D[1], A[1]), X[2] = fmaf(s, D[2], A[2]);
     point_cylinder(ra, rb, X, Y, n, sd);

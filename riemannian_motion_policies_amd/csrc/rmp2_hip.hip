@@ -1494,25 +1494,30 @@ constexpr decltype(&launch_contacts_table_capsules) kLaunchContactsCapsules[2] =
                                                                                   launch_contacts_lists_capsules};
 // ... and with the handle's self pairs as well: [LIST]
 constexpr decltype(&launch_contacts_table_self) kLaunchContactsSelf[2] = {launch_contacts_table_self, launch_contacts_lists_self};
+// ... and with flat-capped cylinder obstacles as well: [LIST]
+constexpr decltype(&launch_contacts_table_cylinders) kLaunchContactsCylinders[2] = {launch_contacts_table_cylinders,
+                                                                                    launch_contacts_lists_cylinders};
 
-// The host path of the five contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
+// The host path of the six contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
 // each entry point keeps its `what` and its own rules (table: K <= RMP2_MAX_CONTACT_SPHERES; lists: both CSR arrays, the pool
 // aligned; planes: the CSR arrays both set or both null, P and the plane table; capsules: the planes' rules, C and the capsule
 // table; self: the capsules' rules, the pairs are the handle's).  The planes entry always runs a PLANES kernel, P == 0 included;
 // the capsules entry always a capsule kernel (planes and capsules on), P == 0 and C == 0 included; the self entry always a self
-// kernel (planes, capsules and self on), no pairs set included.
-enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules, kContactsSelf };
+// kernel (planes, capsules and self on), no pairs set included; the cylinders entry (the self call's rules, Y, the cylinder table
+// and the self_pairs flag) always a cylinder kernel, Y == 0 included.
+enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules, kContactsSelf, kContactsCylinders };
 
 int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float* q, float* qd, const float* u, int32_t drive,
                        const float* tau_limit, const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
                        const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
                        const float* capsules, int32_t C, float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out,
                        float* stop_out, float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
-                       int32_t R, void* stream) {
+                       int32_t R, void* stream, const float* cylinders = nullptr, int32_t Y = 0, int32_t self_pairs = 1) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   const std::string w = what;
   if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
-  const bool with_self = form == kContactsSelf;   // (the capsules' rules; always a self kernel, no pairs set included)
+  const bool with_cylinders = form == kContactsCylinders;   // (the self call's rules; always a cylinder kernel, Y == 0 included)
+  const bool with_self = form == kContactsSelf || with_cylinders;   // (the capsules' rules; always a self kernel, no pairs set included)
   const bool with_capsules = form == kContactsCapsules || with_self;
   const bool with_planes = form == kContactsPlanes || with_capsules;
   if (with_planes && (csr_offset != nullptr) != (csr_index != nullptr))
@@ -1539,6 +1544,15 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
     if (C > 0 && ((uintptr_t)capsules & 15u))
       return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the capsule table must be 16-byte aligned");
   }
+  if (with_cylinders) {
+    if (Y < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y < 0");
+    if (Y > RMP2_MAX_OBSTACLE_CYLINDERS)
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y > " + std::to_string(RMP2_MAX_OBSTACLE_CYLINDERS));
+    if (Y > 0 && !cylinders) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null cylinder table with Y > 0");
+    if (Y > 0 && ((uintptr_t)cylinders & 15u))
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the cylinder table must be 16-byte aligned");
+    if (self_pairs != 0 && self_pairs != 1) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": self_pairs must be 0 or 1");
+  }
   if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": d_act must be finite and >= 0");
   if (h->contact_n == 0)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
@@ -1551,7 +1565,11 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
   if (int rc = step_rows_check(h, what, q, qd, u, others_ok, R, launch)) return rc;
   if (!launch) return RMP2_OK;
   // (N in {2, 9} by the handle's template size, SLOTS by its program)
-  if (with_self)
+  if (with_cylinders)
+    kLaunchContactsCylinders[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
+                                    csr_index, planes, P, capsules, C, cylinders, Y, self_pairs, d_act, dt, substeps, qdd_out, tau_out,
+                                    stop_out, contact_out, contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
+  else if (with_self)
     kLaunchContactsSelf[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index,
                                planes, P, capsules, C, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda,
                                contact_pair, status_out, R, (hipStream_t)stream);
@@ -3232,6 +3250,19 @@ int rmp2_dynamics_step_contacts_self(rmp2_handle* h, float* q, float* qd, const 
   return contacts_step_impl(h, "dynamics step with self contacts", kContactsSelf, q, qd, u, drive, tau_limit, q_lower, q_upper,
                             spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps, qdd_out,
                             tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream);
+}
+
+int rmp2_dynamics_step_contacts_cylinders(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
+                                          const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
+                                          const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
+                                          const float* obstacle_capsules, int32_t C, const float* cylinders, int32_t Y,
+                                          int32_t self_pairs, float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out,
+                                          float* stop_out, float* contact_out, float* contact_lambda, int32_t* contact_pair,
+                                          uint32_t* status_out, int32_t R, void* stream) {
+  return contacts_step_impl(h, "dynamics step with contact cylinders", kContactsCylinders, q, qd, u, drive, tau_limit, q_lower,
+                            q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps, qdd_out,
+                            tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream, cylinders, Y,
+                            self_pairs);
 }
 
 }  // extern "C"

@@ -204,4 +204,14 @@ RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_capsules);
 // the self forms (rmp2_dynamics_step_contacts_self): planes, capsule obstacles and the handle's self pairs on, [LIST]; two more
 RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_self);
 RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_self);
+// the cylinder forms (rmp2_dynamics_step_contacts_cylinders): all of those and the cylinder table on, [LIST]; two more.
+// self_pairs: 0 -- the handle's self pairs are left out, none of their tables is passed to the kernel
+#define RMP2_DECL_CONTACTS_CYLINDERS(NAME)                                                                                        \
+  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
+            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
+            int P, const float* capsules, int C, const float* cylinders, int Y, int self_pairs, float d_act, float dt,            \
+            int substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* lambda_out,                 \
+            int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
+RMP2_DECL_CONTACTS_CYLINDERS(launch_contacts_table_cylinders);
+RMP2_DECL_CONTACTS_CYLINDERS(launch_contacts_lists_cylinders);
 }  // namespace rmp2

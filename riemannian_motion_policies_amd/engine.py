@@ -14,6 +14,7 @@ import torch
 from . import _native
 from . import descriptor as D
 from .urdf import MAX_OBSTACLE_CAPSULES   # include/rmp2.h RMP2_MAX_OBSTACLE_CAPSULES: capsules of dynamics_step(contact_obstacle_capsules=)
+from .urdf import MAX_OBSTACLE_CYLINDERS  # include/rmp2.h RMP2_MAX_OBSTACLE_CYLINDERS: cylinders of dynamics_step(contact_cylinders=)
 
 MAX_CONTACTS = 8   # include/rmp2.h RMP2_MAX_CONTACTS
 MAX_CONTACT_LIST = 256        # include/rmp2.h RMP2_MAX_CONTACT_LIST: entries per robot of dynamics_step(contact_lists=)
@@ -24,19 +25,28 @@ CONTACT_KIND_SPHERE, CONTACT_KIND_PLANE = 0, 1
 CONTACT_KIND_CAPSULE = 2
 CONTACT_KIND_SELF = 3          # include/rmp2.h RMP2_CONTACT_KIND_SELF: a pair of the robot's own link capsules
 MAX_CONTACT_SELF_FRAMES = 22   # include/rmp2.h RMP2_MAX_CONTACT_SELF_FRAMES: distinct partner frames of set_contact_self_pairs
+CONTACT_KIND_CYLINDER = 4      # include/rmp2.h RMP2_CONTACT_KIND_CYLINDER: a link capsule against a flat-capped cylinder obstacle
 
 
-def contact_pair_split(pair: int, n_frames: int, K: int, P: int, C: int = 0, self_pairs: bool = False):
+def contact_pair_split(pair: int, n_frames: int, K: int, P: int, C: int = 0, self_pairs: bool = False, cylinders: int = 0):
     """(kind, frame, record, end) of a contact_pair value of dynamics_step (include/rmp2.h RMP2_CONTACT_PAIR_* macros): kind is
     CONTACT_KIND_SPHERE (record: the sphere's index in the table or pool, end 0), CONTACT_KIND_PLANE (record: the plane, end: 0
     or 1, the capsule's end point) or CONTACT_KIND_CAPSULE (record: the obstacle capsule, end 0).  n_frames: the robot's frame
     count; K, P, C: the call's sphere, plane and obstacle-capsule counts.  None for an empty slot (-1).  self_pairs: the value
-    comes from dynamics_step(contact_self=True), whose self rows are (CONTACT_KIND_SELF, link frame, partner frame, 0)."""
+    comes from dynamics_step(contact_self=True), whose self rows are (CONTACT_KIND_SELF, link frame, partner frame, 0).
+    cylinders: the Y of dynamics_step(contact_cylinders=), whose cylinder rows -- after the self block of n_frames ** 2 values,
+    which that call reserves with or without contact_self -- are (CONTACT_KIND_CYLINDER, frame, cylinder, 0)."""
     pair, base = int(pair), int(n_frames) * int(K)
     if pair < 0:
         return None
     cbase = base + 2 * int(n_frames) * int(P)
     sbase = cbase + int(n_frames) * int(C)
+    ybase = sbase + int(n_frames) ** 2
+    if cylinders and pair >= ybase:
+        if pair >= ybase + int(n_frames) * int(cylinders):
+            raise ValueError(f"contact pair {pair} is outside the range of {n_frames} frames, {K} spheres, {P} planes, {C} capsules, "
+                             f"the self pairs and {cylinders} cylinders")
+        return CONTACT_KIND_CYLINDER, (pair - ybase) // int(cylinders), (pair - ybase) % int(cylinders), 0
     if self_pairs and pair >= sbase:
         if pair >= sbase + int(n_frames) ** 2:
             raise ValueError(f"contact pair {pair} is outside the range of {n_frames} frames, {K} spheres, {P} planes, {C} capsules "
@@ -667,7 +677,8 @@ class Engine:
                       contacts: Optional[torch.Tensor] = None, d_act: float = 0.0, contact_out: Optional[torch.Tensor] = None,
                       contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None,
                       contact_lists=None, contact_planes: Optional[torch.Tensor] = None,
-                      contact_obstacle_capsules: Optional[torch.Tensor] = None, contact_self: bool = False) -> None:
+                      contact_obstacle_capsules: Optional[torch.Tensor] = None, contact_self: bool = False,
+                      contact_cylinders: Optional[torch.Tensor] = None) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
@@ -703,7 +714,15 @@ class Engine:
         contact_self=True: the robot's own link capsules against each other, the pairs of set_contact_self_pairs, with or without
         any of the obstacle arguments (include/rmp2.h rmp2_dynamics_step_contacts_self; needs set_contact_capsules).  One row per
         pair; contact_pair_out holds n_frames * (K + 2 P + C) + link * n_frames + partner for them (contact_pair_split(...,
-        self_pairs=True)).  With no pairs set it is the call without the flag."""
+        self_pairs=True)).  With no pairs set it is the call without the flag.
+        contact_cylinders = flat-capped cylinder obstacles [Y, 8] fp32 = (centre, radius, unit axis, half height) on the engine's
+        device (Y <= MAX_OBSTACLE_CYLINDERS; urdf.cylinder_obstacles builds them from configs.cylinder_record rows): the
+        reference's posts as what they are, exact flat caps and rims, shared by the fleet, with or without any of the arguments
+        above (include/rmp2.h rmp2_dynamics_step_contacts_cylinders; needs set_contact_capsules).  It is the table that
+        obstacles(..., primitive="cylinder") hands to the policy.  One row per link capsule and cylinder, at the point of the link's
+        axis nearest the cylinder, along the outward normal of the cylinder's surface; contact_pair_out holds n_frames * (K + 2 P +
+        C) + n_frames ** 2 + frame * Y + cylinder for them (contact_pair_split(..., cylinders=Y)).  contact_self says whether the
+        handle's self pairs take part.  Without it the call takes the routes above, unchanged."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
@@ -722,8 +741,18 @@ class Engine:
                                   or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
 
-        if contacts is not None or contact_planes is not None or contact_obstacle_capsules is not None or contact_self:
-            P = C = 0
+        if (contacts is not None or contact_planes is not None or contact_obstacle_capsules is not None or contact_self
+                or contact_cylinders is not None):
+            P = C = Y = 0
+            if contact_cylinders is not None:
+                cyl = contact_cylinders
+                _require_resident(self.device, contact_cylinders=cyl)
+                if cyl.dim() != 2 or cyl.shape[1] != 8 or cyl.dtype != torch.float32 or not cyl.is_contiguous():
+                    raise ValueError("contact_cylinders must be a contiguous fp32 [Y, 8] tensor (centre, radius, unit axis, half height), "
+                                     f"got {list(cyl.shape)}")
+                Y = int(cyl.shape[0])
+                if Y > MAX_OBSTACLE_CYLINDERS:
+                    raise ValueError(f"contact_cylinders holds {Y} cylinders, at most {MAX_OBSTACLE_CYLINDERS}")
             if contact_obstacle_capsules is not None:
                 oc = contact_obstacle_capsules
                 _require_resident(self.device, contact_obstacle_capsules=oc)
@@ -774,7 +803,12 @@ class Engine:
             tail = (float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), ptr(stop_out), ptr(contact_out),
                     ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s)
             lists = (ptr(csr_offset), ptr(csr_index))
-            if contact_self:
+            if contact_cylinders is not None:
+                rc = self._lib.rmp2_dynamics_step_contacts_cylinders(*head, *lists, contact_planes.data_ptr() if P else None, P,
+                                                                     contact_obstacle_capsules.data_ptr() if C else None, C,
+                                                                     contact_cylinders.data_ptr() if Y else None, Y,
+                                                                     1 if contact_self else 0, *tail)
+            elif contact_self:
                 rc = self._lib.rmp2_dynamics_step_contacts_self(*head, *lists, contact_planes.data_ptr() if P else None, P,
                                                                 contact_obstacle_capsules.data_ptr() if C else None, C, *tail)
             elif contact_obstacle_capsules is not None:

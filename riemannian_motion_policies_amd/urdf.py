@@ -532,6 +532,40 @@ def cylinders_as_capsules(cylinders, mode: str = "covering") -> np.ndarray:
     return capsule_obstacles(np.concatenate([c - reach[:, None] * u, r[:, None], c + reach[:, None] * u], axis=1))
 
 
+MAX_OBSTACLE_CYLINDERS = 32   # include/rmp2.h RMP2_MAX_OBSTACLE_CYLINDERS
+
+
+def cylinder_obstacles(rows) -> np.ndarray:
+    """Flat-capped cylinder obstacles [Y, 8] float32 = (centre xyz, radius, unit axis xyz, half height) for
+    Engine.dynamics_step(contact_cylinders=) (include/rmp2.h rmp2_dynamics_step_contacts_cylinders) from host rows of 8 values --
+    configs.cylinder_record rows, the record of RMP2_PRIM_CYLINDER tables: the table that engine.obstacles(..., primitive="cylinder")
+    steers around is the one the plant simulates.  The axis is normalised in float64 (the device uses it as given) and the record
+    rounded once.  Refused: a wrong shape, a non-finite value, a zero axis, radius <= 0, half height < 0, more than
+    MAX_OBSTACLE_CYLINDERS rows."""
+    a = np.asarray(rows, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((0, 8), np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError(f"cylinder obstacles must be rows (cx, cy, cz, radius, ux, uy, uz, half_height), got shape {list(a.shape)}")
+    if len(a) > MAX_OBSTACLE_CYLINDERS:
+        raise ValueError(f"{len(a)} cylinder obstacles, at most {MAX_OBSTACLE_CYLINDERS}")
+    if not np.isfinite(a).all():
+        raise ValueError("cylinder obstacles: a value is not finite")
+    if (a[:, 3] <= 0).any():
+        raise ValueError(f"cylinder obstacles: row {int(np.argmax(a[:, 3] <= 0))} has a radius <= 0")
+    if (a[:, 7] < 0).any():
+        raise ValueError(f"cylinder obstacles: row {int(np.argmax(a[:, 7] < 0))} has a negative half height")
+    length = np.linalg.norm(a[:, 4:7], axis=1)
+    if (length == 0).any():
+        raise ValueError(f"cylinder obstacles: row {int(np.argmax(length == 0))} has a zero axis")
+    out = a.copy()
+    out[:, 4:7] /= length[:, None]
+    out = out.astype(np.float32)
+    if not np.isfinite(out).all():
+        raise ValueError("cylinder obstacles: a value is not finite in float32")
+    return out
+
+
 # ---- convex-hull link geometry (simulation.py:462-484: PyBullet loads each .obj collision mesh as its convex hull) ------------
 
 MAX_HULL_VERTICES = 512   # include/rmp2.h RMP2_MAX_HULL_VERTICES

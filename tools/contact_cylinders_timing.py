@@ -1,0 +1,147 @@
+"""Time the plant's step with exact flat-capped cylinder obstacles (include/rmp2.h rmp2_dynamics_step_contacts_cylinders) against
+the existing calls, on the workload and by the method of tools/contact_timing_common.py (the fleet, the timing loop, one process
+per measurement).  Prints ONE JSON line (profiles/contact_cylinders_timing.json).  Per fleet size:
+  (a) `self_us`: the existing rmp2_dynamics_step_contacts_self on tools/contact_self_timing.py's folded scene -- the 32-sphere
+      table, one floor 50 m below, seven capsules 50 m away, the Panda's whole urdf.contact_self_pairs, 256 states on which the
+      nearest self pair is between 1 cm inside and d_act, closing on it at 0.5 rad / s.  With --parent-lib this leg alternates
+      between the parent's library and this build (`self_us_parent`, `self_us_this`, `self_us_ok`: this build's median is not above
+      the parent's largest round times (1 + the parent's own relative spread); `self_bits_as_parent`): the kernel is the parent's.
+  (b) `cyl_far_us`: the new call on the same scene with configs.EXP06_CYLINDERS moved 50 m away: every cylinder trip ends at the
+      cull (`far_same_results`: the final state and status have (a)'s bits).
+  (c) `cyl_us`: the new call with the seven cylinders in place, from the workload's own start states (two robots of three touch a
+      sphere), self pairs on; `contact_fraction`, `overflow_fraction`: the status words after the call.
+  (c') `cyl_nocull_us`: (c) on a library built with -DRMP2_CYLINDER_NO_CULL (--nocull-lib; `nocull_same_results`: (c)'s bits).
+  (d) `capsules_us`: (c)'s scene with the cylinders as urdf.cylinders_as_capsules(..., "covering") through the existing self call.
+`b_over_a`, `c_over_b`, `nocull_over_c`, `c_over_d`: the ratios of the medians.
+usage: python tools/contact_cylinders_timing.py [--parent-lib PATH] [--nocull-lib PATH] [--rounds N] [steps] [reps]"""
+import json
+import os
+import sys
+
+nocull_lib = None
+if "--nocull-lib" in sys.argv:
+    k = sys.argv.index("--nocull-lib")
+    nocull_lib = os.path.abspath(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+
+import contact_timing_common as T
+
+FAR_FLOOR = [[0.0, 0.0, 1.0, -50.0]]
+
+
+def far_capsules():
+    import numpy as np
+    return np.array([[50.0 + j, 3.0, 1.0, 0.05 + 0.01 * j, 50.0 + j, 3.0, 1.5, 0.0] for j in range(7)], np.float32)
+
+
+def cylinders(far):
+    import numpy as np
+    from riemannian_motion_policies_amd import configs, urdf as U
+    cyl = configs.EXP06_CYLINDERS.astype(np.float64)
+    if far:
+        cyl[:, 0] += 50.0
+    return U.cylinder_obstacles(cyl)
+
+
+def call(c, oc, cyl=None):
+    import torch
+    floor = torch.tensor(FAR_FLOOR, device=c.dev)
+    more = {} if cyl is None else {"contact_cylinders": cyl}
+    c.eng.dynamics_step(c.qs, c.qds, c.u, T.DT, stop_out=c.stop, status_out=c.status, contacts=c.spheres, d_act=T.D_ACT,
+                        contact_planes=floor, contact_obstacle_capsules=oc, contact_self=True, **more, **c.step)
+
+
+def folded(c):
+    """tools/contact_self_timing.py's folded start states: the fleet starts from them, closing on the nearest self pair."""
+    import numpy as np
+    import torch
+    import contact_self_reference as SR
+    import joint_stops_reference as JR
+    from riemannian_motion_policies_amd import urdf as U
+    pairs = U.contact_self_pairs(c.table)
+    lo, hi = JR.table_limits(c.table)
+    rng = np.random.default_rng(616)
+    qs, rows = [], []
+    for _ in range(40):
+        q = (lo + (hi - lo) * rng.uniform(0.02, 0.98, (4096, len(lo)))).astype(np.float32)
+        d = SR.self_rows(c.table, c.caps, pairs, 0, 0, 0, q.astype(np.float64))
+        g = d["gap"].min(1)
+        ok = (g > -0.01) & (g <= T.D_ACT)
+        qs.append(q[ok])
+        rows.append(d["J"][np.arange(len(q)), d["gap"].argmin(1)][ok])
+        if sum(len(x) for x in qs) >= 256:
+            break
+    else:
+        raise SystemExit("no 256 folded states in 40 draws of 4096")
+    q, J = np.concatenate(qs)[:256], np.concatenate(rows)[:256]
+    qd = (-0.5 * J / np.abs(J).max(1, keepdims=True)).astype(np.float32)
+    c.q.copy_(torch.from_numpy(np.tile(q, (c.R // len(q), 1))).to(c.dev))
+    c.qd.copy_(torch.from_numpy(np.tile(qd, (c.R // len(q), 1))).to(c.dev))
+    c.u.zero_()
+    c.eng.set_contact_self_pairs(pairs)
+
+
+def fractions(c, suffix=""):
+    st = c.status.cpu().numpy()
+    c.row.update({"contact_fraction" + suffix: round(float((st & 4 != 0).mean()), 4),
+                  "overflow_fraction" + suffix: round(float((st & 8 != 0).mean()), 4)})
+
+
+def leg_self(c):
+    import torch
+    folded(c)
+    oc = torch.from_numpy(far_capsules()).to(c.dev)
+    c.time("self_us", lambda: call(c, oc))
+    c.final("self_bits", lambda: call(c, oc))
+    fractions(c, "_fold")
+
+
+def leg_far(c):
+    import torch
+    folded(c)
+    oc = torch.from_numpy(far_capsules()).to(c.dev)
+    cyl = torch.from_numpy(cylinders(True)).to(c.dev)
+    c.time("cyl_far_us", lambda: call(c, oc, cyl))
+    c.final("cyl_far_bits", lambda: call(c, oc, cyl))
+
+
+def leg_place(c, key="cyl"):
+    import torch
+    from riemannian_motion_policies_amd import urdf as U
+    c.eng.set_contact_self_pairs(U.contact_self_pairs(c.table))
+    oc = torch.from_numpy(far_capsules()).to(c.dev)
+    cyl = torch.from_numpy(cylinders(False)).to(c.dev)
+    c.time(key + "_us", lambda: call(c, oc, cyl))
+    c.final(key + "_bits", lambda: call(c, oc, cyl))
+    fractions(c, "" if key == "cyl" else "_" + key)
+    c.row["finite_" + key] = bool(torch.isfinite(c.qs).all())
+
+
+def leg_capsules(c):
+    import numpy as np
+    import torch
+    from riemannian_motion_policies_amd import urdf as U
+    c.eng.set_contact_self_pairs(U.contact_self_pairs(c.table))
+    oc = torch.from_numpy(np.concatenate([far_capsules(), U.cylinders_as_capsules(cylinders(False), "covering")])).to(c.dev)
+    c.time("capsules_us", lambda: call(c, oc))
+    fractions(c, "_capsules")
+
+
+LEGS = {"self": leg_self, "far": leg_far, "place": leg_place, "nocull": lambda c: leg_place(c, "cyl_nocull"), "capsules": leg_capsules}
+parent_lib, rounds, child, steps, reps = T.parse(__doc__)
+if child is not None:
+    T.main(__file__, "contact_cylinders_timing", LEGS, __doc__)          # (measures the leg, prints its rows and exits)
+result = T.main(__file__, "contact_cylinders_timing", {"self": leg_self}, __doc__)          # (a): alternating with the parent's library
+for name in ("far", "place", "capsules") + (("nocull",) if nocull_lib else ()):          # (b), (c), (d), (c'): this build only
+    for row, got in zip(result["sizes"], T.run_child(__file__, name, steps, reps, nocull_lib if name == "nocull" else None)):
+        row.update({k: v for k, v in got.items() if k != "robots"})
+result["cylinders"] = 7
+for row in result["sizes"]:
+    row["far_same_results"] = row["self_bits"] == row["cyl_far_bits"]
+    row["b_over_a"] = round(row["cyl_far_us"] / row["self_us"], 3)
+    row["c_over_b"] = round(row["cyl_us"] / row["cyl_far_us"], 3)
+    row["c_over_d"] = round(row["cyl_us"] / row["capsules_us"], 3)
+    if nocull_lib:
+        row["nocull_same_results"] = row["cyl_bits"] == row["cyl_nocull_bits"]
+        row["nocull_over_c"] = round(row["cyl_nocull_us"] / row["cyl_us"], 3)
+print(json.dumps(result))
