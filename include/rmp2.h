@@ -928,6 +928,46 @@ int rmp2_dynamics_step_contacts_cylinders(rmp2_handle *h, float *q, float *qd, c
                                           float *contact_out, float *contact_lambda, int32_t *contact_pair, uint32_t *status_out,
                                           int32_t R, void *stream);
 
+/* ---- per-robot cylinder lists over a shared cylinder pool -----------------------------------------------------------------------
+ * rmp2_dynamics_step_contacts_cylinder_lists is rmp2_dynamics_step_contacts_cylinders -- its argument list -- with cylinders [Y][8]
+ * a POOL (16-byte aligned, 0 <= Y <= RMP2_MAX_CYLINDER_POOL) and, after Y, every robot's own list over it: cyl_offset (device
+ * [R + 1]) and cyl_index (device [cyl_offset[R]]) in the layout of rmp2_obstacles.csr_offset / csr_index.  Robot r's cylinders are
+ * cylinders[cyl_index[i]], i in [cyl_offset[r], cyl_offset[r + 1]), in list order, at most RMP2_MAX_CYLINDER_LIST of them: the arrays
+ * built for the policy's ragged cylinder mode (RMP2_OBS_RAGGED_SPHERES with RMP2_PRIM_CYLINDER) feed the plant unchanged, with no
+ * copy.  The sphere arguments keep both of their forms, independently: the shared table (csr_offset == csr_index == NULL) or lists.
+ * Per pair everything is the cylinders call's word for word -- segment_cylinder, the surface's outward normal, g = sd - r_f, the
+ * row, b = -max(g, 0) / dt, the cull, the RMP2_MAX_CONTACTS slots and their tie rule, solver, landing, clamps, outputs and status
+ * flags; the axis is used as given.  The PAIR INDEX stays RMP2_CONTACT_PAIR_CYLINDER_BASE(F, K, P, C) + f Y + y with Y the POOL's
+ * size and y the POOL index, so that the RMP2_CONTACT_PAIR_CYLINDER_* macros decode it unchanged; at most
+ * 32 * 2^24 + 512 + 1024 + 1024 + 32 * 2^22 < 2^31, within int32.
+ * Contracts, as for the sphere lists: a robot with an empty list gets the results the same call gives it with Y = 0; a robot whose
+ * list is strictly ascending gets the results of the cylinders call on the compacted table cylinders[list], pairs mapped through
+ * the list (a monotone map keeps the tie order); a robot's results depend on no other robot's list, not on R and not on its lane;
+ * an unsorted list gives the same candidate set but possibly another slot order and other bits; a repeated index gives two pairs
+ * with identical rows.  On the device, BIT-LEVEL equality is promised among the kernels of this call only -- a robot's bits do not
+ * depend on its lane, on the fleet beside it or on where in the pool its records lie; against the cylinders call (other kernels,
+ * whose fma contraction is the compiler's) the candidate pairs and the status flags are equal and the floats agree to rounding.
+ * INVALID LISTS are refused per robot on the device, by the sphere lists' rule and with their status: a negative start or length,
+ * more than RMP2_MAX_CYLINDER_LIST entries, or an entry outside [0, Y) (with Y == 0: any entry).  Every entry is range-checked once
+ * per launch, before anything is read through it.  The refused robot's rows are NaN, its contact_pair -1 and its status_out
+ * exactly RMP2_CONTACT_LIST_INVALID -- an invalid sphere list and an invalid cylinder list give the same word --, other robots are
+ * untouched.  A non-finite value in a cylinder record makes the robots that LIST it NaN, not the fleet.
+ * Beyond the cylinders call's refusals, with the pool's cap in place of the table's: cyl_offset or cyl_index NULL with R > 0,
+ * Y > RMP2_MAX_CYLINDER_POOL, a null or misaligned pool with Y > 0: RMP2_ERR_INVALID_ARGUMENT.  Robots of at most 9 dofs
+ * (RMP2_ERR_UNSUPPORTED beyond).  Stream-ordered, no allocation, no read-back of cyl_offset: capturable. */
+#define RMP2_MAX_CYLINDER_LIST 32          /* entries per robot (RMP2_MAX_OBSTACLE_CYLINDERS) */
+#define RMP2_MAX_CYLINDER_POOL (1 << 22)   /* records in the pool; 32 * Y must fit the int32 pair index beside the other kinds */
+int rmp2_dynamics_step_contacts_cylinder_lists(rmp2_handle *h, float *q, float *qd, const float *u, int32_t drive,
+                                               const float *tau_limit, const float *q_lower, const float *q_upper,
+                                               const float *spheres, int32_t K, const int32_t *csr_offset, const int32_t *csr_index,
+                                               const float *planes, int32_t P, const float *obstacle_capsules /* device [C][8] */,
+                                               int32_t C, const float *cylinders /* device [Y][8], the pool */, int32_t Y,
+                                               const int32_t *cyl_offset /* device [R+1] */,
+                                               const int32_t *cyl_index /* device [cyl_offset[R]] */, int32_t self_pairs, float d_act,
+                                               float dt, int32_t substeps, float *qdd_out, float *tau_out, float *stop_out,
+                                               float *contact_out, float *contact_lambda, int32_t *contact_pair, uint32_t *status_out,
+                                               int32_t R, void *stream);
+
 /* The control steps of TWO engines (two robot types of one fleet shard: BASELINE config 5) issued together: arguments as two
  * rmp2_step calls, `stream` shared.  Where a fused instantiation exists for the pair -- a 2-dof and a 3..9-dof robot type,
  * plain steps on shared or ragged sphere tables, both fleets beyond 8 192 robots -- the two steps are ONE grid (the first

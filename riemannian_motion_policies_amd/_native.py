@@ -107,6 +107,10 @@ def lib():
         if hasattr(l, "rmp2_dynamics_step_contacts_cylinders"):   # (likewise for a diagnostic RMP2_LIB built before the cylinders)
             # ... planes, P, obstacle capsules, C, cylinders, Y, self_pairs
             l.rmp2_dynamics_step_contacts_cylinders.argtypes = head + lists + [C.c_void_p, C.c_int32] * 3 + [C.c_int32] + tail
+        if hasattr(l, "rmp2_dynamics_step_contacts_cylinder_lists"):   # (likewise for a diagnostic RMP2_LIB built before them)
+            # ... planes, P, obstacle capsules, C, the cylinder pool, Y, cyl_offset, cyl_index, self_pairs
+            l.rmp2_dynamics_step_contacts_cylinder_lists.argtypes = (head + lists + [C.c_void_p, C.c_int32] * 3 + lists + [C.c_int32]
+                                                                     + tail)
     l.rmp2_differentiate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     l.rmp2_differentiate_euler.argtypes = l.rmp2_differentiate.argtypes

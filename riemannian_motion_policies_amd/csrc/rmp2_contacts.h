@@ -42,6 +42,9 @@
 // body with planes, capsules and self pairs on, behind rmp2_dynamics_step_contacts_self_kernel<N, SLOTS, LIST>.
 // A fifth, exact flat-capped cylinder obstacles (rmp2_dynamics_step_contacts_cylinders; NoCylinders / CylinderTable), is the body
 // with all of those on and the cylinder trips after the self trips, behind rmp2_dynamics_step_contacts_cylinders_kernel<N, SLOTS, LIST>.
+// A sixth, every robot's own cylinder list over a shared pool (rmp2_dynamics_step_contacts_cylinder_lists; CylinderList in
+// CylinderTable's place), is that body with the cylinder fetch a gather, behind rmp2_dynamics_step_contacts_cylinder_lists_kernel<N,
+// SLOTS, LIST> -- LIST is still the SPHERES' form, the two are independent.
 #pragma once
 #include <type_traits>
 
@@ -249,11 +252,106 @@ constexpr int contact_self_words(int n) {
 // skip.  -DRMP2_CYLINDER_NO_CULL (tests/contact_cylinders_driver.cpp and tools/contact_cylinders_timing.py only) leaves it out.
 struct NoCylinders {
   static constexpr bool kOn = false;
+  static constexpr bool kList = false;
 };
 struct CylinderTable {
   const float* cylinders;
   int Y, F, P, C;
   static constexpr bool kOn = true;
+  static constexpr bool kList = false;
+};
+
+// One robot's list over a shared pool of cylinder records (rmp2_dynamics_step_contacts_cylinder_lists): records pool[index[i]],
+// i = 0 .. len - 1, in list order, as SphereList is for the spheres.  The arithmetic of a cylinder trip is CylinderTable's; the
+// fetch is a gather -- a record is two 16-byte loads at the lane's own address (the pool is 16-byte aligned) -- and the trip count
+// is the lane's own.  The cursor (begin / next) keeps the next entry's record and the index after it in flight while the current
+// entry is evaluated.  scan() range-checks every entry BEFORE anything is read through it, adds the robot's own records to the poison sum
+// and empties an invalid list: the cursor never sees an entry that was not checked.  Y is the POOL's size and the pair index counts
+// in it: F (K + 2 P + C) + F F + f Y + (the pool index).
+struct CylinderRec {
+  float4 a, b;   // (centre, radius), (unit axis, half height)
+};
+struct CylinderList {
+  const float* cylinders;   // the pool [Y][8]
+  int Y;
+  const int32_t* index;     // the robot's entries
+  int len;                  // how many; < 0 or > RMP2_MAX_CYLINDER_LIST: invalid
+  int F, P, C;
+  // the cursor (begin / next): the record of the entry that next() hands out next, that entry's index and the index after it, and
+  // the index of the entry handed out last.  State of the list itself -- the routines that walk it take the list by value
+  CylinderRec rec;
+  int k, k_next, k_now;
+  float held[8];
+  static constexpr bool kOn = true;
+  static constexpr bool kList = true;
+  __host__ __device__ CylinderRec record(int k) const {
+    CylinderRec r;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float4* p = reinterpret_cast<const float4*>(cylinders + 8 * (size_t)k);
+    r.a = p[0];
+    r.b = p[1];
+#else
+    __builtin_memcpy(&r, cylinders + 8 * (size_t)k, sizeof(r));
+#endif
+    return r;
+  }
+  __host__ __device__ float scan(bool& invalid) {
+    invalid = len < 0 || len > RMP2_MAX_CYLINDER_LIST;
+    if (invalid) len = 0;
+    float p = 0.f;
+    for (int i = 0; i < len; ++i) {
+      const int k = index[i];
+      if ((uint32_t)k >= (uint32_t)Y) {   // (also a negative entry, and every entry when Y == 0)
+        invalid = true;
+        continue;
+      }
+      const CylinderRec r = record(k);
+      p += r.a.x * 0.f;
+      p += r.a.y * 0.f;
+      p += r.a.z * 0.f;
+      p += r.a.w * 0.f;
+      p += r.b.x * 0.f;
+      p += r.b.y * 0.f;
+      p += r.b.z * 0.f;
+      p += r.b.w * 0.f;
+    }
+    if (invalid) len = 0;
+    return p;
+  }
+  __host__ __device__ void begin() {
+    k = k_next = k_now = 0;
+    rec.a = rec.b = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (len > 0) {
+      k = index[0];
+      rec = record(k);
+    }
+    if (len > 1) k_next = index[1];
+  }
+  // entry j's record -- its eight words in `held`, returned, where the table form has a pointer into the table -- and its index in
+  // the pool in k_now; the fetches of entry j + 1's record and of entry j + 2's index are issued before the caller uses what it got
+  __host__ __device__ const float* next(int j) {
+    held[0] = rec.a.x, held[1] = rec.a.y, held[2] = rec.a.z, held[3] = rec.a.w;
+    held[4] = rec.b.x, held[5] = rec.b.y, held[6] = rec.b.z, held[7] = rec.b.w;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // as SphereList::Cursor::next: the eight words enter the trip defined here, in the table form's load order, and not as
+    // loop-carried registers, so that the contraction into fma meets them where the table form's loads stand
+    asm volatile("" : "+v"(held[0]));
+    asm volatile("" : "+v"(held[1]));
+    asm volatile("" : "+v"(held[2]));
+    asm volatile("" : "+v"(held[3]));
+    asm volatile("" : "+v"(held[4]));
+    asm volatile("" : "+v"(held[5]));
+    asm volatile("" : "+v"(held[6]));
+    asm volatile("" : "+v"(held[7]));
+#endif
+    k_now = k;
+    if (j + 1 < len) {
+      k = k_next;
+      rec = record(k);
+    }
+    if (j + 2 < len) k_next = index[j + 2];
+    return held;
+  }
 };
 
 // The slot of a qualifying candidate (gap g, pair index idx) among the kept ones: a free slot, or the kept candidate of largest
@@ -406,7 +504,12 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
     if constexpr (Cp::kOn) trips += oc.C;
     if constexpr (Sp::kOn) trips += self_trips;   // ... then its self pairs
     const int cyl_first = trips;                  // ... then the Y cylinders
-    if constexpr (Cy::kOn) trips += cy.Y;
+    if constexpr (Cy::kList) {   // (the robot's own cylinders: the lane's trip count)
+      cy.begin();
+      trips += cy.len;
+    } else if constexpr (Cy::kOn) {
+      trips += cy.Y;
+    }
     for (int s = 0; s < trips; ++s) {
       float c[3], rs;
       int sk = s;   // the record's index in the pool
@@ -458,7 +561,9 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
       float X[3], n[3], len, g;   // the point on the link's axis, the normal (of length len) and the gap
       if (cylinder) {
         if constexpr (Cy::kOn) {   // X, the surface's unit normal and the signed distance, from segment_cylinder as they are
-          const float* rec = cy.cylinders + 8 * (size_t)(s - cyl_first);
+          const float* rec;   // the record's eight words: in the table, or -- a list -- fetched through the cursor
+          if constexpr (Cy::kList) rec = cy.next(s - cyl_first);
+          else rec = cy.cylinders + 8 * (size_t)(s - cyl_first);
           const float4 ra = make_float4(rec[0], rec[1], rec[2], rec[3]), rb = make_float4(rec[4], rec[5], rec[6], rec[7]);
 #ifndef RMP2_CYLINDER_NO_CULL
           {   // the solid lies in the ball (centre, rho): no point of the segment is nearer than L (see CylinderTable)
@@ -494,7 +599,9 @@ __host__ __device__ inline int contact_candidates_from(const DevOp* ops, int n_o
       int idx = op.frame * src.pool() + sk;
       if constexpr (Cp::kOn) idx = capsule ? oc.F * (src.pool() + 2 * oc.P) + op.frame * oc.C + (s - K) : idx;
       if constexpr (Sp::kOn) idx = self ? oc.F * (src.pool() + 2 * oc.P + oc.C) + op.frame * sp.F + se : idx;
-      if constexpr (Cy::kOn)   // after the self block, which is reserved whether or not self pairs are on
+      if constexpr (Cy::kList)   // (the record's index in the POOL, of Y records)
+        idx = cylinder ? cy.F * (src.pool() + 2 * cy.P + cy.C) + cy.F * cy.F + op.frame * cy.Y + cy.k_now : idx;
+      else if constexpr (Cy::kOn)   // after the self block, which is reserved whether or not self pairs are on
         idx = cylinder ? cy.F * (src.pool() + 2 * cy.P + cy.C) + cy.F * cy.F + op.frame * cy.Y + (s - cyl_first) : idx;
       int put = -1;
       if (count < kMaxContacts) {
@@ -807,7 +914,8 @@ __host__ __device__ inline auto contact_source(const float* spheres, int K, cons
 // / pair_out [kMaxContacts]: null or the robot's rows.  lds / stride: room for contact_words(N) floats (with SelfPairs:
 // contact_self_words(N)).  The spheres are scanned
 // once, before the substeps: a non-finite record makes the robot NaN, an invalid list NaN with the status word
-// RMP2_CONTACT_LIST_INVALID alone (its substeps run on no spheres, and nothing is read through its entries).
+// RMP2_CONTACT_LIST_INVALID alone (its substeps run on no spheres, and nothing is read through its entries).  With Cy =
+// CylinderList the robot's cylinder list is scanned in the same place, by the same rule and with the same status word.
 template <int N, int SLOTS, bool LIST = false, class Pl = NoPlanes, class Cp = NoCapsules, class Sp = NoSelfPairs, class Cy = NoCylinders>
 __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, int n_ops, int n_dof, const float* inert,
                                                              const float base_acc[3], float* q_io, float* qd_io,
@@ -848,7 +956,11 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
   if constexpr (Cp::kOn) {   // a non-finite capsule value: every robot NaN
     for (int s = 0; s < 8 * oc.C; ++s) table_poison += oc.capsules[s] * 0.f;
   }
-  if constexpr (Cy::kOn) {   // a non-finite cylinder value: every robot NaN
+  if constexpr (Cy::kList) {   // a non-finite value in a record of the robot's own list: that robot NaN; an invalid list as above
+    bool cyl_invalid = false;
+    table_poison += cy.scan(cyl_invalid);
+    invalid = invalid || cyl_invalid;
+  } else if constexpr (Cy::kOn) {   // a non-finite cylinder value: every robot NaN
     for (int s = 0; s < 8 * cy.Y; ++s) table_poison += cy.cylinders[s] * 0.f;
   }
   uint32_t status = 0u;
@@ -1120,6 +1232,51 @@ rmp2_dynamics_step_contacts_cylinders_kernel(const DevProgram* __restrict__ prog
       status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, PlaneTable{planes, P, F},
       CapsuleTable{capsules, C, F, P}, SelfPairs{self_slot, self_begin, self_rec, n_self, F, nullptr},
       CylinderTable{cylinders, Y, F, P, C});
+}
+
+// The cylinder-list forms (rmp2_dynamics_step_contacts_cylinder_lists): the cylinder forms with every robot's own list over the
+// pool cylinders [Y][8] (CylinderList; cyl_offset / cyl_index laid out as csr_offset / csr_index), behind a kernel of its own, so
+// that the cylinder forms' kernels are what they were.  LIST: the spheres' form, as everywhere.  No LDS beyond the self forms'.
+template <int N, int SLOTS, bool LIST>
+__global__ void __launch_bounds__(kWave)
+rmp2_dynamics_step_contacts_cylinder_lists_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax,
+                                                  float ay, float az, float* q, float* qd, const float* __restrict__ u, int accel,
+                                                  const float* __restrict__ lim, const float* __restrict__ qlo,
+                                                  const float* __restrict__ qhi, const float* __restrict__ caps,
+                                                  const float* __restrict__ spheres, int K, const int32_t* __restrict__ csr_offset,
+                                                  const int32_t* __restrict__ csr_index, const float* __restrict__ planes, int P,
+                                                  const float* __restrict__ capsules, int C, const int32_t* __restrict__ self_slot,
+                                                  const int32_t* __restrict__ self_begin, const int32_t* __restrict__ self_rec,
+                                                  int n_self, const float* __restrict__ cylinders, int Y,
+                                                  const int32_t* __restrict__ cyl_offset, const int32_t* __restrict__ cyl_index,
+                                                  int F, float d_act, float dt, int substeps, float* __restrict__ qdd_out,
+                                                  float* __restrict__ tau_out, float* __restrict__ stop_out,
+                                                  float* __restrict__ contact_out, float* __restrict__ lambda_out,
+                                                  int32_t* __restrict__ pair_out, uint32_t* __restrict__ status_out, int R) {
+  static_assert(contact_self_words(N) * kWave * sizeof(float) <= 65536, "the per-lane storage of one wave must fit 64 KiB of LDS");
+  __shared__ float lds[contact_self_words(N) * kWave];
+  const int robot = blockIdx.x * kWave + threadIdx.x;
+  if (robot >= R) return;
+  const int n_dof = prog->n_dof;
+  const size_t row = (size_t)robot * n_dof;
+  const size_t crow = (size_t)robot * kMaxContacts;
+  const float base_acc[3] = {ax, ay, az};
+  const int32_t* list = nullptr;
+  int len = 0;
+  if constexpr (LIST) {
+    int beg;
+    len = contact_list_span(csr_offset, robot, beg);
+    list = csr_index + beg;
+  }
+  int cyl_beg;
+  const int cyl_len = contact_list_span(cyl_offset, robot, cyl_beg);   // (-1: no list; above the cap: as it is -- scan refuses both)
+  dynamics_step_contacts_robot<N, SLOTS, LIST, PlaneTable, CapsuleTable, SelfPairs, CylinderList>(
+      prog->ops, prog->n_ops, n_dof, inert, base_acc, q + row, qd + row, u + row, accel != 0, lim, qlo, qhi, caps, spheres, K, d_act,
+      dt, substeps, qdd_out ? qdd_out + row : nullptr, tau_out ? tau_out + row : nullptr, stop_out ? stop_out + row : nullptr,
+      contact_out ? contact_out + row : nullptr, lambda_out ? lambda_out + crow : nullptr, pair_out ? pair_out + crow : nullptr,
+      status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, PlaneTable{planes, P, F},
+      CapsuleTable{capsules, C, F, P}, SelfPairs{self_slot, self_begin, self_rec, n_self, F, nullptr},
+      CylinderList{cylinders, Y, cyl_index + cyl_beg, cyl_len, F, P, C});
 }
 #endif
 

@@ -5,7 +5,8 @@
 // rmp2_dynamics_step_contacts_capsules_kernel -- two more code objects, RMP2_TU_LIST = 0 and 1.  With RMP2_TU_SELF = 1 (and the
 // other two) it holds the self forms -- the handle's self pairs on as well, rmp2_dynamics_step_contacts_self_kernel -- two more.
 // With RMP2_TU_CYLINDERS = 1 (and the other three) it holds the cylinder forms -- the cylinder table on as well,
-// rmp2_dynamics_step_contacts_cylinders_kernel -- two more.
+// rmp2_dynamics_step_contacts_cylinders_kernel -- two more.  With RMP2_TU_CYLINDER_LISTS = 1 (and the other four) it holds the
+// cylinder-list forms -- every robot's own cylinder list over a pool, rmp2_dynamics_step_contacts_cylinder_lists_kernel -- two more.
 #include <cfloat>
 #include <cmath>
 
@@ -35,9 +36,41 @@
 #error "the cylinder forms run with the planes, the capsules and the self pairs on"
 #endif
 
+#ifndef RMP2_TU_CYLINDER_LISTS
+#define RMP2_TU_CYLINDER_LISTS 0
+#endif
+#if RMP2_TU_CYLINDER_LISTS && !RMP2_TU_CYLINDERS
+#error "the cylinder-list forms are cylinder forms"
+#endif
+
 namespace rmp2 {
 
-#if RMP2_TU_CYLINDERS
+#if RMP2_TU_CYLINDER_LISTS
+#if RMP2_TU_LIST
+RMP2_DECL_CONTACTS_CYLINDER_LISTS(launch_contacts_lists_cylinder_lists) {
+#else
+RMP2_DECL_CONTACTS_CYLINDER_LISTS(launch_contacts_table_cylinder_lists) {
+#endif
+  const dim3 grid((R + kWave - 1) / kWave), block(kWave);
+  const float* a = h->base_acc;
+  // the handle's pair tables, where the call asks for them (self_pairs); else the kernel reads none of them
+  const int n_ops = (int)h->full_op_frame.size(), n_self = self_pairs ? h->contact_self_n : 0;
+  const int32_t* slot = n_self ? h->d_contact_self : nullptr;
+  const int32_t* begin = n_self ? slot + n_ops : nullptr;
+  const int32_t* rec = n_self ? begin + n_ops + 1 : nullptr;
+  auto launch = [&](auto N) {
+    with_slots(h->n_slots_full, [&](auto S) {
+      hipLaunchKernelGGL((rmp2_dynamics_step_contacts_cylinder_lists_kernel<N, S, RMP2_TU_LIST != 0>), grid, block, 0, s,
+                         h->d_prog_full, h->d_inert, a[0], a[1], a[2], q, qd, u, accel, lim, qlo, qhi, h->d_contact_caps, spheres, K,
+                         csr_offset, csr_index, planes, P, capsules, C, slot, begin, rec, n_self, cylinders, Y, cyl_offset, cyl_index,
+                         h->n_frames, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, lambda_out, pair_out, status_out,
+                         R);
+    });
+  };
+  if (h->n_template == 2) launch(std::integral_constant<int, 2>());
+  else launch(std::integral_constant<int, 9>());
+}
+#elif RMP2_TU_CYLINDERS
 #if RMP2_TU_LIST
 RMP2_DECL_CONTACTS_CYLINDERS(launch_contacts_lists_cylinders) {
 #else

@@ -1497,6 +1497,9 @@ constexpr decltype(&launch_contacts_table_self) kLaunchContactsSelf[2] = {launch
 // ... and with flat-capped cylinder obstacles as well: [LIST]
 constexpr decltype(&launch_contacts_table_cylinders) kLaunchContactsCylinders[2] = {launch_contacts_table_cylinders,
                                                                                     launch_contacts_lists_cylinders};
+// ... and with every robot's own cylinder list over a cylinder pool: [LIST] (the spheres' form)
+constexpr decltype(&launch_contacts_table_cylinder_lists) kLaunchContactsCylinderLists[2] = {launch_contacts_table_cylinder_lists,
+                                                                                             launch_contacts_lists_cylinder_lists};
 
 // The host path of the six contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
 // each entry point keeps its `what` and its own rules (table: K <= RMP2_MAX_CONTACT_SPHERES; lists: both CSR arrays, the pool
@@ -1504,19 +1507,24 @@ constexpr decltype(&launch_contacts_table_cylinders) kLaunchContactsCylinders[2]
 // table; self: the capsules' rules, the pairs are the handle's).  The planes entry always runs a PLANES kernel, P == 0 included;
 // the capsules entry always a capsule kernel (planes and capsules on), P == 0 and C == 0 included; the self entry always a self
 // kernel (planes, capsules and self on), no pairs set included; the cylinders entry (the self call's rules, Y, the cylinder table
-// and the self_pairs flag) always a cylinder kernel, Y == 0 included.
-enum ContactForm { kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules, kContactsSelf, kContactsCylinders };
+// and the self_pairs flag) always a cylinder kernel, Y == 0 included; the cylinder-lists entry (the cylinders call's rules with the
+// pool's cap on Y, and both cylinder CSR arrays) always a cylinder-list kernel.
+enum ContactForm {
+  kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules, kContactsSelf, kContactsCylinders, kContactsCylinderLists
+};
 
 int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float* q, float* qd, const float* u, int32_t drive,
                        const float* tau_limit, const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
                        const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
                        const float* capsules, int32_t C, float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out,
                        float* stop_out, float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
-                       int32_t R, void* stream, const float* cylinders = nullptr, int32_t Y = 0, int32_t self_pairs = 1) {
+                       int32_t R, void* stream, const float* cylinders = nullptr, int32_t Y = 0, int32_t self_pairs = 1,
+                       const int32_t* cyl_offset = nullptr, const int32_t* cyl_index = nullptr) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   const std::string w = what;
   if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
-  const bool with_cylinders = form == kContactsCylinders;   // (the self call's rules; always a cylinder kernel, Y == 0 included)
+  const bool cylinder_lists = form == kContactsCylinderLists;   // (the cylinders call's rules; the pool's cap on Y)
+  const bool with_cylinders = form == kContactsCylinders || cylinder_lists;   // (the self call's rules; always a cylinder kernel, Y == 0 included)
   const bool with_self = form == kContactsSelf || with_cylinders;   // (the capsules' rules; always a self kernel, no pairs set included)
   const bool with_capsules = form == kContactsCapsules || with_self;
   const bool with_planes = form == kContactsPlanes || with_capsules;
@@ -1546,11 +1554,12 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
   }
   if (with_cylinders) {
     if (Y < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y < 0");
-    if (Y > RMP2_MAX_OBSTACLE_CYLINDERS)
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y > " + std::to_string(RMP2_MAX_OBSTACLE_CYLINDERS));
-    if (Y > 0 && !cylinders) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null cylinder table with Y > 0");
+    const int y_max = cylinder_lists ? RMP2_MAX_CYLINDER_POOL : RMP2_MAX_OBSTACLE_CYLINDERS;
+    if (Y > y_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y > " + std::to_string(y_max));
+    const std::string table = cylinder_lists ? "cylinder pool" : "cylinder table";
+    if (Y > 0 && !cylinders) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null " + table + " with Y > 0");
     if (Y > 0 && ((uintptr_t)cylinders & 15u))
-      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the cylinder table must be 16-byte aligned");
+      return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the " + table + " must be 16-byte aligned");
     if (self_pairs != 0 && self_pairs != 1) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": self_pairs must be 0 or 1");
   }
   if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": d_act must be finite and >= 0");
@@ -1561,11 +1570,16 @@ int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float
                 w + ": robots of more than 9 dofs are not supported (this one has " + std::to_string(h->n_dof) + ")");
   bool launch;
   const bool others_ok = (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres) &&
-                         (form != kContactsLists || (csr_offset && csr_index));
+                         (form != kContactsLists || (csr_offset && csr_index)) && (!cylinder_lists || (cyl_offset && cyl_index));
   if (int rc = step_rows_check(h, what, q, qd, u, others_ok, R, launch)) return rc;
   if (!launch) return RMP2_OK;
   // (N in {2, 9} by the handle's template size, SLOTS by its program)
-  if (with_cylinders)
+  if (cylinder_lists)
+    kLaunchContactsCylinderLists[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
+                                        csr_index, planes, P, capsules, C, cylinders, Y, cyl_offset, cyl_index, self_pairs, d_act, dt,
+                                        substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R,
+                                        (hipStream_t)stream);
+  else if (with_cylinders)
     kLaunchContactsCylinders[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
                                     csr_index, planes, P, capsules, C, cylinders, Y, self_pairs, d_act, dt, substeps, qdd_out, tau_out,
                                     stop_out, contact_out, contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
@@ -3263,6 +3277,20 @@ int rmp2_dynamics_step_contacts_cylinders(rmp2_handle* h, float* q, float* qd, c
                             q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps, qdd_out,
                             tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream, cylinders, Y,
                             self_pairs);
+}
+
+int rmp2_dynamics_step_contacts_cylinder_lists(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive,
+                                               const float* tau_limit, const float* q_lower, const float* q_upper,
+                                               const float* spheres, int32_t K, const int32_t* csr_offset, const int32_t* csr_index,
+                                               const float* planes, int32_t P, const float* obstacle_capsules, int32_t C,
+                                               const float* cylinders, int32_t Y, const int32_t* cyl_offset, const int32_t* cyl_index,
+                                               int32_t self_pairs, float d_act, float dt, int32_t substeps, float* qdd_out,
+                                               float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
+                                               int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
+  return contacts_step_impl(h, "dynamics step with contact cylinder lists", kContactsCylinderLists, q, qd, u, drive, tau_limit,
+                            q_lower, q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps,
+                            qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream, cylinders, Y,
+                            self_pairs, cyl_offset, cyl_index);
 }
 
 }  // extern "C"

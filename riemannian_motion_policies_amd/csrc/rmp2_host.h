@@ -214,4 +214,14 @@ RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_self);
             int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
 RMP2_DECL_CONTACTS_CYLINDERS(launch_contacts_table_cylinders);
 RMP2_DECL_CONTACTS_CYLINDERS(launch_contacts_lists_cylinders);
+// the cylinder-list forms (rmp2_dynamics_step_contacts_cylinder_lists): the cylinder forms with every robot's own list over a
+// cylinder pool (cyl_offset / cyl_index), [LIST] still the spheres' form; two more
+#define RMP2_DECL_CONTACTS_CYLINDER_LISTS(NAME)                                                                                   \
+  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
+            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
+            int P, const float* capsules, int C, const float* cylinders, int Y, const int32_t* cyl_offset,                        \
+            const int32_t* cyl_index, int self_pairs, float d_act, float dt, int substeps, float* qdd_out, float* tau_out,        \
+            float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
+RMP2_DECL_CONTACTS_CYLINDER_LISTS(launch_contacts_table_cylinder_lists);
+RMP2_DECL_CONTACTS_CYLINDER_LISTS(launch_contacts_lists_cylinder_lists);
 }  // namespace rmp2

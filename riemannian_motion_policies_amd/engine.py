@@ -26,6 +26,8 @@ CONTACT_KIND_CAPSULE = 2
 CONTACT_KIND_SELF = 3          # include/rmp2.h RMP2_CONTACT_KIND_SELF: a pair of the robot's own link capsules
 MAX_CONTACT_SELF_FRAMES = 22   # include/rmp2.h RMP2_MAX_CONTACT_SELF_FRAMES: distinct partner frames of set_contact_self_pairs
 CONTACT_KIND_CYLINDER = 4      # include/rmp2.h RMP2_CONTACT_KIND_CYLINDER: a link capsule against a flat-capped cylinder obstacle
+MAX_CYLINDER_LIST = 32         # include/rmp2.h RMP2_MAX_CYLINDER_LIST: entries per robot of dynamics_step(contact_cylinder_lists=)
+MAX_CYLINDER_POOL = 1 << 22    # include/rmp2.h RMP2_MAX_CYLINDER_POOL: records in its pool
 
 
 def contact_pair_split(pair: int, n_frames: int, K: int, P: int, C: int = 0, self_pairs: bool = False, cylinders: int = 0):
@@ -678,7 +680,7 @@ class Engine:
                       contact_lambda_out: Optional[torch.Tensor] = None, contact_pair_out: Optional[torch.Tensor] = None,
                       contact_lists=None, contact_planes: Optional[torch.Tensor] = None,
                       contact_obstacle_capsules: Optional[torch.Tensor] = None, contact_self: bool = False,
-                      contact_cylinders: Optional[torch.Tensor] = None) -> None:
+                      contact_cylinders: Optional[torch.Tensor] = None, contact_cylinder_lists=None) -> None:
         """The plant's step (include/rmp2.h rmp2_dynamics_step) on the current stream, IN PLACE on q and qd [R, n] (contiguous
         fp32 on the engine's device): `substeps` times qdd = forward dynamics; qd += dt qdd; q += dt qd.  drive="accel": u is the
         policy's qdd_des and the applied torque is the inverse dynamics of it at every substep's state, clamped by tau_limit;
@@ -722,7 +724,16 @@ class Engine:
         obstacles(..., primitive="cylinder") hands to the policy.  One row per link capsule and cylinder, at the point of the link's
         axis nearest the cylinder, along the outward normal of the cylinder's surface; contact_pair_out holds n_frames * (K + 2 P +
         C) + n_frames ** 2 + frame * Y + cylinder for them (contact_pair_split(..., cylinders=Y)).  contact_self says whether the
-        handle's self pairs take part.  Without it the call takes the routes above, unchanged."""
+        handle's self pairs take part.  Without it the call takes the routes above, unchanged.
+        contact_cylinder_lists = (cyl_offset [R + 1], cyl_index) int32 on the engine's device, with contact_cylinders = a POOL [Y, 8]
+        (Y up to MAX_CYLINDER_POOL): every robot's own cylinders, robot r's being contact_cylinders[cyl_index[cyl_offset[r]:
+        cyl_offset[r + 1]]] (at most MAX_CYLINDER_LIST of them; urdf.cylinder_scenes builds the three arrays) -- the arrays of
+        obstacles(spheres=pool, csr_offset=, csr_index=, primitive="cylinder") feed the plant unchanged (include/rmp2.h
+        rmp2_dynamics_step_contacts_cylinder_lists).  contacts= / contact_lists= keep both of their forms beside it.
+        contact_pair_out stays ... + frame * Y + the POOL index (contact_pair_split(..., cylinders=Y)).  The lists are checked on the
+        device like contact_lists: a robot with an invalid list gets NaN rows and status_out == CONTACT_LIST_INVALID, a robot that
+        lists a non-finite record NaN rows; nothing is read back, the call stays capturable.  Without it every route is the one
+        above."""
         _require_resident(self.device, q=q, qd=qd)
         drives = {"torque": 0, "accel": 1}
         if drive not in drives:
@@ -741,6 +752,8 @@ class Engine:
                                   or tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous int32 {list(shape)} tensor on {self.device}")
 
+        if contact_cylinder_lists is not None and contact_cylinders is None:
+            raise ValueError("contact_cylinder_lists needs contact_cylinders (the pool the lists index)")
         if (contacts is not None or contact_planes is not None or contact_obstacle_capsules is not None or contact_self
                 or contact_cylinders is not None):
             P = C = Y = 0
@@ -751,7 +764,10 @@ class Engine:
                     raise ValueError("contact_cylinders must be a contiguous fp32 [Y, 8] tensor (centre, radius, unit axis, half height), "
                                      f"got {list(cyl.shape)}")
                 Y = int(cyl.shape[0])
-                if Y > MAX_OBSTACLE_CYLINDERS:
+                if contact_cylinder_lists is not None:
+                    if Y > MAX_CYLINDER_POOL:
+                        raise ValueError(f"contact_cylinders holds {Y} cylinders, at most {MAX_CYLINDER_POOL} in a pool")
+                elif Y > MAX_OBSTACLE_CYLINDERS:
                     raise ValueError(f"contact_cylinders holds {Y} cylinders, at most {MAX_OBSTACLE_CYLINDERS}")
             if contact_obstacle_capsules is not None:
                 oc = contact_obstacle_capsules
@@ -785,25 +801,36 @@ class Engine:
             check_int("contact_pair_out", contact_pair_out, (R, MAX_CONTACTS))
             check_int("status_out", status_out, (R,))
             lower, upper = (None, None) if q_limits is None else self._q_limits_device(q_limits)
-            csr_offset = csr_index = None
-            if contact_lists is not None:
+            def csr_pair(what, names, pair):
                 try:
-                    csr_offset, csr_index = contact_lists
+                    offset, index = pair
                 except (TypeError, ValueError):
-                    raise ValueError("contact_lists must be a pair (csr_offset, csr_index)") from None
-                for name, t, shape in (("csr_offset", csr_offset, (R + 1,)), ("csr_index", csr_index, None)):
+                    raise ValueError(f"{what} must be a pair ({names[0]}, {names[1]})") from None
+                for name, t, shape in ((names[0], offset, (R + 1,)), (names[1], index, None)):
                     if (not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.int32
                             or not t.is_contiguous() or (t.dim() != 1 if shape is None else tuple(t.shape) != shape)):
-                        raise ValueError(f"contact_lists {name} must be a contiguous int32 {'1-D' if shape is None else list(shape)} "
+                        raise ValueError(f"{what} {name} must be a contiguous int32 {'1-D' if shape is None else list(shape)} "
                                          f"tensor on {self.device}")
-                if csr_index.numel() == 0:   # every list empty: the C ABI still wants a readable pointer (it cannot see the counts)
-                    csr_index = self._empty_index   # (made by set_contact_capsules; without capsules the call is refused anyway)
+                if index.numel() == 0:   # every list empty: the C ABI still wants a readable pointer (it cannot see the counts)
+                    index = self._empty_index   # (made by set_contact_capsules; without capsules the call is refused anyway)
+                return offset, index
+
+            csr_offset = csr_index = None
+            if contact_lists is not None:
+                csr_offset, csr_index = csr_pair("contact_lists", ("csr_offset", "csr_index"), contact_lists)
             head = (self._h, q.data_ptr(), qd.data_ptr(), u.data_ptr(), drives[drive], ptr(lim), ptr(lower), ptr(upper),
                     contacts.data_ptr() if K else None, K)
             tail = (float(d_act), float(dt), int(substeps), ptr(qdd_out), ptr(tau_out), ptr(stop_out), ptr(contact_out),
                     ptr(contact_lambda_out), ptr(contact_pair_out), ptr(status_out), R, s)
             lists = (ptr(csr_offset), ptr(csr_index))
-            if contact_cylinders is not None:
+            if contact_cylinder_lists is not None:
+                cyl_offset, cyl_index = csr_pair("contact_cylinder_lists", ("cyl_offset", "cyl_index"), contact_cylinder_lists)
+                rc = self._lib.rmp2_dynamics_step_contacts_cylinder_lists(*head, *lists, contact_planes.data_ptr() if P else None, P,
+                                                                          contact_obstacle_capsules.data_ptr() if C else None, C,
+                                                                          contact_cylinders.data_ptr() if Y else None, Y,
+                                                                          ptr(cyl_offset), ptr(cyl_index), 1 if contact_self else 0,
+                                                                          *tail)
+            elif contact_cylinders is not None:
                 rc = self._lib.rmp2_dynamics_step_contacts_cylinders(*head, *lists, contact_planes.data_ptr() if P else None, P,
                                                                      contact_obstacle_capsules.data_ptr() if C else None, C,
                                                                      contact_cylinders.data_ptr() if Y else None, Y,

@@ -566,6 +566,27 @@ def cylinder_obstacles(rows) -> np.ndarray:
     return out
 
 
+def cylinder_scenes(scenes):
+    """Per-robot cylinder scenes as ONE pool and ONE CSR pair: scenes is a sequence of R row arrays [n_r, 8] (cylinder_obstacles'
+    rows; configs.cylinder_record / configs.sample_cylinders rows qualify; n_r = 0 allowed) -> (pool [Y, 8] float32, csr_offset
+    int32 [R + 1], csr_index int32 [Y]), the scenes' records one after the other and every robot listing its own, ascending.  The
+    three arrays feed both Engine.obstacles(spheres=pool, csr_offset=, csr_index=, primitive="cylinder") and
+    Engine.dynamics_step(contact_cylinders=pool, contact_cylinder_lists=(csr_offset, csr_index)) (include/rmp2.h
+    rmp2_dynamics_step_contacts_cylinder_lists).  Axes are normalised and rows refused as cylinder_obstacles does it -- a robot with
+    more than MAX_OBSTACLE_CYLINDERS rows, non-finite values --, a pool beyond 1 << 22 records (RMP2_MAX_CYLINDER_POOL) as well."""
+    pools, offset = [], [0]
+    for r, rows in enumerate(scenes):
+        try:
+            pools.append(cylinder_obstacles(rows))
+        except ValueError as e:
+            raise ValueError(f"cylinder scene of robot {r}: {e}") from None
+        offset.append(offset[-1] + len(pools[-1]))
+    if offset[-1] > (1 << 22):
+        raise ValueError(f"{offset[-1]} cylinders in the pool, at most {1 << 22}")
+    pool = np.concatenate(pools).astype(np.float32) if pools else np.zeros((0, 8), np.float32)
+    return np.ascontiguousarray(pool.reshape(-1, 8)), np.asarray(offset, np.int32), np.arange(offset[-1], dtype=np.int32)
+
+
 # ---- convex-hull link geometry (simulation.py:462-484: PyBullet loads each .obj collision mesh as its convex hull) ------------
 
 MAX_HULL_VERTICES = 512   # include/rmp2.h RMP2_MAX_HULL_VERTICES

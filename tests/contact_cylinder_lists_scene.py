@@ -1,0 +1,120 @@
+"""List fleets of the per-robot cylinder lists (include/rmp2.h rmp2_dynamics_step_contacts_cylinder_lists), built from the catalogue
+and the slot catalogue of tests/contact_cylinders_scene.py, unchanged, and shared by tests/test_contact_cylinder_lists_host.py and
+tests/test_gpu_contact_cylinder_lists.py.
+
+A FAMILY is the groups of one robot that share every table but the cylinders -- spheres, planes, obstacle capsules, self pairs, link
+capsules, effort limits and joint limits.  Their cylinder tables are concatenated into one POOL, every robot lists its own group's
+records, ascending, and ONE call runs what took one call per group.  The fp64 reference of a robot under lists is
+contact_cylinders_reference.dynamics_step on cylinders[list_r]: for these lists that is the robot's group's own reference, with the
+pair indices mapped through the list (to_group_pairs / to_pool_pairs)."""
+import numpy as np
+
+import contact_cylinders_reference as YR
+import contact_cylinders_scene as YS
+
+TABLES = ("spheres", "planes", "capsules", "pairs", "caps")
+INVALID = 16          # include/rmp2.h RMP2_CONTACT_LIST_INVALID
+
+
+def _key(c):
+    lim = None if c["lim"] is None else np.asarray(c["lim"], np.float64).tobytes()
+    limits = None if c["limits"] is None else tuple(np.asarray(x, np.float64).tobytes() for x in c["limits"])
+    return (c["name"], c["drive"], lim, limits) + tuple(np.ascontiguousarray(c[k]).tobytes() for k in TABLES)
+
+
+def families(groups):
+    """[dict(name, groups, pool [Y, 8], start [per group])]: the groups that share every table but the cylinders, in catalogue order."""
+    out = {}
+    for c in groups:
+        out.setdefault(_key(c), []).append(c)
+    fams = []
+    for gs in out.values():
+        sizes = [len(c["cylinders"]) for c in gs]
+        fams.append(dict(name=gs[0]["name"], groups=gs, pool=np.ascontiguousarray(np.concatenate([c["cylinders"] for c in gs]), np.float32),
+                         start=np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(int)))
+    return fams
+
+
+def csr(lists):
+    """(cyl_offset int32 [R + 1], cyl_index int32) of per-robot index lists."""
+    off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32)
+    idx = np.concatenate([np.asarray(l, np.int32).reshape(-1) for l in lists]).astype(np.int32) if len(lists) else np.zeros(0, np.int32)
+    return off, idx
+
+
+def own_list(fam, g):
+    """The ascending list of group g's records in the family's pool."""
+    return np.arange(fam["start"][g], fam["start"][g] + len(fam["groups"][g]["cylinders"]), dtype=np.int32)
+
+
+def merged(fam):
+    """The family as ONE fleet: the first group's tables, cylinders = the pool, the groups' robots one after the other, every robot
+    listing its own group's records.  dict(c: the call's group-like dict, lists: per robot, rows: [(g, slice of the fleet)])."""
+    gs = fam["groups"]
+    c = dict(gs[0], cylinders=fam["pool"], q=np.concatenate([x["q"] for x in gs]), qd=np.concatenate([x["qd"] for x in gs]),
+             u=np.concatenate([x["u"] for x in gs]), label=f"{fam['name']}-pool-of-{len(gs)}")
+    lists, rows, at = [], [], 0
+    for g, x in enumerate(gs):
+        lists += [own_list(fam, g)] * len(x["q"])
+        rows.append((g, slice(at, at + len(x["q"]))))
+        at += len(x["q"])
+    return dict(c=c, lists=lists, rows=rows)
+
+
+def map_pairs(pair, c, Y_from, Y_to, record_map):
+    """The pair indices `pair` of a call with Y_from cylinders as those of a call with Y_to, cylinder records through record_map (an
+    int array [Y_from]); the other kinds and -1 unchanged."""
+    F, K, P, C, _ = YS.counts(c)
+    base = YR.cylinder_base(F, K, P, C)
+    pair = np.asarray(pair).astype(np.int64)
+    if not Y_from:
+        return pair.astype(np.int32)
+    cyl = pair >= base
+    f, y = (pair - base) // Y_from, np.where(cyl, (pair - base) % Y_from, 0)
+    return np.where(cyl, base + f * Y_to + np.asarray(record_map, np.int64)[y], pair).astype(np.int32)
+
+
+def to_group_pairs(pair, fam, g):
+    """Pool pair indices of robots that list group g's records -> the group's own pair indices."""
+    Y, Yg = len(fam["pool"]), len(fam["groups"][g]["cylinders"])
+    return map_pairs(pair, fam["groups"][g], Y, Yg, np.arange(Y) - fam["start"][g])
+
+
+def with_pairs(d, pair):
+    return dict(d, pair=pair)
+
+
+def rows(d, sel):
+    return {k: v[sel] for k, v in d.items()}
+
+
+def write_driver_input(path, c, substeps, dt, d_act, cyl_lists, lists=None, flag=1, **over):
+    """Input file of tests/contact_cylinder_lists_driver.cpp: contact_cylinders_reference.write_driver_input's followed by int32
+    cyl_offset [B + 1], int32 n_index, int32 cyl_index [n_index].  cyl_lists = (cyl_offset, cyl_index)."""
+    YR.write_driver_input(path, c, substeps, dt, d_act, lists=lists, flag=flag, **over)
+    off, idx = (np.ascontiguousarray(x, np.int32) for x in cyl_lists)
+    with open(path, "ab") as f:
+        off.tofile(f)
+        np.array([len(idx)], np.int32).tofile(f)
+        idx.tofile(f)
+
+
+def length_fleet(fam_groups, rng, lengths=(0, 1, 7, 32), Y=600):
+    """A pool of Y records and one robot per (group, length): the group's planted cylinder somewhere in a list of that length, the
+    rest of the list far records (configs.EXP06_CYLINDERS 50 m away, culled), all lists ascending.  The groups must share their
+    tables (a family) and have one cylinder each.  dict(pool, lists, lane_group, lane_length, planted: the pool index per group)."""
+    from riemannian_motion_policies_amd import configs as Cf
+    far = Cf.EXP06_CYLINDERS.copy()
+    far[:, 0] += 50.0
+    pool = np.ascontiguousarray(np.tile(far, (Y // len(far) + 1, 1))[:Y], np.float32)
+    planted = rng.choice(Y, len(fam_groups), replace=False)
+    for g, c in enumerate(fam_groups):
+        assert len(c["cylinders"]) == 1
+        pool[planted[g]] = c["cylinders"][0]
+    free = np.setdiff1d(np.arange(Y), planted)
+    lists, lane_group, lane_length = [], [], []
+    for g in range(len(fam_groups)):
+        for n in lengths:
+            l = np.sort(np.concatenate([[planted[g]], rng.choice(free, n - 1, replace=False)])) if n else np.zeros(0, int)
+            lists.append(l.astype(np.int32)), lane_group.append(g), lane_length.append(n)
+    return dict(pool=pool, lists=lists, lane_group=np.array(lane_group), lane_length=np.array(lane_length), planted=planted)

@@ -1,0 +1,433 @@
+"""Per-robot cylinder lists over a shared cylinder pool (include/rmp2.h rmp2_dynamics_step_contacts_cylinder_lists) on the host: the
+cylinder-list form of the device routine of rmp2_contacts.h run on the CPU through tests/contact_cylinder_lists_driver.cpp (also
+under the host sanitizers, as a stand-alone program, and built without the cull) on the list fleets of
+tests/contact_cylinder_lists_scene.py -- the catalogue and the slot catalogue of tests/contact_cylinders_scene.py with the cylinder
+tables of the groups that share every other table merged into one pool -- against the fp64 reference of
+tests/contact_cylinders_reference.py on cylinders[list_r], within K_CYLINDERS (tests/test_contact_cylinders_host.py, unchanged: the
+arithmetic of a pair is that call's) on the robots of DESIGN 4.12's kept rule; BIT FOR BIT against the table form, Y = 0, the
+per-group calls, a robot alone, the reversed fleet, a permuted pool and the build without the cull; unsorted and repeated lists; the
+five-kind tie; invalid lists beside valid neighbours; a NaN record; pair indices over a 600-record pool; the header, the bindings and
+urdf.cylinder_scenes.  No GPU."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import contact_cylinder_lists_scene as LS
+import contact_cylinders_reference as YR
+import contact_cylinders_scene as YS
+import contacts_reference as CR
+import test_contact_planes_host as PH
+import test_contacts_host as S
+from test_contact_cylinders_host import K_CYLINDERS, tie_case
+from test_contacts_host import D_ACT, DT, ROOT
+
+FLOATS = PH.FLOATS
+SAN = PH.SAN
+whole_lists, same, by = PH.whole_lists, PH.same, PH.by
+NONE_CYL = np.zeros((0, 8), np.float32)
+SOURCE = "contact_cylinder_lists_driver.cpp"
+
+
+@pytest.fixture(scope="module")
+def groups(golden_dir, tmp_path_factory):
+    return YS.catalogue(golden_dir, tmp_path_factory.mktemp("trees"))
+
+
+@pytest.fixture(scope="module")
+def slot_groups(tmp_path_factory):
+    return YS.slot_catalogue(tmp_path_factory.mktemp("trees"))
+
+
+@pytest.fixture(scope="module")
+def fams(groups, slot_groups):
+    return LS.families(groups + slot_groups)
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    return S._build(tmp_path_factory, SOURCE, "contact_cylinder_lists_driver")
+
+
+@pytest.fixture(scope="module")
+def driver_no_cull(tmp_path_factory):
+    return S._build(tmp_path_factory, SOURCE, "contact_cylinder_lists_driver_no_cull", ("-DRMP2_CYLINDER_NO_CULL",))
+
+
+@pytest.fixture(scope="module")
+def driver_san(tmp_path_factory):
+    return S._build(tmp_path_factory, SOURCE, "contact_cylinder_lists_driver_san", SAN)
+
+
+def run_lists(exe, tmp_path, c, cyl_lists, substeps=1, lists=None, flag=1, table=False, **over):
+    """The driver on a group-like dict (fields replaced by the keywords) with cyl_lists = per-robot index lists or a ready
+    (cyl_offset, cyl_index) pair; table=True: the pool as the shared table through the cylinder form (the lists are ignored).  A
+    sanitizer report fails it: exit status 0 and nothing on stderr."""
+    if isinstance(cyl_lists, list):
+        cyl_lists = LS.csr(cyl_lists)
+    LS.write_driver_input(str(tmp_path / "in.bin"), c, substeps, DT, D_ACT, cyl_lists, lists=lists, flag=flag, **over)
+    argv = [exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")] + (["table"] if table else [])
+    p = subprocess.run(argv, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
+    B = len(over["q"]) if over.get("q") is not None else len(c["q"])
+    return CR.read_driver_output(str(tmp_path / "out.bin"), B, c["t"].n_dof)
+
+
+def sphere_forms(c, B=None):
+    return (None, whole_lists(len(c["q"]) if B is None else B, len(c["spheres"])))
+
+
+# ---- 1: the merged-pool fleets against the reference ----------------------------------------------------------------------------
+
+def test_families_merge_the_catalogue(fams, groups, slot_groups):
+    assert sum(len(f["groups"]) for f in fams) == len(groups + slot_groups)
+    assert max(len(f["groups"]) for f in fams) >= 8 and max(len(f["pool"]) for f in fams) > 8          # (one call for many groups)
+    for f in fams:
+        for g, c in enumerate(f["groups"]):
+            assert np.array_equal(f["pool"][LS.own_list(f, g)], c["cylinders"])
+
+
+def test_device_routine_on_the_cpu_against_the_reference(driver, fams, groups, slot_groups, tmp_path):
+    every = groups + slot_groups
+    for name in YS.robots(every):          # the envelope alone keeps the share: the cap cannot hide a failure
+        gs = YS.for_robot(every, name)
+        keep = np.concatenate([YS.kept(c, K_CYLINDERS) for c in gs]), np.concatenate([YS.kept_step(c, K_CYLINDERS) for c in gs])
+        assert keep[0].mean() >= 0.9 and keep[1].mean() >= 0.9, (name, keep[0].mean(), keep[1].mean())
+    worst, kept, total = {}, {}, {}
+    for fam in fams:
+        m = LS.merged(fam)
+        for lists in sphere_forms(m["c"]):
+            d1 = run_lists(driver, tmp_path, m["c"], m["lists"], lists=lists)
+            d4 = run_lists(driver, tmp_path, m["c"], m["lists"], substeps=YS.STEP_SUBSTEPS, lists=lists)
+            for g, sel in m["rows"]:
+                c = fam["groups"][g]
+                what = c["label"] + "-pool" + ("-lists" if lists else "")
+                got = LS.rows(d1, sel)
+                got = dict(got, pair=LS.to_group_pairs(got["pair"], fam, g))
+                n = YS.check_group(c, got, K_CYLINDERS, what, worst)
+                YS.check_group_step(c, LS.rows(d4, sel), K_CYLINDERS, what, worst)
+                if lists is None:
+                    kept[c["name"]] = kept.get(c["name"], 0) + n
+                    total[c["name"]] = total.get(c["name"], 0) + len(c["q"])
+                if c["group"] in YS.PUSHED:
+                    assert YS.planted_active(c, got).all() and ((got["pair"] >= 0).sum(1) == 1).all(), what
+    print("CPU driver worst ratios", worst, "kept", kept, "of", total)
+    for name in total:
+        assert kept[name] >= 0.9 * total[name], (name, kept[name], total[name])
+    for k, K in K_CYLINDERS.items():
+        assert worst[k] <= K, (k, worst[k], K)
+
+
+# ---- 2: bit for bit -------------------------------------------------------------------------------------------------------------
+
+def test_ascending_lists_and_the_merged_pool_equal_the_table_form_per_group_bit_for_bit(driver, fams, tmp_path):
+    """Per group: the table form on the group's own table == the list form with that table as the pool and whole lists == the
+    group's robots in the merged-pool call, pairs mapped through the list.  Status words included."""
+    seen = 0
+    for fam in fams:
+        m = LS.merged(fam)
+        for substeps in (1, 3):
+            for si, lists in enumerate(sphere_forms(m["c"])):
+                dm = run_lists(driver, tmp_path, m["c"], m["lists"], substeps=substeps, lists=lists)
+                for g, sel in m["rows"]:
+                    c = fam["groups"][g]
+                    B, Y = len(c["q"]), len(c["cylinders"])
+                    gl = sphere_forms(c)[si]
+                    table = run_lists(driver, tmp_path, c, [np.zeros(0, np.int32)] * B, substeps=substeps, lists=gl, table=True)
+                    own = run_lists(driver, tmp_path, c, [np.arange(Y, dtype=np.int32)] * B, substeps=substeps, lists=gl)
+                    same(own, table, (c["label"], "whole lists", substeps, si))
+                    got = LS.rows(dm, sel)
+                    same(dict(got, pair=LS.to_group_pairs(got["pair"], fam, g)), table, (c["label"], "merged pool", substeps, si))
+                    seen += int((table["pair"] >= YR.cylinder_base(*YS.counts(c)[:4])).sum())
+    assert seen >= 400
+
+
+def test_a_compacted_sublist_equals_the_table_form_on_the_compacted_table(driver, groups, tmp_path):
+    """A strictly ascending list that is NOT everything: the table call on cylinders[list], pairs mapped through the list."""
+    for c in by(groups, "overflow") + by(groups, "graze"):
+        B, Y = len(c["q"]), len(c["cylinders"])
+        for keep in (np.arange(0, Y, 2), np.arange(1, Y), np.array([Y - 1])):
+            keep = keep.astype(np.int32)
+            d = run_lists(driver, tmp_path, c, [keep] * B)
+            t = run_lists(driver, tmp_path, c, [np.zeros(0, np.int32)] * B, table=True, cylinders=c["cylinders"][keep])
+            tc = dict(c, cylinders=c["cylinders"][keep])
+            same(dict(d, pair=LS.map_pairs(d["pair"], c, Y, len(keep), np.searchsorted(keep, np.arange(Y)))), t, (c["label"], keep.tolist()))
+            assert np.array_equal(LS.map_pairs(t["pair"], tc, len(keep), Y, keep), d["pair"]), c["label"]
+
+
+def test_an_empty_list_is_the_call_with_no_cylinders_bit_for_bit(driver, groups, slot_groups, tmp_path):
+    for c in by(groups + slot_groups, "side") + by(groups, "mixed") + by(groups, "far"):
+        B = len(c["q"])
+        none = [np.zeros(0, np.int32)] * B
+        for substeps in (1, 3):
+            for lists in sphere_forms(c):
+                want = run_lists(driver, tmp_path, c, none, substeps=substeps, lists=lists, cylinders=NONE_CYL)
+                same(run_lists(driver, tmp_path, c, none, substeps=substeps, lists=lists), want, (c["label"], "empty lists"))
+                same(run_lists(driver, tmp_path, c, none, substeps=substeps, lists=lists, cylinders=NONE_CYL, table=True), want,
+                     (c["label"], "the table form with Y = 0"))
+        # ... and one robot with an empty list beside robots with theirs
+        mixed_lists = [np.zeros(0, np.int32) if r == 1 else np.arange(len(c["cylinders"]), dtype=np.int32) for r in range(B)]
+        d, full = run_lists(driver, tmp_path, c, mixed_lists), run_lists(driver, tmp_path, c, [mixed_lists[0]] * B)
+        want = run_lists(driver, tmp_path, c, none, cylinders=NONE_CYL)
+        same(LS.rows(d, slice(1, 2)), LS.rows(want, slice(1, 2)), c["label"])
+        others = np.arange(B) != 1
+        same(LS.rows(d, others), LS.rows(full, others), c["label"])
+
+
+def test_alone_reversed_and_in_a_permuted_pool_a_robot_keeps_its_bits(driver, fams, tmp_path):
+    rng = np.random.default_rng(5)
+    for fam in fams:
+        m = LS.merged(fam)
+        c, lists_ = m["c"], m["lists"]
+        B, Y = len(c["q"]), len(c["cylinders"])
+        for si, lists in enumerate(sphere_forms(c)):
+            d = run_lists(driver, tmp_path, c, lists_, substeps=2, lists=lists)
+            rev = run_lists(driver, tmp_path, c, lists_[::-1], substeps=2, lists=lists, q=c["q"][::-1], qd=c["qd"][::-1], u=c["u"][::-1])
+            same(LS.rows(rev, slice(None, None, -1)), d, (c["label"], "reversed"))
+            for r in sorted({0, B // 2, B - 1}):
+                one = run_lists(driver, tmp_path, c, lists_[r:r + 1], substeps=2, lists=sphere_forms(c, 1)[si], q=c["q"][r:r + 1],
+                                qd=c["qd"][r:r + 1], u=c["u"][r:r + 1])
+                same(one, LS.rows(d, slice(r, r + 1)), (c["label"], "alone", r))
+            perm = rng.permutation(Y)          # record y of the pool moves to perm[y]
+            pool = np.empty_like(c["cylinders"])
+            pool[perm] = c["cylinders"]
+            p = run_lists(driver, tmp_path, c, [perm[l].astype(np.int32) for l in lists_], substeps=2, lists=lists, cylinders=pool)
+            same(dict(p, pair=LS.map_pairs(p["pair"], c, Y, Y, np.argsort(perm))), d, (c["label"], "permuted pool"))
+
+
+def test_cull_on_equals_cull_off_bit_for_bit(driver, driver_no_cull, fams, tmp_path):
+    for fam in fams:
+        m = LS.merged(fam)
+        for substeps in (1, YS.STEP_SUBSTEPS):
+            for lists in sphere_forms(m["c"]):
+                same(run_lists(driver, tmp_path, m["c"], m["lists"], substeps=substeps, lists=lists),
+                     run_lists(driver_no_cull, tmp_path, m["c"], m["lists"], substeps=substeps, lists=lists), (m["c"]["label"], substeps))
+
+
+# ---- 3: unsorted and repeated lists, the tie ------------------------------------------------------------------------------------
+
+def test_unsorted_lists_give_the_same_candidates_and_a_repeat_two_identical_rows(driver, groups, tmp_path):
+    rng = np.random.default_rng(9)
+    for c in by(groups, "overflow") + by(groups, "graze") + by(groups, "mixed"):
+        B, Y = len(c["q"]), len(c["cylinders"])
+        want = run_lists(driver, tmp_path, c, [np.arange(Y, dtype=np.int32)] * B)
+        for order in (np.arange(Y)[::-1], rng.permutation(Y)):
+            d = run_lists(driver, tmp_path, c, [order.astype(np.int32)] * B)
+            assert np.array_equal(np.sort(d["pair"], 1), np.sort(want["pair"], 1)), (c["label"], order)
+            assert np.array_equal(d["status"] & 0xff, want["status"] & 0xff), c["label"]
+            YS.hard_invariants(c, d, K_CYLINDERS, c["label"])
+    for c in by(groups, "side") + by(groups, "rim"):
+        B = len(c["q"])
+        F, K, P, C, Y = YS.counts(c)
+        once = run_lists(driver, tmp_path, c, [np.array([0], np.int32)] * B)
+        d = run_lists(driver, tmp_path, c, [np.array([0, 0], np.int32)] * B)
+        w = YS.planted_pair(c)
+        assert ((once["pair"] == w).sum(1) == 1).all() and ((d["pair"] == w).sum(1) == 2).all(), (c["label"], d["pair"])
+        assert ((d["pair"] >= 0).sum(1) == 2).all()
+        # identical rows: the two slots' forces add up to the single pair's, and the motion is the single pair's, to the K's
+        ratio = YS.per_robot_ratios(c, d)
+        keep = YS.kept(c, K_CYLINDERS)
+        for k in ("res", "vel", "force"):
+            assert (ratio[k][keep] <= K_CYLINDERS[k]).all(), (c["label"], k, ratio[k])
+
+
+def test_the_five_kinds_tie_in_index_order_with_the_cylinder_through_a_list(driver, golden_dir, tmp_path_factory, tmp_path):
+    self_groups = YS.SS.catalogue(golden_dir, tmp_path_factory.mktemp("self_trees"))
+    SR = YR.SR
+    for n_small, kept_kinds in ((3, [0, 1, 2, 3, 4]), (4, [0, 1, 2, 3]), (5, [0, 1, 2])):
+        c = tie_case(self_groups, n_small)
+        far = np.tile(np.array([[50.0, 0, 0, 0.05, 0, 0, 1, 0.1]], np.float32), (5, 1))
+        pool = np.concatenate([far[:3], c["cylinders"], far[3:]])          # the tied cylinder is record 3 of 6
+        c = dict(c, cylinders=pool)
+        F, K, P, C, Y = YS.counts(c)
+        tied = [2 * K + 0, SR.QR.PR.pair_index(F, K, P, 2, n_small, 0), SR.QR.pair_index(F, K, P, C, 2, 0), SR.pair_index(F, K, P, C, 2, 0),
+                YR.pair_index(F, K, P, C, Y, 2, 3)]
+        small = [SR.QR.PR.pair_index(F, K, P, 2, k, 0) for k in range(n_small)]
+        assert tied == sorted(tied) and [YR.split_pair(p, F, K, P, C, Y)[0] for p in tied[:8 - n_small]] == kept_kinds
+        for lists in (None, whole_lists(1, K)):
+            for cl in ([3], [5, 3, 0]):
+                d = run_lists(driver, tmp_path, c, [np.array(cl, np.int32)], lists=lists)
+                assert bool(d["status"][0] & CR.OVERFLOW) == (n_small > 3)
+                assert sorted(d["pair"][0]) == sorted(small + tied[:8 - n_small]), (d["pair"][0], cl)
+
+
+# ---- 4: invalid lists, poisoning, the sanitizers -----------------------------------------------------------------------------------
+
+def invalid_fleet(c, Y=8):
+    """Ten robots of the group c (one cylinder) over a pool of Y records, record 2 the group's cylinder, the rest far away: the even
+    ones with an invalid list each -- a negative start, a negative length, 33 entries, an entry -1, an entry Y --, the odd ones
+    listing [2].  (pool, (cyl_offset, cyl_index), q, qd, u, the invalid robots)."""
+    pool = np.tile(np.array([[50.0, 0, 0, 0.05, 0, 0, 1, 0.1]], np.float32), (Y, 1))
+    pool[2] = c["cylinders"][0]
+    index = np.full(42, 2, np.int32)
+    offset = np.array([-1, 1, 2, 1, 2, 35, 36, 38, 39, 41, 42], np.int32)
+    index[2:35] = np.arange(33) % Y          # (33 entries, each in range)
+    index[36:38] = (2, -1)
+    index[39:41] = (Y, 2)
+    pick = np.arange(10) % len(c["q"])
+    return pool, (offset, index), c["q"][pick], c["qd"][pick], c["u"][pick], np.arange(0, 10, 2)
+
+
+def check_invalid(d, good, bad, contacts=True):
+    others = np.setdiff1d(np.arange(len(d["status"])), bad)
+    for k in FLOATS:
+        assert np.isnan(d[k][bad]).all(), k
+    assert (d["pair"][bad] == -1).all() and (d["status"][bad] == LS.INVALID).all(), d["status"]
+    same(LS.rows(d, others), LS.rows(good, others), "the valid neighbours")
+    assert (good["pair"][others] >= 0).any() == contacts and np.isfinite(good["q"]).all()
+
+
+def test_invalid_lists_are_refused_per_robot_and_nothing_is_read_through_them(driver, driver_san, groups, tmp_path):
+    for c in by(YS.for_robot(groups, "panda"), "side") + by(YS.for_robot(groups, "two_joint"), "side"):
+        pool, cl, q, qd, u, bad = invalid_fleet(c)
+        for lists in sphere_forms(c, 10):
+            good = run_lists(driver, tmp_path, c, [np.array([2], np.int32)] * 10, substeps=2, lists=lists, cylinders=pool, q=q, qd=qd, u=u)
+            for exe in (driver, driver_san):          # (the pool and cyl_index are allocated at exactly their sizes)
+                check_invalid(run_lists(exe, tmp_path, c, cl, substeps=2, lists=lists, cylinders=pool, q=q, qd=qd, u=u), good, bad)
+        # Y == 0 is accepted; every list must then be empty
+        none = run_lists(driver, tmp_path, c, [np.zeros(0, np.int32)] * 10, cylinders=NONE_CYL, q=q, qd=qd, u=u)
+        some = [np.zeros(0, np.int32) if r % 2 else np.array([0], np.int32) for r in range(10)]
+        for exe in (driver, driver_san):
+            check_invalid(run_lists(exe, tmp_path, c, some, cylinders=NONE_CYL, q=q, qd=qd, u=u), none, bad, contacts=False)
+        # an invalid sphere list and an invalid cylinder list give the same word
+        K = len(c["spheres"])
+        off, idx = whole_lists(10, K)
+        sph = ((off + np.arange(11) // 10).astype(np.int32), np.concatenate([idx, [K]]).astype(np.int32))          # robot 9: and the entry K
+        d = run_lists(driver_san, tmp_path, c, cl, lists=sph, cylinders=pool, q=q, qd=qd, u=u)
+        assert (d["status"][np.concatenate([bad, [9]])] == LS.INVALID).all() and np.isnan(d["q"][9]).all()
+
+
+def test_a_nan_word_in_a_pool_record_poisons_exactly_the_robots_that_list_it(driver, fams, tmp_path):
+    seen = 0
+    for fam in fams:
+        if len(fam["groups"]) < 2:
+            continue
+        m = LS.merged(fam)
+        c = m["c"]
+        good = run_lists(driver, tmp_path, c, m["lists"])
+        for g in (0, len(fam["groups"]) - 1):
+            y = int(LS.own_list(fam, g)[-1])
+            for word, bad in ((0, np.nan), (3, np.inf), (5, np.nan), (7, -np.inf)):
+                pool = c["cylinders"].copy()
+                pool[y, word] = bad
+                d = run_lists(driver, tmp_path, c, m["lists"], cylinders=pool)
+                hit = np.array([y in l for l in m["lists"]])
+                assert hit.any() and not hit.all()
+                for k in FLOATS:
+                    assert np.isnan(d[k][hit]).all(), (c["label"], word, k)
+                assert (d["pair"][hit] == -1).all()
+                same(LS.rows(d, ~hit), LS.rows(good, ~hit), (c["label"], "not listed"))
+                seen += 1
+    assert seen >= 8
+
+
+def test_driver_under_the_host_sanitizers_equals_the_plain_build(driver, driver_san, fams, tmp_path):
+    for fam in fams:
+        if fam["name"] not in ("two_joint", "panda"):
+            continue
+        m = LS.merged(fam)
+        for lists in sphere_forms(m["c"]):
+            same(run_lists(driver_san, tmp_path, m["c"], m["lists"], substeps=2, lists=lists),
+                 run_lists(driver, tmp_path, m["c"], m["lists"], substeps=2, lists=lists), m["c"]["label"])
+
+
+# ---- 5: pair indices ---------------------------------------------------------------------------------------------------------------
+
+def test_pair_indices_decode_to_the_planted_frame_and_the_pool_index(driver, fams, tmp_path):
+    from riemannian_motion_policies_amd import engine as E
+    rng = np.random.default_rng(11)
+    seen = 0
+    for fam in fams:
+        gs = [c for c in fam["groups"] if c["group"] in YS.PUSHED + ("tip", "base", "disc", "buried")]
+        if fam["name"] not in ("two_joint", "panda") or len(gs) < 4:
+            continue
+        fl = LS.length_fleet(gs, rng)
+        c0 = gs[0]
+        pick = lambda k: np.concatenate([gs[g][k][:1] for g in fl["lane_group"]])
+        c = dict(c0, cylinders=fl["pool"])
+        d = run_lists(driver, tmp_path, c, fl["lists"], q=pick("q"), qd=pick("qd"), u=pick("u"))
+        F, K, P, C, Y = YS.counts(c)
+        assert Y == 600
+        for lane, (g, n) in enumerate(zip(fl["lane_group"], fl["lane_length"])):
+            got = {E.contact_pair_split(p, F, K, P, C, self_pairs=True, cylinders=Y) for p in d["pair"][lane] if p >= 0}
+            want = (E.CONTACT_KIND_CYLINDER, gs[g]["planted"][0], int(fl["planted"][g]), 0)
+            assert (want in got) == (n > 0), (gs[g]["label"], n, got, want)
+            assert all(k[0] != E.CONTACT_KIND_CYLINDER or k[2] == want[2] for k in got), (gs[g]["label"], got)          # (the far records: none)
+            if n and gs[g]["group"] in YS.PUSHED:          # the planted pair is the one active pair
+                assert got == {want} and (d["lam"][lane][d["pair"][lane] >= 0] > 0).all(), (gs[g]["label"], n)
+            seen += n > 0
+    assert seen >= 24
+
+
+def test_pair_split_macros_of_the_header_over_a_pool_and_the_int32_bound(tmp_path):
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang") or "/opt/rocm/lib/llvm/bin/clang"
+    src = tmp_path / "split.c"
+    src.write_text('#include <stdio.h>\n#include "rmp2.h"\nint main(void) {\n  const int F = 5, K = 3, P = 2, C = 4, Y = 600;\n'
+                   '  const int64_t top = RMP2_CONTACT_PAIR_CYLINDER_BASE(RMP2_MAX_FRAMES, RMP2_MAX_CONTACT_POOL, RMP2_MAX_CONTACT_PLANES, RMP2_MAX_OBSTACLE_CAPSULES)\n'
+                   '                      + (int64_t)RMP2_MAX_FRAMES * RMP2_MAX_CYLINDER_POOL;\n'
+                   '  if (top != 32ll * (1 << 24) + 512 + 1024 + 1024 + 32ll * (1 << 22) || top - 1 > INT32_MAX) return 1;\n'
+                   '  if (RMP2_MAX_CYLINDER_LIST != RMP2_MAX_OBSTACLE_CYLINDERS || RMP2_ABI_VERSION != 5) return 2;\n'
+                   '  const int32_t base = (int32_t)RMP2_CONTACT_PAIR_CYLINDER_BASE(F, K, P, C);\n'
+                   '  for (int32_t p = base; p < base + F * Y; ++p)\n'
+                   '    printf("%d %d %d %d\\n", p, RMP2_CONTACT_PAIR_KIND5(p, F, K, P, C), RMP2_CONTACT_PAIR_CYLINDER_FRAME(p, F, K, P, C, Y),\n'
+                   '           RMP2_CONTACT_PAIR_CYLINDER_RECORD(p, F, K, P, C, Y));\n  return 0;\n}\n')
+    exe = tmp_path / "split"
+    subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    lines = [list(map(int, l.split())) for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()]
+    assert len(lines) == 5 * 600
+    for p, k, f, y in lines:
+        assert (k, f, y, 0) == YR.split_pair(p, 5, 3, 2, 4, 600), (p, k, f, y)
+    assert lines[0][1:] == [4, 0, 0] and lines[-1][1:] == [4, 4, 599]
+
+
+# ---- 6: the interface --------------------------------------------------------------------------------------------------------------
+
+def test_urdf_cylinder_scenes_round_trip_and_refusals():
+    from riemannian_motion_policies_amd import configs as Cf, urdf as U
+    rng = np.random.default_rng(2)
+    scenes = [Cf.sample_cylinders(rng, n) if n else np.zeros((0, 8)) for n in (7, 0, 1, 7, 3, 32)]
+    scenes[2] = scenes[2] * np.array([1, 1, 1, 1, 3, 3, 3, 1.0])          # (an axis that is not a unit vector)
+    pool, off, idx = U.cylinder_scenes(scenes)
+    assert pool.dtype == np.float32 and pool.shape == (50, 8) and pool.flags["C_CONTIGUOUS"]
+    assert off.dtype == np.int32 == idx.dtype and off.tolist() == [0, 7, 7, 8, 15, 18, 50] and idx.tolist() == list(range(50))
+    for r, rows in enumerate(scenes):
+        assert np.array_equal(pool[idx[off[r]:off[r + 1]]], U.cylinder_obstacles(rows)), r
+    assert np.abs(np.linalg.norm(pool[:, 4:7].astype(np.float64), axis=1) - 1).max() < 1e-7
+    pool, off, idx = U.cylinder_scenes([])
+    assert pool.shape == (0, 8) and off.tolist() == [0] and idx.shape == (0,)
+    pool, off, idx = U.cylinder_scenes([[], []])
+    assert pool.shape == (0, 8) and off.tolist() == [0, 0, 0]
+    bad = scenes[0].copy()
+    bad[3, 1] = np.nan
+    for rows, msg in ((np.tile(scenes[0][:1], (33, 1)), "robot 1: 33 cylinder obstacles, at most 32"), (bad, "robot 1: .*not finite"),
+                      (scenes[0][:, :7], "robot 1: .*shape")):
+        with pytest.raises(ValueError, match=msg):
+            U.cylinder_scenes([scenes[0], rows])
+
+
+def test_symbol_declared_and_bound_with_its_constants(hip_lib):
+    import ctypes as C
+    import inspect
+    lib = C.CDLL(hip_lib)
+    hdr = open(os.path.join(ROOT, "include", "rmp2.h")).read()
+    assert re.search(r"\bint rmp2_dynamics_step_contacts_cylinder_lists\(", hdr) and hasattr(lib, "rmp2_dynamics_step_contacts_cylinder_lists")
+    assert re.search(r"#define RMP2_MAX_CYLINDER_LIST 32\b", hdr) and re.search(r"#define RMP2_MAX_CYLINDER_POOL \(1 << 22\)", hdr)
+    assert re.search(r"#define RMP2_ABI_VERSION (\d+)", hdr).group(1) == "5" and lib.rmp2_abi_version() == 5
+    from riemannian_motion_policies_amd import _native, engine as E
+    assert E.MAX_CYLINDER_LIST == 32 == E.MAX_OBSTACLE_CYLINDERS and E.MAX_CYLINDER_POOL == 1 << 22 and E.CONTACT_LIST_INVALID == LS.INVALID
+    assert "contact_cylinder_lists" in inspect.signature(E.Engine.dynamics_step).parameters
+    n = _native.lib()
+    assert len(n.rmp2_dynamics_step_contacts_cylinder_lists.argtypes) == 33 and len(n.rmp2_dynamics_step_contacts_cylinders.argtypes) == 31
+    args = [None] * 33
+    for k, v in ((4, 0), (9, 0), (13, 0), (15, 0), (17, 0), (20, 1), (21, 0.0), (22, 0.0), (23, 0), (31, 0)):
+        args[k] = v
+    assert n.rmp2_dynamics_step_contacts_cylinder_lists(*args) == -1          # (no handle: RMP2_ERR_INVALID_ARGUMENT)
+    import __graft_entry__ as g
+    names = [u[0] for u in g.HIP_UNITS]
+    assert "rmp2_contacts_l0_cylinder_lists" in names and "rmp2_contacts_l1_cylinder_lists" in names and len(names) == len(set(names))
+    for name, _, defs, _ in g.HIP_UNITS:
+        if name.endswith("_cylinder_lists"):
+            assert "-DRMP2_TU_CYLINDER_LISTS=1" in defs and "-DRMP2_TU_CYLINDERS=1" in defs

@@ -1,0 +1,193 @@
+"""Time the plant's step with per-robot cylinder lists over a shared cylinder pool (include/rmp2.h
+rmp2_dynamics_step_contacts_cylinder_lists) against the cylinders call, on the workload and by the method of
+tools/contact_timing_common.py (the fleet, the timing loop, one process per measurement) and with the scene of
+tools/contact_cylinders_timing.py's leg (c).  Prints ONE JSON line (profiles/contact_cylinder_lists_timing.json).  Per fleet size:
+  (a) `cyl_us`: the existing rmp2_dynamics_step_contacts_cylinders, the seven configs.EXP06_CYLINDERS in place, the workload's
+      touching start states, self pairs on.  With --parent-lib this leg alternates between the parent's library and this build
+      (`cyl_us_parent`, `cyl_us_this`, `cyl_us_ok`; `cyl_bits_as_parent`): the code objects are the parent's.
+  (b) `whole_us`: the new call, every robot listing 0 .. 6 of that table.  `same_results`: the final state and status have (a)'s
+      bits; `same_flags`: the status flags (status & 0xff) are (a)'s -- what is promised against the table form's kernels.
+  (c) `own_us`: the new call, every robot its own 7-record slice of an R x 7 pool of copies.  `own_same_results`: (b)'s bits, asserted
+      (bits are promised among the new kernels).
+  (d) `scenes_us`: the workload itself, configs.sample_cylinders(rng, 7) per state through urdf.cylinder_scenes (4 096 scenes, tiled
+      with the states to the fleet size); `contact_fraction`; `cull_survivors`: the share of the (frame, cylinder) trips of the 4 096
+      start states that the cull lets through, counted on the CPU in fp32.
+  (e) `uneven_us`: list lengths drawn from {0, 1, 7, 32} inside every wave (a pool of 4 096 x 32 records) and sphere lists of
+      lengths drawn from {0, 8, 32} beside them: lanes of one wave stand in different kinds of trip at the same trip count.
+`b_over_a`, `c_over_b`, `d_over_a`, `e_over_d`: the ratios of the medians.
+usage: python tools/contact_cylinder_lists_timing.py [--parent-lib PATH] [--rounds N] [steps] [reps]"""
+import json
+import sys
+
+import contact_timing_common as T
+
+FAR_FLOOR = [[0.0, 0.0, 1.0, -50.0]]
+SCENES = T.STATES
+
+
+def far_capsules():
+    import numpy as np
+    return np.array([[50.0 + j, 3.0, 1.0, 0.05 + 0.01 * j, 50.0 + j, 3.0, 1.5, 0.0] for j in range(7)], np.float32)
+
+
+def table7():
+    from riemannian_motion_policies_amd import configs, urdf as U
+    return U.cylinder_obstacles(configs.EXP06_CYLINDERS)
+
+
+def setup(c):
+    import torch
+    from riemannian_motion_policies_amd import urdf as U
+    c.eng.set_contact_self_pairs(U.contact_self_pairs(c.table))
+    c.oc = torch.from_numpy(far_capsules()).to(c.dev)
+    c.floor = torch.tensor(FAR_FLOOR, device=c.dev)
+
+
+def call(c, cyl, lists=None, sphere_lists=None):
+    more = {} if lists is None else {"contact_cylinder_lists": lists}
+    if sphere_lists is not None:
+        more["contact_lists"] = sphere_lists
+    c.eng.dynamics_step(c.qs, c.qds, c.u, T.DT, stop_out=c.stop, status_out=c.status, contacts=c.spheres, d_act=T.D_ACT,
+                        contact_planes=c.floor, contact_obstacle_capsules=c.oc, contact_self=True, contact_cylinders=cyl, **more, **c.step)
+
+
+def ints(c, x):
+    import numpy as np
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x, np.int32)).to(c.dev)
+
+
+def after(c, key):
+    import hashlib
+    import torch
+    st = c.status.cpu().numpy()
+    c.row["contact_fraction_" + key] = round(float((st & 4 != 0).mean()), 4)
+    c.row["overflow_fraction_" + key] = round(float((st & 8 != 0).mean()), 4)
+    c.row["invalid_" + key] = int((st == 16).sum())
+    c.row["flags_" + key] = hashlib.sha256((st & 0xff).tobytes()).hexdigest()[:16]
+    c.row["finite_" + key] = bool(torch.isfinite(c.qs).all())
+
+
+def leg_table(c):
+    import torch
+    setup(c)
+    cyl = torch.from_numpy(table7()).to(c.dev)
+    c.time("cyl_us", lambda: call(c, cyl))
+    c.final("cyl_bits", lambda: call(c, cyl))
+    after(c, "cyl")
+
+
+def leg_whole(c):
+    import numpy as np
+    import torch
+    setup(c)
+    cyl = torch.from_numpy(table7()).to(c.dev)
+    lists = ints(c, 7 * np.arange(c.R + 1)), ints(c, np.tile(np.arange(7), c.R))
+    c.time("whole_us", lambda: call(c, cyl, lists))
+    c.final("whole_bits", lambda: call(c, cyl, lists))
+    after(c, "whole")
+
+
+def leg_own(c):
+    import numpy as np
+    import torch
+    setup(c)
+    cyl = torch.from_numpy(np.tile(table7(), (c.R, 1))).to(c.dev)
+    lists = ints(c, 7 * np.arange(c.R + 1)), ints(c, np.arange(7 * c.R))
+    c.time("own_us", lambda: call(c, cyl, lists))
+    c.final("own_bits", lambda: call(c, cyl, lists))
+    after(c, "own")
+    c.row["pool_mib_own"] = round(cyl.numel() * 4 / 2 ** 20, 2)
+
+
+def scenes(n):
+    """(pool [SCENES x n, 8], the scenes [SCENES, n, 8]): configs.sample_cylinders(rng, n) per start state."""
+    import numpy as np
+    from riemannian_motion_policies_amd import configs, urdf as U
+    rng = np.random.default_rng(1806)
+    pool, off, idx = U.cylinder_scenes([configs.sample_cylinders(rng, n) for _ in range(SCENES)])
+    assert np.array_equal(off, n * np.arange(SCENES + 1)) and np.array_equal(idx, np.arange(n * SCENES))
+    return pool, pool.reshape(SCENES, n, 8)
+
+
+def cull_survivors(c, per_scene):
+    """The share of (frame, cylinder) trips at the 4 096 start states that pass the cull of rmp2_contacts.h, in fp32."""
+    import numpy as np
+    import contacts_reference as CR
+    f32 = np.float32
+    q = c.q0.astype(f32)
+    R_, p, _ = CR.poses(c.table, q, f32)
+    caps = np.asarray(c.caps, f32)
+    cy = per_scene.astype(f32)
+    passed = total = 0
+    for f in CR.capsule_frames(caps):
+        A = (np.einsum("bij,j->bi", R_[f], caps[f, 0:3]) + p[f]).astype(f32)
+        D = np.einsum("bij,j->bi", R_[f], caps[f, 4:7] - caps[f, 0:3]).astype(f32)
+        dd = (D * D).sum(-1)
+        inv = np.where(dd > 0, 1 / np.where(dd > 0, dd, 1), 0).astype(f32)
+        t = np.clip(((cy[:, :, 0:3] - A[:, None]) * D[:, None]).sum(-1) * inv[:, None], 0, 1).astype(f32)
+        dv = A[:, None] + t[..., None] * D[:, None] - cy[:, :, 0:3]
+        dist = np.sqrt((dv * dv).sum(-1)).astype(f32)
+        rho = np.sqrt(cy[:, :, 3] ** 2 + cy[:, :, 7] ** 2).astype(f32)
+        L = dist - rho - caps[f, 3]
+        passed += int((~(L > f32(T.D_ACT) + f32(1e-4) * (1 + dist + rho))).sum())
+        total += L.size
+    return round(passed / total, 4)
+
+
+def leg_scenes(c):
+    import numpy as np
+    import torch
+    setup(c)
+    pool, per_scene = scenes(7)
+    who = np.arange(c.R) % SCENES
+    lists = ints(c, 7 * np.arange(c.R + 1)), ints(c, (7 * who[:, None] + np.arange(7)).reshape(-1))
+    cyl = torch.from_numpy(pool).to(c.dev)
+    c.time("scenes_us", lambda: call(c, cyl, lists))
+    c.final("scenes_bits", lambda: call(c, cyl, lists))
+    after(c, "scenes")
+    c.row["cull_survivors"] = cull_survivors(c, per_scene)
+
+
+def leg_uneven(c):
+    import numpy as np
+    import torch
+    setup(c)
+    pool, _ = scenes(32)
+    rng = np.random.default_rng(1807)
+    who = np.arange(c.R) % SCENES
+    n = rng.choice([0, 1, 7, 32], c.R)
+    off = np.concatenate([[0], np.cumsum(n)])
+    idx = np.concatenate([32 * who[r] + np.arange(n[r]) for r in range(c.R)])
+    ns = rng.choice([0, 8, 32], c.R)
+    soff = np.concatenate([[0], np.cumsum(ns)])
+    sidx = np.concatenate([np.arange(ns[r]) for r in range(c.R)])
+    lists, sphere_lists = (ints(c, off), ints(c, idx)), (ints(c, soff), ints(c, sidx))
+    cyl = torch.from_numpy(pool).to(c.dev)
+    c.time("uneven_us", lambda: call(c, cyl, lists, sphere_lists))
+    after(c, "uneven")
+    c.row["mean_list_uneven"] = round(float(n.mean()), 2)
+
+
+LEGS = {"table": leg_table, "whole": leg_whole, "own": leg_own, "scenes": leg_scenes, "uneven": leg_uneven}
+parent_lib, rounds, child, steps, reps = T.parse(__doc__)
+if child is not None:
+    T.main(__file__, "contact_cylinder_lists_timing", LEGS, __doc__)          # (measures the leg, prints its rows and exits)
+result = T.main(__file__, "contact_cylinder_lists_timing", {"table": leg_table}, __doc__)          # (a): alternating with the parent's library
+for name in ("whole", "own", "scenes", "uneven"):          # (b) .. (e): this build only
+    for row, got in zip(result["sizes"], T.run_child(__file__, name, steps, reps)):
+        row.update({k: v for k, v in got.items() if k != "robots"})
+result["cylinders"] = 7
+for row in result["sizes"]:
+    row["same_results"] = row["cyl_bits"] == row["whole_bits"]
+    row["same_flags"] = row["flags_cyl"] == row["flags_whole"]
+    row["own_same_results"] = row["whole_bits"] == row["own_bits"]
+    row["b_over_a"] = round(row["whole_us"] / row["cyl_us"], 3)
+    row["c_over_b"] = round(row["own_us"] / row["whole_us"], 3)
+    row["d_over_a"] = round(row["scenes_us"] / row["cyl_us"], 3)
+    row["e_over_d"] = round(row["uneven_us"] / row["scenes_us"], 3)
+print(json.dumps(result))
+bad = [r["robots"] for r in result["sizes"] if not (r["own_same_results"] and r["same_flags"]) or r["invalid_whole"] or r["invalid_own"]
+       or r["invalid_scenes"] or r["invalid_uneven"]]
+if bad:
+    sys.exit(f"results differ where they are promised equal, or a list was refused, at {bad} robots")
