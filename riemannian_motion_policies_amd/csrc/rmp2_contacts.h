@@ -31,20 +31,20 @@
 // These are indexed at run time (LDS addresses are per lane); every index into a REGISTER array is a compile-time constant
 // after unrolling -- dynamic picks are unrolled compares.  Host-compilable (tests/contacts_driver.cpp).
 //
-// Forms.  The step has two orthogonal switches: LIST -- the robot's spheres are the fleet's shared table or its own list over a
-// shared pool (rmp2_dynamics_step_contacts_lists; SphereTable / SphereList below) -- and planes -- half-spaces beside the spheres
-// or none (rmp2_dynamics_step_contacts_planes; NoPlanes / PlaneTable).  All four are dynamics_step_contacts_robot<N, SLOTS, LIST,
-// Pl>, one body with the differences under `if constexpr`, behind ONE kernel, rmp2_dynamics_step_contacts_kernel<N, SLOTS, LIST,
-// PLANES> at the end of this file, which rmp2_contacts_tu.hip instantiates once per form (a code object each).
-// A third switch, capsule obstacles beside both (rmp2_dynamics_step_contacts_capsules; NoCapsules / CapsuleTable), is the same
-// body again with planes and capsules on, behind a kernel of its own (rmp2_dynamics_step_contacts_capsules_kernel<N, SLOTS, LIST>).
-// A fourth, self contacts between the robot's own link capsules (rmp2_dynamics_step_contacts_self; NoSelfPairs / SelfPairs), is the
-// body with planes, capsules and self pairs on, behind rmp2_dynamics_step_contacts_self_kernel<N, SLOTS, LIST>.
-// A fifth, exact flat-capped cylinder obstacles (rmp2_dynamics_step_contacts_cylinders; NoCylinders / CylinderTable), is the body
-// with all of those on and the cylinder trips after the self trips, behind rmp2_dynamics_step_contacts_cylinders_kernel<N, SLOTS, LIST>.
-// A sixth, every robot's own cylinder list over a shared pool (rmp2_dynamics_step_contacts_cylinder_lists; CylinderList in
-// CylinderTable's place), is that body with the cylinder fetch a gather, behind rmp2_dynamics_step_contacts_cylinder_lists_kernel<N,
-// SLOTS, LIST> -- LIST is still the SPHERES' form, the two are independent.
+// Forms.  All are dynamics_step_contacts_robot<N, SLOTS, LIST, Pl, Cp, Sp, Cy>, one body with the differences under `if constexpr`:
+// LIST says where the robot's SPHERES come from (SphereTable, the fleet's shared table, or SphereList, its own list over a shared
+// pool) and is independent of everything else; Pl / Cp / Sp / Cy are a form object below or its empty No... twin.  The kernels at
+// the end of this file (one per row of the table; rmp2_contacts_tu.hip instantiates each once per LIST, a code object each) build
+// the form objects from their parameters and run dynamics_step_contacts_robot on the lane's robot (why each spells that out: the comment above the
+// kernels).  A form's rows are numbered from its pair-index base (F frames, K / P / C / Y the pool or table sizes); the LDS words are per lane.
+//
+//   entry point rmp2_dynamics_step_  kernel rmp2_dynamics_step_              on                                  LDS words              pair-index base
+//   contacts, contacts_lists         contacts_kernel<.., PLANES = false>     spheres                             contact_words(N)       0
+//   contacts_planes                  contacts_kernel<.., PLANES = true>      + PlaneTable                        contact_words(N)       F K
+//   contacts_capsules                contacts_capsules_kernel                + CapsuleTable                      contact_words(N)       F (K + 2 P)
+//   contacts_self                    contacts_self_kernel                    + SelfPairs (the handle's)          contact_self_words(N)  F (K + 2 P + C)
+//   contacts_cylinders               contacts_cylinders_kernel               + CylinderTable (SelfPairs by flag) contact_self_words(N)  F (K + 2 P + C) + F F
+//   contacts_cylinder_lists          contacts_cylinder_lists_kernel          CylinderList in its place           contact_self_words(N)  F (K + 2 P + C) + F F
 #pragma once
 #include <type_traits>
 
@@ -249,7 +249,7 @@ constexpr int contact_self_words(int n) {
 // The cull in front of the bisection: the solid lies inside the ball (centre, rho = sqrt(r^2 + h^2)), so with X_c the point of the
 // link's segment nearest the centre every point of the segment has g >= L = |X_c - centre| - rho - r_f; a trip with
 // L > d_act + 1e-4 (1 + |X_c - centre| + rho) (a hundred times the rounding of L) cannot qualify and is skipped; a NaN L does not
-// skip.  -DRMP2_CYLINDER_NO_CULL (tests/contact_cylinders_driver.cpp and tools/contact_cylinders_timing.py only) leaves it out.
+// skip.  -DRMP2_CYLINDER_NO_CULL (tests/contacts_driver.cpp and tools/contact_cylinders_timing.py only) leaves it out.
 struct NoCylinders {
   static constexpr bool kOn = false;
   static constexpr bool kList = false;
@@ -1073,11 +1073,20 @@ __host__ __device__ inline void dynamics_step_contacts_robot(const DevOp* ops, i
 }
 
 #if defined(__HIPCC__)
-// The step's one kernel: one lane per robot, one wave per block; the per-lane storage of the wave's 64 robots in LDS,
-// lane-interleaved (the plane rows go into the same candidate slots: no word more with PLANES).  LIST: every robot's own list over
-// a shared pool (csr_offset / csr_index; the lanes' trip counts and sphere addresses differ), else the shared table and both are
-// unused.  PLANES: planes [P][4] beside the spheres, read at uniform addresses, F the robot's frame count; else the three are
-// unused and the routines are instantiated with NoPlanes.
+// The kernels: one lane per robot, one wave per block; the per-lane storage of the wave's 64 robots in LDS, lane-interleaved.
+// Each keeps a parameter list of its own, scalars and __restrict__ pointers, and spells out the same twenty lines -- the rows, the
+// base acceleration, the sphere list span, the call -- for measured reasons (profiles/contacts_fold_timing.json):
+//  - one kernel over a by-value struct of all forms' arguments loses __restrict__ on the members; compiled for the cylinder units
+//    it moved register allocation and the scalar loads throughout;
+//  - a shared __device__ __forceinline__ lane body under these five parameter lists leaves every kernel's vector arithmetic,
+//    registers and LDS what they are and gives the same bits, but the tests of the optional outputs then compile to scalar branches,
+//    and on the MI355X the sphere, plane and self kernels ran 0.5 to 1.9 % slower, the cylinder and cylinder-list kernels over
+//    sphere lists 0.3 to 1 % (the capsule kernels over sphere lists 2 % faster, the rest inside the spread).
+//
+// The sphere and plane forms.  LIST: every robot's own list over a shared pool (csr_offset / csr_index; the lanes' trip counts and
+// sphere addresses differ), else the shared table and both are unused.  PLANES: planes [P][4] beside the spheres, read at uniform
+// addresses, F the robot's frame count (the plane rows go into the same candidate slots: no word more); else the three are unused
+// and the routines are instantiated with NoPlanes.
 template <int N, int SLOTS, bool LIST, bool PLANES>
 __global__ void __launch_bounds__(kWave)
 rmp2_dynamics_step_contacts_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
@@ -1114,9 +1123,8 @@ rmp2_dynamics_step_contacts_kernel(const DevProgram* __restrict__ prog, const fl
       status_out ? status_out + robot : nullptr, lds + threadIdx.x, kWave, list, len, pl);
 }
 
-// The capsule forms (rmp2_dynamics_step_contacts_capsules): the same robot routine with planes AND capsules on, behind a kernel
-// of their own, so that the argument list of the kernel above -- and with it the register allocation of its instantiations -- is
-// what it was.  capsules [C][8] beside the planes; P == 0 and C == 0 run it too.
+// The capsule forms (rmp2_dynamics_step_contacts_capsules): planes AND capsules on.  capsules [C][8] beside the planes; P == 0 and
+// C == 0 run it too.
 template <int N, int SLOTS, bool LIST>
 __global__ void __launch_bounds__(kWave)
 rmp2_dynamics_step_contacts_capsules_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
@@ -1152,9 +1160,8 @@ rmp2_dynamics_step_contacts_capsules_kernel(const DevProgram* __restrict__ prog,
       CapsuleTable{capsules, C, F, P});
 }
 
-// The self forms (rmp2_dynamics_step_contacts_self): the same robot routine with planes, capsules AND self pairs on, behind a
-// kernel of its own like the capsule forms.  self_slot / self_begin / self_rec: the handle's pair tables (SelfPairs), n_self pairs;
-// n_self == 0 reads none of them.
+// The self forms (rmp2_dynamics_step_contacts_self): planes, capsules AND self pairs on.  self_slot / self_begin / self_rec: the
+// handle's pair tables (SelfPairs), n_self pairs; n_self == 0 reads none of them.
 template <int N, int SLOTS, bool LIST>
 __global__ void __launch_bounds__(kWave)
 rmp2_dynamics_step_contacts_self_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
@@ -1192,9 +1199,9 @@ rmp2_dynamics_step_contacts_self_kernel(const DevProgram* __restrict__ prog, con
       CapsuleTable{capsules, C, F, P}, SelfPairs{self_slot, self_begin, self_rec, n_self, F, nullptr});
 }
 
-// The cylinder forms (rmp2_dynamics_step_contacts_cylinders): the same robot routine with planes, capsules, self pairs AND the
-// cylinder table on, behind a kernel of its own like the self forms.  cylinders [Y][8] (CylinderTable); Y == 0 reads nothing of it.
-// n_self == 0 (no pairs set, or the call's self_pairs flag 0) reads none of the pair tables.  No LDS beyond the self forms'.
+// The cylinder forms (rmp2_dynamics_step_contacts_cylinders): planes, capsules, self pairs AND the cylinder table on.  cylinders
+// [Y][8] (CylinderTable); Y == 0 reads nothing of it.  n_self == 0 (no pairs set, or the call's self_pairs flag 0) reads none of the
+// pair tables.  No LDS beyond the self forms'.
 template <int N, int SLOTS, bool LIST>
 __global__ void __launch_bounds__(kWave)
 rmp2_dynamics_step_contacts_cylinders_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax, float ay,
@@ -1235,8 +1242,8 @@ rmp2_dynamics_step_contacts_cylinders_kernel(const DevProgram* __restrict__ prog
 }
 
 // The cylinder-list forms (rmp2_dynamics_step_contacts_cylinder_lists): the cylinder forms with every robot's own list over the
-// pool cylinders [Y][8] (CylinderList; cyl_offset / cyl_index laid out as csr_offset / csr_index), behind a kernel of its own, so
-// that the cylinder forms' kernels are what they were.  LIST: the spheres' form, as everywhere.  No LDS beyond the self forms'.
+// pool cylinders [Y][8] (CylinderList; cyl_offset / cyl_index laid out as csr_offset / csr_index).  LIST: the spheres' form, as
+// everywhere.  No LDS beyond the self forms'.
 template <int N, int SLOTS, bool LIST>
 __global__ void __launch_bounds__(kWave)
 rmp2_dynamics_step_contacts_cylinder_lists_kernel(const DevProgram* __restrict__ prog, const float* __restrict__ inert, float ax,

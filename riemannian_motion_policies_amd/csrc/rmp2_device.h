@@ -211,7 +211,7 @@ __host__ __device__ __forceinline__ void point_cylinder(const float4 ra, const f
 // function of the point, so it is convex in s, and its derivative along the segment is n(s) . D with n the outward normal of the
 // nearest surface point -- monotone in s.  Bisection on its sign (24 halvings: the parameter to 6e-8) after the two end tests; every
 // step is one point_cylinder.  (No closed form: the rim case is a quartic.)  Host-compilable, like point_cylinder: the contact
-// step's cylinder trip (rmp2_contacts.h) runs it on the CPU in tests/contact_cylinders_driver.cpp.
+// step's cylinder trip (rmp2_contacts.h) runs it on the CPU in tests/contacts_driver.cpp.
 __host__ __device__ __forceinline__ void segment_cylinder(const float4 ra, const float4 rb, const float A[3], const float D[3],
                                                           float X[3], float Y[3], float n[3], float& sd) {
   auto at = [&](float s) {

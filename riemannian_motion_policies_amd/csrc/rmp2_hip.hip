@@ -1486,22 +1486,16 @@ void launch_dynamics_step_stops(const rmp2_handle* h, float* q, float* qd, const
   });
 }
 
-// The contact step's launchers (rmp2_contacts_tu.hip; the kernel and its routines are rmp2_contacts.h): [LIST][PLANES]
-constexpr decltype(&launch_contacts_table) kLaunchContacts[2][2] = {{launch_contacts_table, launch_contacts_table_planes},
-                                                                    {launch_contacts_lists, launch_contacts_lists_planes}};
-// ... and with capsule obstacles (planes on): [LIST]
-constexpr decltype(&launch_contacts_table_capsules) kLaunchContactsCapsules[2] = {launch_contacts_table_capsules,
-                                                                                  launch_contacts_lists_capsules};
-// ... and with the handle's self pairs as well: [LIST]
-constexpr decltype(&launch_contacts_table_self) kLaunchContactsSelf[2] = {launch_contacts_table_self, launch_contacts_lists_self};
-// ... and with flat-capped cylinder obstacles as well: [LIST]
-constexpr decltype(&launch_contacts_table_cylinders) kLaunchContactsCylinders[2] = {launch_contacts_table_cylinders,
-                                                                                    launch_contacts_lists_cylinders};
-// ... and with every robot's own cylinder list over a cylinder pool: [LIST] (the spheres' form)
-constexpr decltype(&launch_contacts_table_cylinder_lists) kLaunchContactsCylinderLists[2] = {launch_contacts_table_cylinder_lists,
-                                                                                             launch_contacts_lists_cylinder_lists};
+// The contact step's launchers (rmp2_contacts_tu.hip; the kernels and their routines are rmp2_contacts.h): [kernel family][LIST],
+// the families in the order each adds to the one before -- spheres, planes, capsules, self, cylinders, cylinder lists
+constexpr ContactLauncher* kLaunchContacts[6][2] = {{launch_contacts_table, launch_contacts_lists},
+                                                    {launch_contacts_table_planes, launch_contacts_lists_planes},
+                                                    {launch_contacts_table_capsules, launch_contacts_lists_capsules},
+                                                    {launch_contacts_table_self, launch_contacts_lists_self},
+                                                    {launch_contacts_table_cylinders, launch_contacts_lists_cylinders},
+                                                    {launch_contacts_table_cylinder_lists, launch_contacts_lists_cylinder_lists}};
 
-// The host path of the six contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
+// The host path of the seven contact entry points.  form: which of them is calling -- the checks are shared and run in one order;
 // each entry point keeps its `what` and its own rules (table: K <= RMP2_MAX_CONTACT_SPHERES; lists: both CSR arrays, the pool
 // aligned; planes: the CSR arrays both set or both null, P and the plane table; capsules: the planes' rules, C and the capsule
 // table; self: the capsules' rules, the pairs are the handle's).  The planes entry always runs a PLANES kernel, P == 0 included;
@@ -1513,88 +1507,81 @@ enum ContactForm {
   kContactsTable, kContactsLists, kContactsPlanes, kContactsCapsules, kContactsSelf, kContactsCylinders, kContactsCylinderLists
 };
 
-int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, float* q, float* qd, const float* u, int32_t drive,
-                       const float* tau_limit, const float* q_lower, const float* q_upper, const float* spheres, int32_t K,
-                       const int32_t* csr_offset, const int32_t* csr_index, const float* planes, int32_t P,
-                       const float* capsules, int32_t C, float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out,
-                       float* stop_out, float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
-                       int32_t R, void* stream, const float* cylinders = nullptr, int32_t Y = 0, int32_t self_pairs = 1,
-                       const int32_t* cyl_offset = nullptr, const int32_t* cyl_index = nullptr) {
+// The fields every contact entry point has, in the order its parameter list has them; the rest off (no lists, no tables, the
+// handle's self pairs on) for the entry to set by name.
+ContactCall contact_call(float* q, float* qd, const float* u, const float* tau_limit, const float* q_lower, const float* q_upper,
+                         const float* spheres, int32_t K, float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out,
+                         float* stop_out, float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
+                         int32_t R) {
+  ContactCall c{};
+  c.q = q, c.qd = qd, c.u = u, c.lim = tau_limit, c.qlo = q_lower, c.qhi = q_upper;
+  c.spheres = spheres, c.K = K, c.d_act = d_act, c.dt = dt, c.substeps = substeps, c.self_pairs = 1;
+  c.qdd_out = qdd_out, c.tau_out = tau_out, c.stop_out = stop_out, c.contact_out = contact_out, c.lambda_out = contact_lambda;
+  c.pair_out = contact_pair, c.status_out = status_out, c.R = R;
+  return c;
+}
+
+// c: the call as its entry point filled it (contact_call and the entry's own fields), accel apart, which follows drive here.
+int contacts_step_impl(rmp2_handle* h, const char* what, ContactForm form, int32_t drive, ContactCall c, void* stream) {
   if (!h) return RMP2_ERR_INVALID_ARGUMENT;
   const std::string w = what;
-  if (int rc = step_args_check(h, what, drive, substeps, dt)) return rc;
+  if (int rc = step_args_check(h, what, drive, c.substeps, c.dt)) return rc;
   const bool cylinder_lists = form == kContactsCylinderLists;   // (the cylinders call's rules; the pool's cap on Y)
   const bool with_cylinders = form == kContactsCylinders || cylinder_lists;   // (the self call's rules; always a cylinder kernel, Y == 0 included)
   const bool with_self = form == kContactsSelf || with_cylinders;   // (the capsules' rules; always a self kernel, no pairs set included)
   const bool with_capsules = form == kContactsCapsules || with_self;
   const bool with_planes = form == kContactsPlanes || with_capsules;
-  if (with_planes && (csr_offset != nullptr) != (csr_index != nullptr))
+  if (with_planes && (c.csr_offset != nullptr) != (c.csr_index != nullptr))
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": csr_offset and csr_index go together (both null: the shared table)");
-  const bool lists = form == kContactsLists || (with_planes && csr_offset);
+  const bool lists = form == kContactsLists || (with_planes && c.csr_offset);
   const int k_max = lists ? RMP2_MAX_CONTACT_POOL : RMP2_MAX_CONTACT_SPHERES;
-  if (K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": K < 0");
-  if (K > k_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": K > " + std::to_string(k_max));
-  if (lists && K > 0 && spheres && ((uintptr_t)spheres & 15u))
+  if (c.K < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": K < 0");
+  if (c.K > k_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": K > " + std::to_string(k_max));
+  if (lists && c.K > 0 && c.spheres && ((uintptr_t)c.spheres & 15u))
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the pool must be 16-byte aligned");
   if (with_planes) {
-    if (P < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": P < 0");
-    if (P > RMP2_MAX_CONTACT_PLANES)
+    if (c.P < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": P < 0");
+    if (c.P > RMP2_MAX_CONTACT_PLANES)
       return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": P > " + std::to_string(RMP2_MAX_CONTACT_PLANES));
-    if (P > 0 && !planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null plane table with P > 0");
-    if (P > 0 && ((uintptr_t)planes & 15u))
+    if (c.P > 0 && !c.planes) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null plane table with P > 0");
+    if (c.P > 0 && ((uintptr_t)c.planes & 15u))
       return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the plane table must be 16-byte aligned");
   }
   if (with_capsules) {
-    if (C < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": C < 0");
-    if (C > RMP2_MAX_OBSTACLE_CAPSULES)
+    if (c.C < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": C < 0");
+    if (c.C > RMP2_MAX_OBSTACLE_CAPSULES)
       return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": C > " + std::to_string(RMP2_MAX_OBSTACLE_CAPSULES));
-    if (C > 0 && !capsules) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null capsule table with C > 0");
-    if (C > 0 && ((uintptr_t)capsules & 15u))
+    if (c.C > 0 && !c.capsules) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null capsule table with C > 0");
+    if (c.C > 0 && ((uintptr_t)c.capsules & 15u))
       return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the capsule table must be 16-byte aligned");
   }
   if (with_cylinders) {
-    if (Y < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y < 0");
+    if (c.Y < 0) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y < 0");
     const int y_max = cylinder_lists ? RMP2_MAX_CYLINDER_POOL : RMP2_MAX_OBSTACLE_CYLINDERS;
-    if (Y > y_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y > " + std::to_string(y_max));
+    if (c.Y > y_max) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": Y > " + std::to_string(y_max));
     const std::string table = cylinder_lists ? "cylinder pool" : "cylinder table";
-    if (Y > 0 && !cylinders) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null " + table + " with Y > 0");
-    if (Y > 0 && ((uintptr_t)cylinders & 15u))
+    if (c.Y > 0 && !c.cylinders) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": null " + table + " with Y > 0");
+    if (c.Y > 0 && ((uintptr_t)c.cylinders & 15u))
       return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": the " + table + " must be 16-byte aligned");
-    if (self_pairs != 0 && self_pairs != 1) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": self_pairs must be 0 or 1");
+    if (c.self_pairs != 0 && c.self_pairs != 1) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": self_pairs must be 0 or 1");
   }
-  if (!std::isfinite(d_act) || d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": d_act must be finite and >= 0");
+  if (!std::isfinite(c.d_act) || c.d_act < 0.f) return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": d_act must be finite and >= 0");
   if (h->contact_n == 0)
     return fail(h, RMP2_ERR_INVALID_ARGUMENT, w + ": no contact capsules on this handle (call rmp2_set_contact_capsules first)");
   if (h->n_template > 9)
     return fail(h, RMP2_ERR_UNSUPPORTED,
                 w + ": robots of more than 9 dofs are not supported (this one has " + std::to_string(h->n_dof) + ")");
   bool launch;
-  const bool others_ok = (q_lower != nullptr) == (q_upper != nullptr) && (K == 0 || spheres) &&
-                         (form != kContactsLists || (csr_offset && csr_index)) && (!cylinder_lists || (cyl_offset && cyl_index));
-  if (int rc = step_rows_check(h, what, q, qd, u, others_ok, R, launch)) return rc;
+  const bool others_ok = (c.qlo != nullptr) == (c.qhi != nullptr) && (c.K == 0 || c.spheres) &&
+                         (form != kContactsLists || (c.csr_offset && c.csr_index)) && (!cylinder_lists || (c.cyl_offset && c.cyl_index));
+  if (int rc = step_rows_check(h, what, c.q, c.qd, c.u, others_ok, c.R, launch)) return rc;
   if (!launch) return RMP2_OK;
   // (N in {2, 9} by the handle's template size, SLOTS by its program)
-  if (cylinder_lists)
-    kLaunchContactsCylinderLists[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
-                                        csr_index, planes, P, capsules, C, cylinders, Y, cyl_offset, cyl_index, self_pairs, d_act, dt,
-                                        substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R,
-                                        (hipStream_t)stream);
-  else if (with_cylinders)
-    kLaunchContactsCylinders[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
-                                    csr_index, planes, P, capsules, C, cylinders, Y, self_pairs, d_act, dt, substeps, qdd_out, tau_out,
-                                    stop_out, contact_out, contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
-  else if (with_self)
-    kLaunchContactsSelf[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset, csr_index,
-                               planes, P, capsules, C, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out, contact_lambda,
-                               contact_pair, status_out, R, (hipStream_t)stream);
-  else if (with_capsules)
-    kLaunchContactsCapsules[lists](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
-                                   csr_index, planes, P, capsules, C, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
-                                   contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
-  else
-    kLaunchContacts[lists][with_planes](h, q, qd, u, drive == RMP2_DRIVE_ACCEL, tau_limit, q_lower, q_upper, spheres, K, csr_offset,
-                                        csr_index, planes, P, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
-                                        contact_lambda, contact_pair, status_out, R, (hipStream_t)stream);
+  c.accel = drive == RMP2_DRIVE_ACCEL;
+  static_assert(kContactsPlanes + 1 == kContactsCapsules && kContactsCapsules + 1 == kContactsSelf && kContactsSelf + 1 == kContactsCylinders &&
+                    kContactsCylinders + 1 == kContactsCylinderLists && kContactsCylinderLists - kContactsPlanes + 1 == 5,
+                "the forms from kContactsPlanes on stand in the order of kLaunchContacts' rows 1 .. 5");
+  kLaunchContacts[with_planes ? form - kContactsPlanes + 1 : 0][lists](h, c, (hipStream_t)stream);
   HIP_TRY(h, hipGetLastError());
   return RMP2_OK;
 }
@@ -3218,9 +3205,9 @@ int rmp2_dynamics_step_contacts(rmp2_handle* h, float* q, float* qd, const float
                                 const float* q_lower, const float* q_upper, const float* spheres, int32_t K, float d_act, float dt,
                                 int32_t substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,
                                 float* contact_lambda, int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
-  return contacts_step_impl(h, "dynamics step with contacts", kContactsTable, q, qd, u, drive, tau_limit, q_lower, q_upper, spheres, K,
-                            nullptr, nullptr, nullptr, 0, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out, contact_out,
-                            contact_lambda, contact_pair, status_out, R, stream);
+  ContactCall c = contact_call(q, qd, u, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                               contact_out, contact_lambda, contact_pair, status_out, R);
+  return contacts_step_impl(h, "dynamics step with contacts", kContactsTable, drive, c, stream);
 }
 
 int rmp2_dynamics_step_contacts_lists(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
@@ -3228,9 +3215,10 @@ int rmp2_dynamics_step_contacts_lists(rmp2_handle* h, float* q, float* qd, const
                                       const int32_t* csr_offset, const int32_t* csr_index, float d_act, float dt, int32_t substeps,
                                       float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
                                       int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
-  return contacts_step_impl(h, "dynamics step with contact lists", kContactsLists, q, qd, u, drive, tau_limit, q_lower, q_upper,
-                            spheres, K, csr_offset, csr_index, nullptr, 0, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out,
-                            contact_out, contact_lambda, contact_pair, status_out, R, stream);
+  ContactCall c = contact_call(q, qd, u, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                               contact_out, contact_lambda, contact_pair, status_out, R);
+  c.csr_offset = csr_offset, c.csr_index = csr_index;
+  return contacts_step_impl(h, "dynamics step with contact lists", kContactsLists, drive, c, stream);
 }
 
 int rmp2_dynamics_step_contacts_planes(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
@@ -3239,9 +3227,11 @@ int rmp2_dynamics_step_contacts_planes(rmp2_handle* h, float* q, float* qd, cons
                                        float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out, float* stop_out,
                                        float* contact_out, float* contact_lambda, int32_t* contact_pair, uint32_t* status_out,
                                        int32_t R, void* stream) {
-  return contacts_step_impl(h, "dynamics step with contact planes", kContactsPlanes, q, qd, u, drive, tau_limit, q_lower, q_upper,
-                            spheres, K, csr_offset, csr_index, planes, P, nullptr, 0, d_act, dt, substeps, qdd_out, tau_out, stop_out,
-                            contact_out, contact_lambda, contact_pair, status_out, R, stream);
+  ContactCall c = contact_call(q, qd, u, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                               contact_out, contact_lambda, contact_pair, status_out, R);
+  c.csr_offset = csr_offset, c.csr_index = csr_index;
+  c.planes = planes, c.P = P;
+  return contacts_step_impl(h, "dynamics step with contact planes", kContactsPlanes, drive, c, stream);
 }
 
 int rmp2_dynamics_step_contacts_capsules(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
@@ -3250,9 +3240,12 @@ int rmp2_dynamics_step_contacts_capsules(rmp2_handle* h, float* q, float* qd, co
                                          const float* obstacle_capsules, int32_t C, float d_act, float dt, int32_t substeps,
                                          float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
                                          int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
-  return contacts_step_impl(h, "dynamics step with contact capsules", kContactsCapsules, q, qd, u, drive, tau_limit, q_lower,
-                            q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps,
-                            qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream);
+  ContactCall c = contact_call(q, qd, u, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                               contact_out, contact_lambda, contact_pair, status_out, R);
+  c.csr_offset = csr_offset, c.csr_index = csr_index;
+  c.planes = planes, c.P = P;
+  c.capsules = obstacle_capsules, c.C = C;
+  return contacts_step_impl(h, "dynamics step with contact capsules", kContactsCapsules, drive, c, stream);
 }
 
 int rmp2_dynamics_step_contacts_self(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
@@ -3261,9 +3254,12 @@ int rmp2_dynamics_step_contacts_self(rmp2_handle* h, float* q, float* qd, const 
                                      const float* obstacle_capsules, int32_t C, float d_act, float dt, int32_t substeps,
                                      float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
                                      int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
-  return contacts_step_impl(h, "dynamics step with self contacts", kContactsSelf, q, qd, u, drive, tau_limit, q_lower, q_upper,
-                            spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps, qdd_out,
-                            tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream);
+  ContactCall c = contact_call(q, qd, u, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                               contact_out, contact_lambda, contact_pair, status_out, R);
+  c.csr_offset = csr_offset, c.csr_index = csr_index;
+  c.planes = planes, c.P = P;
+  c.capsules = obstacle_capsules, c.C = C;
+  return contacts_step_impl(h, "dynamics step with self contacts", kContactsSelf, drive, c, stream);
 }
 
 int rmp2_dynamics_step_contacts_cylinders(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive, const float* tau_limit,
@@ -3273,10 +3269,13 @@ int rmp2_dynamics_step_contacts_cylinders(rmp2_handle* h, float* q, float* qd, c
                                           int32_t self_pairs, float d_act, float dt, int32_t substeps, float* qdd_out, float* tau_out,
                                           float* stop_out, float* contact_out, float* contact_lambda, int32_t* contact_pair,
                                           uint32_t* status_out, int32_t R, void* stream) {
-  return contacts_step_impl(h, "dynamics step with contact cylinders", kContactsCylinders, q, qd, u, drive, tau_limit, q_lower,
-                            q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps, qdd_out,
-                            tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream, cylinders, Y,
-                            self_pairs);
+  ContactCall c = contact_call(q, qd, u, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                               contact_out, contact_lambda, contact_pair, status_out, R);
+  c.csr_offset = csr_offset, c.csr_index = csr_index;
+  c.planes = planes, c.P = P;
+  c.capsules = obstacle_capsules, c.C = C;
+  c.cylinders = cylinders, c.Y = Y, c.self_pairs = self_pairs;
+  return contacts_step_impl(h, "dynamics step with contact cylinders", kContactsCylinders, drive, c, stream);
 }
 
 int rmp2_dynamics_step_contacts_cylinder_lists(rmp2_handle* h, float* q, float* qd, const float* u, int32_t drive,
@@ -3287,10 +3286,14 @@ int rmp2_dynamics_step_contacts_cylinder_lists(rmp2_handle* h, float* q, float* 
                                                int32_t self_pairs, float d_act, float dt, int32_t substeps, float* qdd_out,
                                                float* tau_out, float* stop_out, float* contact_out, float* contact_lambda,
                                                int32_t* contact_pair, uint32_t* status_out, int32_t R, void* stream) {
-  return contacts_step_impl(h, "dynamics step with contact cylinder lists", kContactsCylinderLists, q, qd, u, drive, tau_limit,
-                            q_lower, q_upper, spheres, K, csr_offset, csr_index, planes, P, obstacle_capsules, C, d_act, dt, substeps,
-                            qdd_out, tau_out, stop_out, contact_out, contact_lambda, contact_pair, status_out, R, stream, cylinders, Y,
-                            self_pairs, cyl_offset, cyl_index);
+  ContactCall c = contact_call(q, qd, u, tau_limit, q_lower, q_upper, spheres, K, d_act, dt, substeps, qdd_out, tau_out, stop_out,
+                               contact_out, contact_lambda, contact_pair, status_out, R);
+  c.csr_offset = csr_offset, c.csr_index = csr_index;
+  c.planes = planes, c.P = P;
+  c.capsules = obstacle_capsules, c.C = C;
+  c.cylinders = cylinders, c.Y = Y, c.self_pairs = self_pairs;
+  c.cyl_offset = cyl_offset, c.cyl_index = cyl_index;
+  return contacts_step_impl(h, "dynamics step with contact cylinder lists", kContactsCylinderLists, drive, c, stream);
 }
 
 }  // extern "C"

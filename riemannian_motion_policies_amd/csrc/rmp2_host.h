@@ -181,47 +181,39 @@ bool launch_hex_n9(const rmp2_handle* h, const float* q, const float* qd, const 
                    const OutArgs& out, const RolloutArgs& ro, int R, hipStream_t s);
 bool launch_hex_n16(const rmp2_handle* h, const float* q, const float* qd, const float* goal, int gs, const ObsArgs& o,
                     const OutArgs& out, const RolloutArgs& ro, int R, hipStream_t s);
-// rmp2_contacts_tu.hip: the contact step's kernels (rmp2_contacts.h), one object per form -- [LIST][PLANES]: the shared sphere
-// table or per-robot lists over a pool, without or with half-spaces beside the spheres.  One signature; a form ignores the
-// arguments it has no use for (csr_offset / csr_index without LIST; planes / P without PLANES).
-#define RMP2_DECL_CONTACTS(NAME)                                                                                                  \
-  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
-            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
-            int P, float d_act, float dt, int substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out,      \
-            float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
-RMP2_DECL_CONTACTS(launch_contacts_table);
-RMP2_DECL_CONTACTS(launch_contacts_table_planes);
-RMP2_DECL_CONTACTS(launch_contacts_lists);
-RMP2_DECL_CONTACTS(launch_contacts_lists_planes);
-// the capsule forms (rmp2_dynamics_step_contacts_capsules): planes and capsule obstacles on, [LIST]; two more objects
-#define RMP2_DECL_CONTACTS_CAPSULES(NAME)                                                                                         \
-  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
-            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
-            int P, const float* capsules, int C, float d_act, float dt, int substeps, float* qdd_out, float* tau_out,             \
-            float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
-RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_capsules);
-RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_capsules);
-// the self forms (rmp2_dynamics_step_contacts_self): planes, capsule obstacles and the handle's self pairs on, [LIST]; two more
-RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_table_self);
-RMP2_DECL_CONTACTS_CAPSULES(launch_contacts_lists_self);
-// the cylinder forms (rmp2_dynamics_step_contacts_cylinders): all of those and the cylinder table on, [LIST]; two more.
-// self_pairs: 0 -- the handle's self pairs are left out, none of their tables is passed to the kernel
-#define RMP2_DECL_CONTACTS_CYLINDERS(NAME)                                                                                        \
-  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
-            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
-            int P, const float* capsules, int C, const float* cylinders, int Y, int self_pairs, float d_act, float dt,            \
-            int substeps, float* qdd_out, float* tau_out, float* stop_out, float* contact_out, float* lambda_out,                 \
-            int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
-RMP2_DECL_CONTACTS_CYLINDERS(launch_contacts_table_cylinders);
-RMP2_DECL_CONTACTS_CYLINDERS(launch_contacts_lists_cylinders);
-// the cylinder-list forms (rmp2_dynamics_step_contacts_cylinder_lists): the cylinder forms with every robot's own list over a
-// cylinder pool (cyl_offset / cyl_index), [LIST] still the spheres' form; two more
-#define RMP2_DECL_CONTACTS_CYLINDER_LISTS(NAME)                                                                                   \
-  void NAME(const rmp2_handle* h, float* q, float* qd, const float* u, int accel, const float* lim, const float* qlo,             \
-            const float* qhi, const float* spheres, int K, const int32_t* csr_offset, const int32_t* csr_index, const float* planes, \
-            int P, const float* capsules, int C, const float* cylinders, int Y, const int32_t* cyl_offset,                        \
-            const int32_t* cyl_index, int self_pairs, float d_act, float dt, int substeps, float* qdd_out, float* tau_out,        \
-            float* stop_out, float* contact_out, float* lambda_out, int32_t* pair_out, uint32_t* status_out, int R, hipStream_t s)
-RMP2_DECL_CONTACTS_CYLINDER_LISTS(launch_contacts_table_cylinder_lists);
-RMP2_DECL_CONTACTS_CYLINDER_LISTS(launch_contacts_lists_cylinder_lists);
+// One call of the contact step, whichever entry point made it: everything any form's launch needs.  A form ignores the fields it
+// has no use for (csr_offset / csr_index without LIST; planes / P in the sphere-only forms; ...).  Host only: the launchers spread
+// it into their kernel's own parameter list, it never reaches a kernel.
+struct ContactCall {
+  float *q, *qd;
+  const float* u;
+  int accel;
+  const float *lim, *qlo, *qhi;
+  const float* spheres;
+  int K;
+  const int32_t *csr_offset, *csr_index;
+  const float* planes;
+  int P;
+  const float* capsules;
+  int C;
+  const float* cylinders;
+  int Y;
+  const int32_t *cyl_offset, *cyl_index;
+  int self_pairs;   // the cylinder forms: 0 -- the handle's self pairs are left out, none of their tables is passed to the kernel
+  float d_act, dt;
+  int substeps;
+  float *qdd_out, *tau_out, *stop_out, *contact_out, *lambda_out;
+  int32_t* pair_out;
+  uint32_t* status_out;
+  int R;
+};
+// rmp2_contacts_tu.hip: the contact step's kernels (rmp2_contacts.h), one object and one launcher per form and sphere source
+// (table: the shared sphere table; lists: per-robot lists over a pool).
+using ContactLauncher = void(const rmp2_handle* h, const ContactCall& c, hipStream_t s);
+ContactLauncher launch_contacts_table, launch_contacts_lists;                  // spheres only
+ContactLauncher launch_contacts_table_planes, launch_contacts_lists_planes;    // ... and half-spaces
+ContactLauncher launch_contacts_table_capsules, launch_contacts_lists_capsules;   // ... and capsule obstacles
+ContactLauncher launch_contacts_table_self, launch_contacts_lists_self;        // ... and the handle's self pairs
+ContactLauncher launch_contacts_table_cylinders, launch_contacts_lists_cylinders;   // ... and the cylinder table
+ContactLauncher launch_contacts_table_cylinder_lists, launch_contacts_lists_cylinder_lists;   // ... as per-robot cylinder lists
 }  // namespace rmp2

@@ -168,7 +168,7 @@ def linearised_gaps(c, got_qd, pair, dt):
 
 
 def write_driver_input(path, c, substeps, dt, d_act, lists=None, **over):
-    """Input file of tests/contact_capsules_driver.cpp: contacts_reference.write_driver_input's (always with a plane section),
+    """Input file of tests/contacts_driver.cpp's capsule form: contacts_reference.write_driver_input's (always with a plane section),
     followed by int32 C, float capsules[C][8].  over: fields of the group replaced."""
     g = dict(c, **{k: v for k, v in over.items() if v is not None})
     CR.write_driver_input(path, g["t"], g["inert"], g["caps"], g["spheres"], d_act, g["q"], g["qd"], g["u"], g["drive"], g["lim"],

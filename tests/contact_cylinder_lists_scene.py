@@ -89,7 +89,7 @@ def rows(d, sel):
 
 
 def write_driver_input(path, c, substeps, dt, d_act, cyl_lists, lists=None, flag=1, **over):
-    """Input file of tests/contact_cylinder_lists_driver.cpp: contact_cylinders_reference.write_driver_input's followed by int32
+    """Input file of tests/contacts_driver.cpp's cylinder-list form: contact_cylinders_reference.write_driver_input's followed by int32
     cyl_offset [B + 1], int32 n_index, int32 cyl_index [n_index].  cyl_lists = (cyl_offset, cyl_index)."""
     YR.write_driver_input(path, c, substeps, dt, d_act, lists=lists, flag=flag, **over)
     off, idx = (np.ascontiguousarray(x, np.int32) for x in cyl_lists)

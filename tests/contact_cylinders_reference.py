@@ -224,7 +224,7 @@ def linearised_gaps(c, got_qd, pair, dt):
 
 
 def write_driver_input(path, c, substeps, dt, d_act, lists=None, flag=1, **over):
-    """Input file of tests/contact_cylinders_driver.cpp: contact_self_reference.write_driver_input's, followed by int32 Y, float
+    """Input file of tests/contacts_driver.cpp's cylinder form: contact_self_reference.write_driver_input's, followed by int32 Y, float
     cylinders[Y][8], int32 self_pairs (the call's flag).  over: fields of the group replaced."""
     g = dict(c, **{k: v for k, v in over.items() if v is not None})
     SR.write_driver_input(path, g, substeps, dt, d_act, lists=lists)

@@ -199,7 +199,7 @@ def pair_tables(table, pairs):
 
 
 def write_driver_input(path, c, substeps, dt, d_act, lists=None, **over):
-    """Input file of tests/contact_self_driver.cpp: contact_capsules_reference.write_driver_input's, followed by int32 n_pairs,
+    """Input file of tests/contacts_driver.cpp's self form: contact_capsules_reference.write_driver_input's, followed by int32 n_pairs,
     [int32 slot [n_ops], int32 begin [n_ops + 1], int32 rec [n_pairs][4]] where n_pairs > 0 (pair_tables).  over: fields of the
     group replaced."""
     g = dict(c, **{k: v for k, v in over.items() if v is not None})

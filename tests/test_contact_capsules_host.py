@@ -1,6 +1,6 @@
 """Capsule obstacles beside the spheres and the half-spaces (include/rmp2.h rmp2_dynamics_step_contacts_capsules) on the host:
 the scenes of tests/contact_capsules_scene.py meet their stated conditions; the fp32 envelope that the bounds are taken from; the
-capsule form of the device routine of rmp2_contacts.h run on the CPU through tests/contact_capsules_driver.cpp (also under the host
+capsule form of the device routine of rmp2_contacts.h run on the CPU through tests/contacts_driver.cpp (also under the host
 sanitizers, as a stand-alone program) against the fp64 reference of tests/contact_capsules_reference.py, and BIT FOR BIT against
 the planes, sphere and stops drivers where the contract promises it; pair indices, ties between the kinds, poisoning, the header,
 the bindings and urdf.capsule_obstacles / urdf.cylinders_as_capsules.  No GPU.
@@ -48,17 +48,17 @@ def slot_groups(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_capsules_driver.cpp", "contact_capsules_driver")
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver")
 
 
 @pytest.fixture(scope="module")
 def driver_san(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_capsules_driver.cpp", "contact_capsules_driver_san", SAN)
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver_san", SAN)
 
 
 @pytest.fixture(scope="module")
-def planes_driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver")
+def planes_driver(driver):
+    return driver
 
 
 @pytest.fixture(scope="module")
@@ -70,7 +70,8 @@ def run_capsules(exe, tmp_path, c, substeps=1, lists=None, d_act=D_ACT, **over):
     """The capsule driver on a group (fields replaced by the keywords: q, qd, u, caps, spheres, planes, capsules):
     contacts_reference.read_driver_output's dict.  A sanitizer report fails it: exit status 0 and nothing on stderr."""
     QR.write_driver_input(str(tmp_path / "in.bin"), c, substeps, DT, d_act, lists=lists, **over)
-    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "capsules"], capture_output=True, text=True,
+                       timeout=300)
     assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
     B = len(over["q"]) if over.get("q") is not None else len(c["q"])
     return CR.read_driver_output(str(tmp_path / "out.bin"), B, c["t"].n_dof)

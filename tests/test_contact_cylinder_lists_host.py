@@ -1,5 +1,5 @@
 """Per-robot cylinder lists over a shared cylinder pool (include/rmp2.h rmp2_dynamics_step_contacts_cylinder_lists) on the host: the
-cylinder-list form of the device routine of rmp2_contacts.h run on the CPU through tests/contact_cylinder_lists_driver.cpp (also
+cylinder-list form of the device routine of rmp2_contacts.h run on the CPU through tests/contacts_driver.cpp (also
 under the host sanitizers, as a stand-alone program, and built without the cull) on the list fleets of
 tests/contact_cylinder_lists_scene.py -- the catalogue and the slot catalogue of tests/contact_cylinders_scene.py with the cylinder
 tables of the groups that share every other table merged into one pool -- against the fp64 reference of
@@ -29,7 +29,7 @@ FLOATS = PH.FLOATS
 SAN = PH.SAN
 whole_lists, same, by = PH.whole_lists, PH.same, PH.by
 NONE_CYL = np.zeros((0, 8), np.float32)
-SOURCE = "contact_cylinder_lists_driver.cpp"
+SOURCE = "contacts_driver.cpp"
 
 
 @pytest.fixture(scope="module")
@@ -49,17 +49,17 @@ def fams(groups, slot_groups):
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    return S._build(tmp_path_factory, SOURCE, "contact_cylinder_lists_driver")
+    return S._build(tmp_path_factory, SOURCE, "contacts_driver")
 
 
 @pytest.fixture(scope="module")
 def driver_no_cull(tmp_path_factory):
-    return S._build(tmp_path_factory, SOURCE, "contact_cylinder_lists_driver_no_cull", ("-DRMP2_CYLINDER_NO_CULL",))
+    return S._build(tmp_path_factory, SOURCE, "contacts_driver_no_cull", ("-DRMP2_CYLINDER_NO_CULL",))
 
 
 @pytest.fixture(scope="module")
 def driver_san(tmp_path_factory):
-    return S._build(tmp_path_factory, SOURCE, "contact_cylinder_lists_driver_san", SAN)
+    return S._build(tmp_path_factory, SOURCE, "contacts_driver_san", SAN)
 
 
 def run_lists(exe, tmp_path, c, cyl_lists, substeps=1, lists=None, flag=1, table=False, **over):
@@ -69,7 +69,7 @@ def run_lists(exe, tmp_path, c, cyl_lists, substeps=1, lists=None, flag=1, table
     if isinstance(cyl_lists, list):
         cyl_lists = LS.csr(cyl_lists)
     LS.write_driver_input(str(tmp_path / "in.bin"), c, substeps, DT, D_ACT, cyl_lists, lists=lists, flag=flag, **over)
-    argv = [exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")] + (["table"] if table else [])
+    argv = [exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "cylinders" if table else "cylinder_lists"]
     p = subprocess.run(argv, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
     B = len(over["q"]) if over.get("q") is not None else len(c["q"])

@@ -1,7 +1,7 @@
 """Exact flat-capped cylinder obstacles in the contact step (include/rmp2.h rmp2_dynamics_step_contacts_cylinders) on the host: the
 scenes of tests/contact_cylinders_scene.py meet their stated conditions; the reference pinned against a brute-force scan; the fp32
 envelope that the bounds are taken from; the cylinder form of the device routine of rmp2_contacts.h run on the CPU through
-tests/contact_cylinders_driver.cpp (also under the host sanitizers, as a stand-alone program, and built without the cull) against
+tests/contacts_driver.cpp (also under the host sanitizers, as a stand-alone program, and built without the cull) against
 the fp64 reference of tests/contact_cylinders_reference.py, and BIT FOR BIT against the self, capsules and stops drivers where the
 contract promises it; pair indices, the five-way tie, the header, the bindings and urdf.cylinder_obstacles.  No GPU.
 
@@ -48,22 +48,22 @@ def slot_groups(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_cylinders_driver.cpp", "contact_cylinders_driver")
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver")
 
 
 @pytest.fixture(scope="module")
 def driver_no_cull(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_cylinders_driver.cpp", "contact_cylinders_driver_no_cull", ("-DRMP2_CYLINDER_NO_CULL",))
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver_no_cull", ("-DRMP2_CYLINDER_NO_CULL",))
 
 
 @pytest.fixture(scope="module")
 def driver_san(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_cylinders_driver.cpp", "contact_cylinders_driver_san", SAN)
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver_san", SAN)
 
 
 @pytest.fixture(scope="module")
-def self_driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_self_driver.cpp", "contact_self_driver")
+def self_driver(driver):
+    return driver
 
 
 @pytest.fixture(scope="module")
@@ -72,15 +72,16 @@ def stops_driver(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def capsules_driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_capsules_driver.cpp", "contact_capsules_driver")
+def capsules_driver(driver):
+    return driver
 
 
 def run_cyl(exe, tmp_path, c, substeps=1, lists=None, d_act=D_ACT, flag=1, **over):
     """The cylinders driver on a group (fields replaced by the keywords): contacts_reference.read_driver_output's dict.  A
     sanitizer report fails it: exit status 0 and nothing on stderr."""
     YR.write_driver_input(str(tmp_path / "in.bin"), c, substeps, DT, d_act, lists=lists, flag=flag, **over)
-    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "cylinders"], capture_output=True, text=True,
+                       timeout=300)
     assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
     B = len(over["q"]) if over.get("q") is not None else len(c["q"])
     return CR.read_driver_output(str(tmp_path / "out.bin"), B, c["t"].n_dof)

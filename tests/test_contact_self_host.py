@@ -1,6 +1,6 @@
 """Self contacts between the robot's own link capsules (include/rmp2.h rmp2_dynamics_step_contacts_self) on the host: the scenes
 of tests/contact_self_scene.py meet their stated conditions; the fp32 envelope that the bounds are taken from; the self form of
-the device routine of rmp2_contacts.h run on the CPU through tests/contact_self_driver.cpp (also under the host sanitizers, as a
+the device routine of rmp2_contacts.h run on the CPU through tests/contacts_driver.cpp (also under the host sanitizers, as a
 stand-alone program) against the fp64 reference of tests/contact_self_reference.py, and BIT FOR BIT against the capsules driver
 where the contract promises it; pair indices, the tie between the four kinds, the header, the bindings and
 urdf.contact_self_pairs.  No GPU.
@@ -51,24 +51,24 @@ def slot_groups(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_self_driver.cpp", "contact_self_driver")
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver")
 
 
 @pytest.fixture(scope="module")
 def driver_san(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_self_driver.cpp", "contact_self_driver_san", SAN)
+    return S._build(tmp_path_factory, "contacts_driver.cpp", "contacts_driver_san", SAN)
 
 
 @pytest.fixture(scope="module")
-def capsules_driver(tmp_path_factory):
-    return S._build(tmp_path_factory, "contact_capsules_driver.cpp", "contact_capsules_driver")
+def capsules_driver(driver):
+    return driver
 
 
 def run_self(exe, tmp_path, c, substeps=1, lists=None, d_act=D_ACT, **over):
     """The self driver on a group (fields replaced by the keywords: q, qd, u, caps, spheres, planes, capsules, pairs):
     contacts_reference.read_driver_output's dict.  A sanitizer report fails it: exit status 0 and nothing on stderr."""
     SR.write_driver_input(str(tmp_path / "in.bin"), c, substeps, DT, d_act, lists=lists, **over)
-    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "self"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
     B = len(over["q"]) if over.get("q") is not None else len(c["q"])
     return CR.read_driver_output(str(tmp_path / "out.bin"), B, c["t"].n_dof)

@@ -480,7 +480,8 @@ def run_driver(exe, tmp_path, c, substeps=1, spheres=None, limits="case", d_act=
     CR.write_driver_input(str(tmp_path / "in.bin"), c["t"], c["inert"], c["caps"] if caps is None else caps,
                           c["spheres"] if spheres is None else spheres, d_act, q, qd, u, c["drive"], c["lim"],
                           c["limits"] if limits == "case" else limits, DT, substeps, c["g"], lists=lists, planes=planes)
-    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "contacts"], capture_output=True, text=True,
+                       timeout=300)
     assert p.returncode == 0 and p.stderr == "", (p.returncode, p.stderr[-2000:])
     return CR.read_driver_output(str(tmp_path / "out.bin"), len(q), c["t"].n_dof)
 

@@ -3,8 +3,8 @@ rmp2_dynamics_step_contacts_cylinder_lists) against the cylinders call, on the w
 tools/contact_timing_common.py (the fleet, the timing loop, one process per measurement) and with the scene of
 tools/contact_cylinders_timing.py's leg (c).  Prints ONE JSON line (profiles/contact_cylinder_lists_timing.json).  Per fleet size:
   (a) `cyl_us`: the existing rmp2_dynamics_step_contacts_cylinders, the seven configs.EXP06_CYLINDERS in place, the workload's
-      touching start states, self pairs on.  With --parent-lib this leg alternates between the parent's library and this build
-      (`cyl_us_parent`, `cyl_us_this`, `cyl_us_ok`; `cyl_bits_as_parent`): the code objects are the parent's.
+      touching start states, self pairs on.  With --parent-lib this leg, (d) and (e) alternate between the parent's library and this
+      build (`cyl_us_parent`, `cyl_us_this`, `cyl_us_ok`, `cyl_bits_as_parent`; likewise `scenes_*` and `uneven_*`).
   (b) `whole_us`: the new call, every robot listing 0 .. 6 of that table.  `same_results`: the final state and status have (a)'s
       bits; `same_flags`: the status flags (status & 0xff) are (a)'s -- what is promised against the table form's kernels.
   (c) `own_us`: the new call, every robot its own 7-record slice of an R x 7 pool of copies.  `own_same_results`: (b)'s bits, asserted
@@ -165,6 +165,7 @@ def leg_uneven(c):
     lists, sphere_lists = (ints(c, off), ints(c, idx)), (ints(c, soff), ints(c, sidx))
     cyl = torch.from_numpy(pool).to(c.dev)
     c.time("uneven_us", lambda: call(c, cyl, lists, sphere_lists))
+    c.final("uneven_bits", lambda: call(c, cyl, lists, sphere_lists))
     after(c, "uneven")
     c.row["mean_list_uneven"] = round(float(n.mean()), 2)
 
@@ -173,8 +174,9 @@ LEGS = {"table": leg_table, "whole": leg_whole, "own": leg_own, "scenes": leg_sc
 parent_lib, rounds, child, steps, reps = T.parse(__doc__)
 if child is not None:
     T.main(__file__, "contact_cylinder_lists_timing", LEGS, __doc__)          # (measures the leg, prints its rows and exits)
-result = T.main(__file__, "contact_cylinder_lists_timing", {"table": leg_table}, __doc__)          # (a): alternating with the parent's library
-for name in ("whole", "own", "scenes", "uneven"):          # (b) .. (e): this build only
+# (a), (d), (e): alternating with the parent's library -- the cylinder kernels, and the list kernels over table and list spheres
+result = T.main(__file__, "contact_cylinder_lists_timing", {k: LEGS[k] for k in ("table", "scenes", "uneven")}, __doc__)
+for name in ("whole", "own"):          # (b), (c): this build only
     for row, got in zip(result["sizes"], T.run_child(__file__, name, steps, reps)):
         row.update({k: v for k, v in got.items() if k != "robots"})
 result["cylinders"] = 7

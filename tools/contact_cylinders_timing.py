@@ -124,6 +124,7 @@ def leg_capsules(c):
     c.eng.set_contact_self_pairs(U.contact_self_pairs(c.table))
     oc = torch.from_numpy(np.concatenate([far_capsules(), U.cylinders_as_capsules(cylinders(False), "covering")])).to(c.dev)
     c.time("capsules_us", lambda: call(c, oc))
+    c.final("capsules_bits", lambda: call(c, oc))
     fractions(c, "_capsules")
 
 

@@ -24,6 +24,7 @@ def far(c):
     tab = c.spheres.clone()
     tab[:, 0] += 50.0
     c.time("contacts_far_us", lambda: call(c, tab))
+    c.final("contacts_far_bits", lambda: call(c, tab))
     assert int((c.status & 12).max()) == 0
 
 
