@@ -41,7 +41,10 @@ struct DevOp {
 static_assert(offsetof(DevOp, axis) % 16 == 0 && offsetof(DevOp, Tc) % 16 == 0, "DevOp: {axis, ctl} and Tc are fetched as float4");
 
 struct DevLeaf {
-  // head: fetched with ONE 64-byte scalar load (s_load_dwordx16)
+  // head (kind .. P[11]): 64 bytes, copied as a LeafHead.  NOT one 64-byte scalar load: the compiler fetches the fields a path
+  // reads, where it reads them -- the headline quad build issues taskmap, P[0..7] and P[8] in front of the branch on the task map and
+  // P[10], vb[0..5] behind it, two waited-for round trips per leaf (a compact record fetched in one burst was built and dropped:
+  // tools/experiments/README.md, "leaf heads")
   int32_t kind, taskmap, frame, goal_offset;
   float P[RMP2_MAX_PARAMS];
   float va[RMP2_MAX_DOF];
@@ -53,7 +56,8 @@ struct DevLeaf {
   int32_t pad_[1];  // 208 bytes
 };
 // the 64-byte head of a leaf / the 32-byte control block of an op, as value types: copying
-// them makes the compiler issue one wide scalar load instead of one dependent s_load per field
+// them lets the compiler merge the fields a path reads into wide scalar loads instead of one dependent s_load per field
+// (it does not fetch fields the path does not read, and it splits the copy at a branch: see DevLeaf)
 struct LeafHead {
   int32_t kind, taskmap, frame, goal_offset;
   float P[RMP2_MAX_PARAMS];

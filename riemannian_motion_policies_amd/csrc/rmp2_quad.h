@@ -35,6 +35,9 @@
 #ifndef RMP2_EXPLICIT_LOCAL
 #define RMP2_EXPLICIT_LOCAL 1  // explicit pairs: every lane evaluates the pairs it loaded (0: compacted + re-fetched; A/B)
 #endif
+#ifndef RMP2_ANC_AT_USE  // A/B knob (profiles/quad_leaf_head_ab.txt): the frame's dof mask tested behind the pair loop (kAncAtUse)
+#define RMP2_ANC_AT_USE 1
+#endif
 #ifndef RMP2_IDENT_FIRST
 #define RMP2_IDENT_FIRST 0  // measured: no gain (43.7 vs 43.6 us at 65 536 robots, 163.1 vs 160.2 at 262 144; tools/experiments/README.md)
 #endif
@@ -1375,6 +1378,12 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   // builds read {axis, ctl} from LDS into vector registers: a rotation there costs moves.)  The symmetric form only: config 2 at 65 536
   // robots -- the general form, one FK leaf behind the walk -- LOST with it, 25.50 -> 25.89 us, every run slower than every parent run.
   constexpr bool kWalkAhead = N == 9 && MINW >= 4 && !PT && !STAGE && SYM;
+  // the tests on the frame's dof mask (three row blocks, nine columns) made where the columns and the pull-back use them, on an opaque
+  // scalar copy of the mask taken behind the pair loop (see there) -- in the fast pass of the plain-step builds among those above whose
+  // pair loops take a sphere table: the ones that were timed with it (profiles/quad_leaf_head_ab.txt).  The careful pass and every other
+  // build keep their listings.
+  constexpr bool kAncAtUse = kWalkAhead && FLAVOR == kPlainStep && !CAP && RMP2_ANC_AT_USE &&
+                             (OBS == RMP2_OBS_SHARED_SPHERES || OBS == RMP2_OBS_RAGGED_SPHERES);
   const RolloutArgs ro = PLAIN ? RolloutArgs{1, 0, 0.f, nullptr, nullptr, 0} : ro_arg;
 #ifdef RMP2_STAMPS
   if (LEAN) out.M = nullptr;  // (diagnostic build: the stamps travel behind the f rows, so the plain build keeps that pointer)
@@ -2342,7 +2351,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
         float ptW = 0.f, ptRho[3] = {0.f, 0.f, 0.f}, ptQ[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ptTau[3] = {0.f, 0.f, 0.f};
         {
           const DevLeaf& lf = STAGE ? leaves[uni<STAGE>(fk_list[op.leaf_begin + li])] : prog->exec_leaves[op.leaf_begin + li];
-          LeafHead lh = *reinterpret_cast<const LeafHead*>(&lf);  // one 64-byte load
+          LeafHead lh = *reinterpret_cast<const LeafHead*>(&lf);  // (the fields the path reads: see DevLeaf)
           lh.kind = uni<STAGE>(lh.kind);
           lh.taskmap = uni<STAGE>(lh.taskmap);
           lh.goal_offset = uni<STAGE>(lh.goal_offset);
@@ -2562,6 +2571,14 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
           }
         }
         RMP2_SEG(1);  // target leaf (S, h) / the quad sums of a distance leaf
+        // The frame's dof mask as the columns and the pull-back test it.  kAncAtUse builds, fast pass: an opaque scalar copy taken HERE,
+        // behind the pair loop.  Tested on op.anc_mask itself, the twelve wave-uniform tests are loop invariants of the leaf loop: the
+        // compiler forms them at the top of the frame as twelve 64-bit lane masks (s_bitcmp1 / s_and + s_cmp, s_cselect_b64) and holds
+        // them, 24 scalar registers, through the pair loop -- in a kernel that parks a hundred scalar registers in vector lanes, where
+        // every frame then ended with eight v_readlane_b32 for what the masks had displaced.  On the copy each test is a scalar
+        // bit test and a branch on scc at its point of use.
+        uint32_t am = op.anc_mask;
+        if constexpr (kAncAtUse && pass == 0) asm volatile("" : "+s"(am));
         if (li == 0) {
           // the columns of MY rows, z_i x (p - o_i) resp. z_i, from the row-joint records read once per pass; inside a row block
           // that is formed, a row whose dof does not move the frame gets a zero column (no per-lane branch below).
@@ -2583,18 +2600,18 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
 #pragma unroll
           for (int m = 0; m < ROWS; ++m) {
             if constexpr (!kRegionPullback) {
-              if (MINW >= 2 && ((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) {  // wave-uniform: no dof of this row block moves
+              if (MINW >= 2 && ((am >> (kQuad * m)) & 0xfu) == 0u) {  // wave-uniform: no dof of this row block moves
                 mycol[m][0] = mycol[m][1] = mycol[m][2] = 0.f;                 // the frame (nor is its record used)
                 continue;
               }
             } else {
               // wave-uniform: no dof of this row block moves the frame -- neither its record nor its column is read then
               undefined3(mycol[m]);
-              if (MINW >= 2 && ((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) continue;
+              if (MINW >= 2 && ((am >> (kQuad * m)) & 0xfu) == 0u) continue;
             }
             // (bits >= n_dof are never set; bit 16 + j: the frame's origin lies on joint j's axis for every q, its column is
             //  exactly zero in the reference -- rmp2_hip.hip structural_lever_zeros -- and here too, instead of rounding noise)
-            const bool act = ((op.anc_mask & ~(op.anc_mask >> 16)) >> (sub + kQuad * m)) & 1u;
+            const bool act = ((am & ~(am >> 16)) >> (sub + kQuad * m)) & 1u;
             if (!kRowRecsInRegs && !kBatchedRowRecs) {
               const float4 j0 = rjs[m][0], j2 = rjs[m][2];
               rjz[m][0] = j2.y, rjz[m][1] = j2.z, rjz[m][2] = j2.w;
@@ -2628,7 +2645,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
 #pragma unroll
           for (int m = 0; m < ROWS; ++m) {
             u[m][0] = u[m][1] = u[m][2] = 0.f;
-            if (((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) continue;  // wave-uniform: no row of this block moves the frame
+            if (((am >> (kQuad * m)) & 0xfu) == 0u) continue;  // wave-uniform: no row of this block moves the frame
             if (kRank1 && hdr.rank1) {  // (wave-uniform) sets without an inertia leaf: componentwise accuracy matters there
               metric_times_column(S, r1, mycol[m], u[m]);
             } else {
@@ -2638,7 +2655,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
             }
             fv[m] += (double)dot3(mycol[m], h);
             if (PT) {  // attached-point leaf:  A_ij += c_j . (W c_i - rho x z_i) + z_j . (Q z_i - c_i x rho),  f_i += z_i . tau
-              const bool actz = pt_leaf && rjrev[m] && ((op.anc_mask >> (sub + kQuad * m)) & 1u);
+              const bool actz = pt_leaf && rjrev[m] && ((am >> (sub + kQuad * m)) & 1u);
 #pragma unroll
               for (int c = 0; c < 3; ++c) myz[m][c] = actz ? rjz[m][c] : 0.f;
               float rz[3], cr2[3];
@@ -2653,7 +2670,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
           }
 #pragma unroll
           for (int j = 0; j < N; ++j) {
-            if (!((op.anc_mask >> j) & 1u)) continue;  // wave-uniform: dof j does not move this frame (its column is 0)
+            if (!((am >> j) & 1u)) continue;  // wave-uniform: dof j does not move this frame (its column is 0)
             float cj[3];
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc) {
@@ -2685,7 +2702,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
           // and c1 first in block 2 -- and this shape keeps each of those choices (compared byte for byte, profiles/quad_pullback_ab.txt).
 #pragma unroll
           for (int m = 0; m < ROWS; ++m) {
-            if (((op.anc_mask >> (kQuad * m)) & 0xfu) == 0u) continue;  // wave-uniform: no row of this block moves the frame
+            if (((am >> (kQuad * m)) & 0xfu) == 0u) continue;  // wave-uniform: no row of this block moves the frame
             float u[3];
             if (kRank1 && hdr.rank1) {  // (wave-uniform) sets without an inertia leaf: componentwise accuracy matters there
               metric_times_column(S, r1, mycol[m], u);
@@ -2697,7 +2714,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
             fv[m] += (double)dot3(mycol[m], h);
 #pragma unroll
             for (int j = kQuad * m; j < N; ++j) {
-              if (!((op.anc_mask >> j) & 1u)) continue;  // wave-uniform: dof j does not move this frame (its column is 0)
+              if (!((am >> j) & 1u)) continue;  // wave-uniform: dof j does not move this frame (its column is 0)
               const float* cj = mycol[j >> 2];           // (column j lives in lane j & 3 as its local row j >> 2)
               float e;
               if ((j & 3) == 0) e = dot3_bcast<0>(u, cj);
