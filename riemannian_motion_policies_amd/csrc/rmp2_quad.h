@@ -35,6 +35,9 @@
 #ifndef RMP2_EXPLICIT_LOCAL
 #define RMP2_EXPLICIT_LOCAL 1  // explicit pairs: every lane evaluates the pairs it loaded (0: compacted + re-fetched; A/B)
 #endif
+#ifndef RMP2_LEAN_TAIL  // A/B knob (profiles/quad_tail_ab.txt): the general identity loop's tests from a laundered n_dof in the four-wave lean builds
+#define RMP2_LEAN_TAIL 1
+#endif
 #ifndef RMP2_ANC_AT_USE  // A/B knob (profiles/quad_leaf_head_ab.txt): the frame's dof mask tested behind the pair loop (kAncAtUse)
 #define RMP2_ANC_AT_USE 1
 #endif
@@ -1646,6 +1649,8 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   };
   constexpr bool sym = SYM;
   // ---- identity-task-map leaves (row layout): they need q and qd only, not the kinematics ------------------------
+  // (id_n_dof: n_dof, or for one call an opaque copy of it -- see identity_phase)
+  int id_n_dof = n_dof;
   auto identity_leaves = [&]() __attribute__((always_inline)) {
       for (int li = 0; li < n_id; ++li) {
         // (scalar-cache walk: the identity leaves follow the FK leaves in exec_leaves[], in execution order -- no index fetch)
@@ -1714,7 +1719,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
             const float dv = fabsf(qdj) - cutoff;
             const float sgn = (qdj > 0.f) ? 1.f : (qdj < 0.f ? -1.f : 0.f);
             const float acc = -fabsf(P[2] * dv) * sgn;
-            xo[m] = (i < n_dof && !(fabsf(qdj) < cutoff)) ? acc : 0.f;
+            xo[m] = (i < id_n_dof && !(fabsf(qdj) < cutoff)) ? acc : 0.f;
             const float ratio = fminf(dv, P[1] - 1e-6f) / P[1];
             dg[m] = P[3] / (1.0f - ratio * ratio);
             sx += xo[m];
@@ -1724,12 +1729,12 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   #pragma unroll
           for (int m = 0; m < ROWS; ++m) {
             const int i = sub + kQuad * m;
-            const bool row_ok = i < n_dof;
+            const bool row_ok = i < id_n_dof;
             const double wr = row_ok ? wd : 0.0;
             const double dd = row_ok ? (double)dg[m] - wd : 0.0;  // exact: A_ii = w + (d_i - w) = d_i
   #pragma unroll
             for (int j = 0; j < N; ++j)
-              if (j < n_dof && (j >= kQuad * m || !sym)) A[m][j] += wr;  // (sym: the blocks below the diagonal are not kept)
+              if (j < id_n_dof && (j >= kQuad * m || !sym)) A[m][j] += wr;  // (sym: the blocks below the diagonal are not kept)
   #pragma unroll
             for (int c = 0; c < kQuad; ++c)
               if (kQuad * m + c < N) A[m][kQuad * m + c] += (sub == c) ? dd : 0.0;
@@ -1764,7 +1769,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
               const float dl = (qj - lo_) * irange;
               const float d = fminf(du, dl);
               const float spline = c3 * (d * d * d) + c2 * (d * d) + 0.f * d + 1.0f;
-              cw_o[m] = (i < n_dof) ? (d > rr_ ? 0.f : spline) : 0.f;
+              cw_o[m] = (i < id_n_dof) ? (d > rr_ ? 0.f : spline) : 0.f;
               zeta_o[m] = (i < N) ? qdj * iqd_max : 0.f;
               s2 += zeta_o[m] * zeta_o[m];
               xdd_o[m] = -P[0] * qj - P[1] * qdj;
@@ -1787,7 +1792,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
             float v[N], s2 = 0.f;
   #pragma unroll
             for (int j = 0; j < N; ++j) {
-              v[j] = (j < n_dof) ? my_goal[lf.goal_offset + j] - my_q[j] : 0.f;
+              v[j] = (j < id_n_dof) ? my_goal[lf.goal_offset + j] - my_q[j] : 0.f;
               s2 += v[j] * v[j];
             }
             const float vn = sqrtf(s2);
@@ -1814,7 +1819,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   #pragma unroll
           for (int m = 0; m < ROWS; ++m) {
             const int i = sd + kQuad * m;
-            const bool row_ok = i < n_dof;
+            const bool row_ok = i < id_n_dof;
             // zeta_i of MY row: select from the statically indexed vector
             float zi = 0.f;
   #pragma unroll
@@ -1822,7 +1827,7 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
             float fi = 0.f;
   #pragma unroll
             for (int j = 0; j < N; ++j) {
-              if (j >= n_dof) continue;
+              if (j >= id_n_dof) continue;
               // JointLimitAvoidance scales COLUMN j by the limit weight of joint j, which is exactly 0 unless
               // that joint is inside its limit band: skip the column when that holds for the whole wave
               if (is_jla && !__any(cw[j] != 0.f)) continue;
@@ -1849,6 +1854,9 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
   // Compiled into the symmetric plain-step and plain-rollout builds of the 3..9-dof template; every other build, a robot with
   // fewer dofs than the template and a set with a dense identity leaf keep the general loop.
   constexpr bool kLeanId = N == 9 && !STAGE && SYM && LEAN;
+  // the fast pass of the four-wave builds that carry the structured loop: the cold general loop reads n_dof through a laundered copy
+  // (identity_phase; DESIGN 4.2, "Tail of the four-wave builds").  Every other build and the careful pass keep their listings.
+  constexpr bool kTailOpaqueDof = kLeanId && MINW >= 4 && RMP2_LEAN_TAIL != 0;
   auto identity_leaves_lean = [&]() __attribute__((always_inline)) {
     int sd = sub;  // (opaque copy: the four lane predicates below live in this phase only)
     if (MINW >= 3) asm volatile("" : "+v"(sd));
@@ -1977,7 +1985,16 @@ __device__ __forceinline__ void quad_step_body(const DevProgram* __restrict__ pr
         return;
       }
     }
-    identity_leaves();
+    if constexpr (kTailOpaqueDof) {
+      // (the general loop is the cold side here, and its tests of rows and columns against n_dof are loop invariants: left to the
+      // compiler they are formed in front of the branch above, as twenty 64-bit lane masks on the path of every step, parked in
+      // vector lanes for want of scalar registers.  From an opaque copy taken HERE they are formed where the loop uses them.)
+      asm volatile("" : "+s"(id_n_dof));
+      identity_leaves();
+      id_n_dof = n_dof;
+    } else {
+      identity_leaves();
+    }
   };
   // Phase order per wave.  The four waves of a SIMD start together and would walk their kinematic trees together -- the
   // one phase that is a dependent chain (latency bound, the SIMD issues next to nothing) -- and then crowd the issue-bound
